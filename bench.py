@@ -2,7 +2,7 @@
 """bench.py -- DBDE encode+decode round trip on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--content noise8|mixed|smooth|flat]
-                    [--frames B] [--concat] [--only] [--no-cpu] [--no-single] [--no-gather]
+                    [--frames B] [--concat] [--only] [--no-cpu] [--no-single] [--no-gather] [--dump-outputs DIR]
 
 One step = one pass of the hot path over one batch: encode B distinct synthetic U8 frames (resident in
 HBM) into DBDE frames, then decode them back to images.  `value` (frames/s) is always the configs[1]
@@ -24,7 +24,10 @@ overlapped with the encode of batch k+1; reported with and without the gather.
 N > 1: `python bench.py --gpus N` starts N ranks itself (torch.distributed.run, one per GPU, before any GPU
 call); launched under torchrun it uses the ranks it is given.  Frames are sharded by contiguous blocks
 (rank g owns frames [g*B, (g+1)*B) of each step): no collective on the data path, weak scaling.
-Rank 0 prints ONE JSON line.  `value` = frames all ranks round-tripped per second.
+Rank 0 prints ONE JSON line.  `value` = frames all ranks round-tripped per second; `ms_per_step` = wall time of one
+timed step of the headline (K steps between barriers, after W untimed ones).
+`--dump-outputs DIR`: after its timed steps the headline writes what its last step computed to DIR/*.npy (rank 0's
+frames; see dump_outputs).
 """
 import argparse
 import copy
@@ -184,6 +187,43 @@ def golden_sha(W, H, content):
             if e["W"] == W and e["H"] == H and e["mode"] == content}
 
 
+DUMP_SAMPLE = 1 << 22    # --dump-outputs: at most this many elements per array (4 Mi float32 = 16 MiB)
+
+
+def dump_outputs(dirname, torch, W, H, B, buf, lead, offs, sizes, images, results, scan_offsets=None):
+    """--dump-outputs DIR: what the timed path handed its caller in the last step, as DIR/<name>.npy.
+      images      decoded pixels, float32: all B*H*W of them in (B, H, W) when they fit DUMP_SAMPLE, else DUMP_SAMPLE
+                  pixels of the flattened batch at sorted positions drawn from a generator seeded with SEED
+      packed      the frames' packed bytes, float32: frame after frame when their total fits DUMP_SAMPLE, else
+                  DUMP_SAMPLE bytes of that concatenation at sorted positions drawn the same way
+      offsets, nbytes, results (and scan_offsets for the scanned stream): the per-frame arrays, float64
+    The inputs are the seeded synthetic frames, so two builds given the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(SEED)
+    dev = images.device
+    flat = images.reshape(-1)
+    if flat.numel() <= DUMP_SAMPLE:
+        img = images.reshape(B, H, W)
+    else:
+        idx = np.sort(rng.integers(0, flat.numel(), DUMP_SAMPLE))
+        img = flat[torch.from_numpy(idx).to(dev)]
+    o_h, s_h = offs.cpu().numpy(), sizes.cpu().numpy()
+    total = int(s_h.sum())
+    q = np.arange(total) if total <= DUMP_SAMPLE else np.sort(rng.integers(0, total, DUMP_SAMPLE))
+    ends = np.cumsum(s_h)
+    f = np.searchsorted(ends, q, side="right")                   # frame each position of the concatenation falls in
+    pos = lead + o_h[f] + (q - (ends[f] - s_h[f]))
+    assert pos.size == 0 or (pos.min() >= lead and pos.max() < buf.numel()), "packed sample outside the stream buffer"
+    packed = buf[torch.from_numpy(pos).to(dev)]
+    arrays = {"images": img.to(torch.float32), "packed": packed.to(torch.float32),
+              "offsets": offs.to(torch.float64), "nbytes": sizes.to(torch.float64), "results": results.to(torch.float64)}
+    if scan_offsets is not None:
+        arrays["scan_offsets"] = scan_offsets.to(torch.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a.cpu().numpy())
+
+
 EXIT_EXCHANGE_FAILED = 3   # a rank that gave up on a stuck or failed exchange leaves with this code, never with 0
 
 
@@ -229,9 +269,10 @@ class Bench:
             self.dist.barrier()
         self.torch.cuda.synchronize(self.dev)
 
-    def case(self, W, H, B, content, layout, steps, warmup, check=True):
+    def case(self, W, H, B, content, layout, steps, warmup, check=True, dump=None):
         """Times `steps` encode+decode passes over B frames.  layout: 'slots' | 'concat' | 'concat+scan'
-        (decode from the offsets the device stream scanner finds, not from the encoder's)."""
+        (decode from the offsets the device stream scanner finds, not from the encoder's).  `dump`: a directory that
+        receives the last timed step's outputs (dump_outputs)."""
         torch, dv, codec, rank = self.torch, self.dv, self.codec, self.rank
         if rank == 0:
             progress(f"case {W}x{H} x{B} {content} {layout}: {steps} steps")
@@ -307,6 +348,9 @@ class Bench:
         tk = codec.timing_read(reset=True)
         codec.timing(False)
         codec.sync()
+        if dump:
+            progress(f"dumping the last step's outputs to {dump}")
+            dump_outputs(dump, torch, W, H, B, buf, lead, offs, sizes, out, res, scan_offsets=found)
         t_all = torch.tensor([dt], dtype=torch.float64, device=self.dev)
         if self.dist is not None:
             self.dist.all_reduce(t_all, op=self.dist.ReduceOp.MAX)
@@ -570,7 +614,13 @@ def main():
     ap.add_argument("--no-single", action="store_true", help="skip the one-frame-per-call leg")
     ap.add_argument("--no-check", action="store_true", help="(experiments) skip the round-trip parity gate")
     ap.add_argument("--dry-run", action="store_true", help="launch contract only: no GPU, no codec (CPU tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's last timed step's outputs to DIR/<name>.npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.config == 5:
+        ap.error("--dump-outputs covers the batch configs (2, 3, 4), not the streaming driver of --config 5")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -668,7 +718,8 @@ def main():
     else:
         B = args.frames or cfg["frames"]
         layout = "concat" if args.concat else cfg["layout"]
-        r = b.case(W, H, B, content, layout, args.steps, args.warmup, check=not args.no_check)
+        r = b.case(W, H, B, content, layout, args.steps, args.warmup, check=not args.no_check,
+                   dump=args.dump_outputs if rank == 0 else None)
         enc, dec = r["encode"], r["decode"]
         dom = ("dbde::encode_kernel", enc) if enc["ms"] >= dec["ms"] else ("dbde::decode_kernel", dec)
         roofline = {"bound": "hbm", "kernel": dom[0], "achieved": dom[1]["GBps"], "peak": HBM_PEAK_GBPS, "unit": "GB/s",

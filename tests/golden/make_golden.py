@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Generate tests/golden/*.{npz,json} by running the REAL reference (oracle/_ref/libdbde_ref.so).
 
-Run in the build container (where /root/reference exists and `make -C oracle` has produced
-oracle/_ref/libdbde_ref.so):
+Run where the reference sources exist and `make -C oracle` has produced oracle/_ref/libdbde_ref.so:
 
     python tests/golden/make_golden.py
 
 The outputs are data only -- inputs and the reference's outputs -- and are committed; the
-reference itself never travels.  Inputs come from three places:
+reference itself never travels.  reference_runs.json holds what the reference returned on inputs the tests
+re-create (oracle_ffi.differential_cases, the writer's file of oracle_ffi.WALKER_FILE).  Inputs come from three places:
   * the README's worked 10x10 example (reference README.md:73-84),
   * the 8x16 image of the reference's own known-answer test (dbde_util_test.cpp:135-144),
   * the counter-based generators of oracle/synth.c (seeded, reproducible anywhere).
@@ -16,12 +16,14 @@ import hashlib
 import json
 import os
 import sys
+import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-from oracle_ffi import Oracle, Reference  # noqa: E402
+from oracle_ffi import (REFERENCE_RUNS, WALKER_FILE, Oracle, Reference, differential_cases,  # noqa: E402
+                        wrapping_add_stream)
 
 SEED = 0xDBDE2016
 
@@ -79,6 +81,38 @@ def depth_ramp_frame(H, W):
             span = (1 << d) - 1
             img[y, x] = (17 * (x // 8) + 5 * (y // 8)) % (256 - span) + ((x * 7 + y * 13) % (span + 1))
     return img
+
+
+def reference_runs(ref, ora):
+    """The reference's results on inputs the tests re-create: the differential run's frames (packed bytes and what its
+    unpack returns), the wrapping-add stream, and its file walker over the .dbde file the HIP writer must produce."""
+    diff = []
+    for W, H, kind, img, idx in differential_cases(ora):
+        packed = ref.pack_frame(idx, img, W, H)
+        n, fh, back = ref.unpack_frame(packed, W, H)
+        diff.append({"W": W, "H": H, "kind": kind, "index": idx, "image_sha": sha(img), "packed_bytes": int(len(packed)),
+                     "packed_sha": sha(packed), "advance": int(n), "header": [int(x) for x in fh],
+                     "unpacked_sha": sha(back)})
+    wrap = wrapping_add_stream(ref)
+    n, fh, back = ref.unpack_frame(wrap, 8, 8)
+    wrapping = {"stream": wrap.tobytes().hex(), "advance": int(n), "header": [int(x) for x in fh],
+                "image": back.tobytes().hex()}
+
+    w = WALKER_FILE
+    W, H, n = w["W"], w["H"], w["n"]
+    imgs = [ora.synth_frame(1, SEED, f, W, H) for f in range(n)]
+    data = np.concatenate([ref.pack_video_header(3, H, W, w["frame_hz"])]
+                          + [ref.pack_frame(w["first_index"] + f, imgs[f], W, H) for f in range(n)])
+    walks = []
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "walk.dbde")
+        data.tofile(path)
+        for keep in w["keeps"]:
+            cnt, hw, last, img = ref.walk_file(path, w["buffered"], W, H, keep=keep)
+            walks.append({"keep": keep, "count": int(cnt), "height_width": [int(x) for x in hw], "last_index": int(last),
+                          "image_sha": sha(img)})
+    walker = {"file_bytes": int(len(data)), "file_sha": sha(data), "walks": walks}
+    return {"differential": diff, "wrapping_add": wrapping, "walker": walker}
 
 
 def main():
@@ -186,6 +220,8 @@ def main():
                                     "image_sha": sha(img), "packed_sha": sha(packed),
                                     "packed_bytes": int(len(packed)), "depth_hist": hist})
 
+    with open(REFERENCE_RUNS, "w") as f:
+        json.dump(reference_runs(ref, ora), f, indent=1)
     np.savez_compressed(os.path.join(HERE, "frames.npz"), **arrays)
     with open(os.path.join(HERE, "manifest.json"), "w") as f:
         json.dump(manifest, f, indent=1)

@@ -311,3 +311,48 @@ class Reference:
         t = self.L.ref_time_roundtrip(_p(src), n, W, H, reps, _p(sp), _p(si),
                                       C.byref(te), C.byref(td), C.byref(bad))
         return t, te.value, td.value, bad.value
+
+
+# ---- inputs the reference was run on when tests/golden was made, and what it returned there ------------------------
+
+REFERENCE_RUNS = os.path.join(ROOT, "tests", "golden", "reference_runs.json")
+
+# the .dbde file of tests/test_gpu_file_io.py::test_reference_walker_reads_writer_file: mixed frames 0..n-1 of the
+# synthetic source, indices from FIRST, frame_hz 30 (the writer's default); the walker buffers 3 frames and keeps one
+WALKER_FILE = dict(W=333, H=77, n=13, first_index=1000, frame_hz=30.0, buffered=3, keeps=(1, 7, 13))
+
+
+def differential_cases(oracle):
+    """The frames of the oracle-versus-reference differential run, in order: (W, H, kind, image, index).  One seeded
+    generator draws them (kind 0: uniform noise, 1: one depth, 2: flat, 3..4: the oracle's synthetic modes 1..2)."""
+    rng = np.random.default_rng(20161004)
+    for it in range(300):
+        W, H = int(rng.integers(1, 90)), int(rng.integers(1, 90))
+        kind = it % 5
+        if kind == 0:
+            img = rng.integers(0, 256, (H, W), dtype=np.uint8)
+        elif kind == 1:
+            d = int(rng.integers(0, 8))
+            img = (rng.integers(0, 256 - (1 << d)) + rng.integers(0, 1 << d, (H, W))).astype(np.uint8)
+        elif kind == 2:
+            img = np.full((H, W), rng.integers(0, 256), np.uint8)
+        else:
+            img = oracle.synth_frame(kind - 2, int(rng.integers(0, 2**62)), it, W, H)
+        yield W, H, kind, img, int(rng.integers(0, 2**63))
+
+
+def wrapping_add_stream(oracle):
+    """An 8x8 frame whose decode needs the byte-wise wrapping add: min byte 200 on a tile of range 255 (the stream
+    still passes validation)."""
+    img = np.full((8, 8), 0, np.uint8)
+    img[0, 1] = 255
+    packed = oracle.pack_frame(0, img, 8, 8)
+    packed[20 + 4 + 1 + 4] = 200
+    return packed
+
+
+def reference_runs():
+    """tests/golden/reference_runs.json: the reference's results on the inputs above (made by make_golden.py)."""
+    import json
+    with open(REFERENCE_RUNS) as f:
+        return json.load(f)

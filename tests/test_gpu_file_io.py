@@ -1,11 +1,14 @@
 """GPU parity for the file ends of the path: the batched .dbde writer and reader
-(dbde_hip_writer_* / dbde_hip_reader_*, include/dbde_hip.h) against the oracle's bytes and,
-where oracle/_ref was built, the reference's own file walker (dbde_util.cpp:362-426).
+(dbde_hip_writer_* / dbde_hip_reader_*, include/dbde_hip.h) against the oracle's bytes and the reference's own file
+walker (dbde_util.cpp:362-426): its recorded results on the same bytes, and live where oracle/_ref was built.
 
 A file is bit-exact when it equals  video_header(28 B) + dbde_pack_frame(...) for every frame.
 """
+import hashlib
+
 import numpy as np
 import pytest
+from oracle_ffi import WALKER_FILE, Reference, reference_runs
 
 pytestmark = pytest.mark.gpu
 
@@ -104,17 +107,30 @@ def test_reader_reads_oracle_file(codec, oracle, tmp_path, W, H, n, batch, ask):
     r.close()
 
 
-def test_reference_walker_reads_writer_file(codec, reference, tmp_path):
-    """The reference's own dbde_walk_a_file decodes what the HIP writer wrote."""
-    W, H, n = 333, 77, 13
+def test_reference_walker_reads_writer_file(codec, tmp_path):
+    """The reference's own dbde_walk_a_file decodes what the HIP writer wrote: the file is byte for byte the one the
+    walker was run on when tests/golden was made (its results are in reference_runs.json), and where oracle/_ref is
+    built the walker reads this very file again."""
+    f = WALKER_FILE
+    W, H, n, first = f["W"], f["H"], f["n"], f["first_index"]
     imgs = codec.synth_frames("mixed", SEED, 0, n, W, H)
     path = str(tmp_path / "ref.dbde")
-    with codec.open_writer(path, W, H, batch_frames=5) as w:
-        w.put(imgs, n, first_index=1000)
-    for keep in (1, 7, 13):
-        cnt, hw, last, img = reference.walk_file(path, 3, W, H, keep=keep)
-        assert cnt == n and hw == (H, W) and last == 1000 + n - 1
-        assert np.array_equal(img, imgs[keep - 1].cpu().numpy())
+    with codec.open_writer(path, W, H, frame_hz=f["frame_hz"], batch_frames=5) as w:
+        w.put(imgs, n, first_index=first)
+    data = open(path, "rb").read()
+    rec = reference_runs()["walker"]
+    assert len(data) == rec["file_bytes"] and hashlib.sha256(data).hexdigest() == rec["file_sha"]
+    assert [w["keep"] for w in rec["walks"]] == list(f["keeps"])
+    for want in rec["walks"]:
+        keep = want["keep"]
+        assert want["count"] == n and want["height_width"] == [H, W] and want["last_index"] == first + n - 1
+        assert want["image_sha"] == hashlib.sha256(imgs[keep - 1].cpu().numpy().tobytes()).hexdigest()
+    if Reference.available():
+        reference = Reference()
+        for keep in f["keeps"]:
+            cnt, hw, last, img = reference.walk_file(path, f["buffered"], W, H, keep=keep)
+            assert cnt == n and hw == (H, W) and last == first + n - 1
+            assert np.array_equal(img, imgs[keep - 1].cpu().numpy())
 
 
 def test_reader_stops_like_the_walker(codec, oracle, tmp_path):

@@ -3,12 +3,14 @@
 Three anchors, strongest first:
   1. the reference's own known-answer vector (dbde_util_test.cpp:135-178),
   2. tests/golden/ fixtures produced by the real reference (make_golden.py),
-  3. live differential runs against oracle/_ref/libdbde_ref.so when it is present.
+  3. a differential run of random frames against the reference's recorded results (tests/golden/reference_runs.json),
+     and live against oracle/_ref/libdbde_ref.so when it is present.
 """
 import hashlib
 
 import numpy as np
 import pytest
+from oracle_ffi import Reference, differential_cases, reference_runs, wrapping_add_stream
 
 MODES = {"noise8": 0, "mixed": 1, "flat": 2, "smooth": 3}
 
@@ -155,31 +157,32 @@ def test_big_config_hashes(oracle, golden):
         assert n == len(packed) and (back == img).all()
 
 
-def test_live_differential_against_reference(oracle, reference):
-    rng = np.random.default_rng(20161004)
-    for it in range(300):
-        W, H = int(rng.integers(1, 90)), int(rng.integers(1, 90))
-        kind = it % 5
-        if kind == 0:
-            img = rng.integers(0, 256, (H, W), dtype=np.uint8)
-        elif kind == 1:
-            d = int(rng.integers(0, 8))
-            img = (rng.integers(0, 256 - (1 << d)) + rng.integers(0, 1 << d, (H, W))).astype(np.uint8)
-        elif kind == 2:
-            img = np.full((H, W), rng.integers(0, 256), np.uint8)
-        else:
-            img = oracle.synth_frame(kind - 2, int(rng.integers(0, 2**62)), it, W, H)
-        idx = int(rng.integers(0, 2**63))
-        a, b = oracle.pack_frame(idx, img, W, H), reference.pack_frame(idx, img, W, H)
-        assert a.tobytes() == b.tobytes(), (W, H, kind)
+def test_live_differential_against_reference(oracle):
+    """300 random frames: the oracle's packed bytes and unpack against the reference's, as recorded by make_golden.py
+    (tests/golden/reference_runs.json) and, where oracle/_ref is built, against the live reference as well."""
+    runs = reference_runs()
+    reference = Reference() if Reference.available() else None
+    cases = list(differential_cases(oracle))
+    assert len(cases) == len(runs["differential"])
+    for (W, H, kind, img, idx), want in zip(cases, runs["differential"]):
+        assert (W, H, kind, idx, sha(img)) == (want["W"], want["H"], want["kind"], want["index"], want["image_sha"])
+        a = oracle.pack_frame(idx, img, W, H)
+        assert len(a) == want["packed_bytes"] and sha(a) == want["packed_sha"], (W, H, kind)
         na, fa, ia = oracle.unpack_frame(a, W, H)
-        nb, fb, ib = reference.unpack_frame(a, W, H)
-        assert na == nb == len(a) and fa == fb and (ia == ib).all() and (ia == img).all()
+        assert na == want["advance"] == len(a) and list(fa) == want["header"] and sha(ia) == want["unpacked_sha"]
+        assert (ia == img).all()
+        if reference is not None:
+            b = reference.pack_frame(idx, img, W, H)
+            assert a.tobytes() == b.tobytes(), (W, H, kind)
+            nb, fb, ib = reference.unpack_frame(a, W, H)
+            assert na == nb and fa == fb and (ia == ib).all()
     # byte-wise wrapping add on decode (min + value > 255 in a crafted but accepted stream)
-    img = np.full((8, 8), 0, np.uint8)
-    img[0, 1] = 255
-    packed = oracle.pack_frame(0, img, 8, 8)
-    packed[20 + 4 + 1 + 4] = 200                 # min byte := 200, stream still passes validation
+    packed = wrapping_add_stream(oracle)
+    want = runs["wrapping_add"]
+    assert packed.tobytes().hex() == want["stream"]
     na, fa, ia = oracle.unpack_frame(packed, 8, 8)
-    nb, fb, ib = reference.unpack_frame(packed, 8, 8)
-    assert na == nb and fa == fb and (ia == ib).all() and ia[0, 1] == (255 + 200) % 256
+    assert na == want["advance"] and list(fa) == want["header"] and ia.tobytes().hex() == want["image"]
+    assert ia[0, 1] == (255 + 200) % 256
+    if reference is not None:
+        nb, fb, ib = reference.unpack_frame(packed, 8, 8)
+        assert na == nb and fa == fb and (ia == ib).all()
