@@ -54,6 +54,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_scatter_set_max_message", "dbde_hip_scatter_set_capacity", "dbde_hip_scatter_begin", "dbde_hip_scatter_post",
     "dbde_hip_scatter_join", "dbde_hip_scatter_sync", "dbde_hip_scatter_blocks", "dbde_hip_scatter_check",
     "dbde_hip_scatter_plan", "dbde_hip_create_on_own_stream", "dbde_hip_set_host_staging",
+    "dbde_hip_decode_roi", "dbde_hip_unpack_image_roi", "dbde_hip_roi_plan",
 ]
 
 
@@ -158,6 +159,12 @@ def lib():
     L.dbde_hip_unpack_image.restype = sz
     L.dbde_hip_unpack_image.argtypes = [vp, vp, i, i, vp]
     L.dbde_hip_unpack_frame.restype = FrameHeader
+    L.dbde_hip_unpack_image_roi.argtypes = [vp, vp, i, i, i, i, i, i, vp]
+    L.dbde_hip_unpack_image_roi.restype = sz
+    L.dbde_hip_decode_roi.argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, vp, vp]
+    L.dbde_hip_decode_roi.restype = i
+    L.dbde_hip_roi_plan.argtypes = [i, i, i, i, i, i, i, C.POINTER(RoiPlan)]
+    L.dbde_hip_roi_plan.restype = i
     L.dbde_hip_unpack_frame.argtypes = [vp, C.POINTER(vp), i, i, vp]
     L.dbde_hip_pack_frame_header.restype = sz
     L.dbde_hip_pack_frame_header.argtypes = [C.POINTER(FrameHeader), vp]
@@ -303,6 +310,27 @@ def decode_plan(W, H, n_frames, image_address=0, n_cu=256):
     rc = L.dbde_hip_decode_plan(W, H, n_frames, image_address, n_cu, C.byref(pl))
     if rc != OK:
         raise ValueError(f"dbde_hip_decode_plan({W}, {H}, {n_frames}) -> {rc}")
+    return pl.as_dict()
+
+
+class RoiPlan(C.Structure):
+    """dbde_hip_roi_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("max_tiles_x", C.c_int32), ("max_tiles_y", C.c_int32), ("chunks_per_frame", C.c_uint32),
+                ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32), ("index_split", C.c_uint32),
+                ("threads", C.c_uint32), ("pieces_x", C.c_uint32), ("grid", C.c_uint64), ("grid_origins", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def roi_plan(W, H, n_frames, x, y, rw, rh):
+    """dbde_hip_roi_plan: the tile window, index geometry and launch of a window decode (host arithmetic only).
+    Raises ValueError where dbde_hip_decode_roi would return DBDE_HIP_ERR_ARG."""
+    pl = RoiPlan()
+    rc = lib().dbde_hip_roi_plan(W, H, n_frames, x, y, rw, rh, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"dbde_hip_roi_plan({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}) -> {rc}")
     return pl.as_dict()
 
 
@@ -474,6 +502,21 @@ class Codec:
         self._check(rc, "dbde_hip_decode_frames")
         return images, results
 
+    def decode_roi(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, origins=None, out=None,
+                   results=None):
+        """Decodes the rw x rh window at (x, y) of n frames (frame f at stream.data_ptr()+stream_offset+offsets[f]).
+        origins: optional int32 device tensor (n, 2) of per-frame (x, y), clamped into the frame.
+        Returns (windows uint8 (n, rh, rw), results (n, 4) int64) like decode_frames."""
+        if out is None:
+            out = torch.empty((n, rh, rw), dtype=torch.uint8, device=self.device)
+        if results is None:
+            results = torch.empty((n, 4), dtype=torch.int64, device=self.device)
+        rc = self.L.dbde_hip_decode_roi(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                        W, H, n, x, y, rw, rh, origins.data_ptr() if origins is not None else None,
+                                        out.data_ptr(), results.data_ptr())
+        self._check(rc, "dbde_hip_decode_roi")
+        return out, results
+
     def index_stream(self, stream, stream_offset, stream_bytes, W, H, max_frames):
         offsets = torch.empty(max(max_frames, 1), dtype=torch.int64, device=self.device)
         n = C.c_int(0)
@@ -547,6 +590,13 @@ class Codec:
         buf = np.concatenate([np.asarray(packed, np.uint8), np.zeros(64, np.uint8)])
         n = self.L.dbde_hip_unpack_image(self.h, buf.ctypes.data, W, H, img.ctypes.data)
         return int(n), img.reshape(H, W)
+
+    def unpack_image_roi(self, packed, W, H, x, y, rw, rh, fill=0xEE):
+        """dbde_hip_unpack_image_roi: one packed frame_data -> (bytes consumed, the rh x rw window)."""
+        win = np.full(max(rw, 0) * max(rh, 0), fill, np.uint8)
+        buf = np.concatenate([np.asarray(packed, np.uint8), np.zeros(64, np.uint8)])
+        n = self.L.dbde_hip_unpack_image_roi(self.h, buf.ctypes.data, W, H, x, y, rw, rh, win.ctypes.data)
+        return int(n), win.reshape(max(rh, 0), max(rw, 0))
 
     def unpack_frame(self, packed, W, H, fill=0xEE):
         img = np.full(W * H, fill, np.uint8)

@@ -16,6 +16,7 @@
 
 #include "dbde16_kernels.h"
 #include "dbde_kernels.h"
+#include "dbde_roi_kernels.h"
 
 using namespace dbde;
 
@@ -817,6 +818,144 @@ int dbde_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t st
     return DBDE_HIP_OK;
 }
 
+// ---- window decode ----------------------------------------------------------------------------------------
+// Index split of the decode index kernel, as dbde_hip_decode_frames chooses it: few frames are cut into pieces so that
+// the index pass fills the device too (>= 4 chunks per piece, about 1024 workgroups in all).
+static uint32_t index_split_for(int n_frames, uint32_t cpf) {
+    if (n_frames < 1 || n_frames >= 256 || cpf < 8u) return 1u;
+    uint32_t sp = 1024u / (uint32_t)n_frames;
+    const uint32_t most = (cpf + 3u) / 4u;
+    return sp > most ? most : (sp < 1u ? 1u : sp);
+}
+
+struct RoiPlan {
+    Geometry g;
+    DecGeom dg;                       // the index's chunks (roi_index_geometry)
+    uint32_t tx0, ty0, ntx, nty;      // the window at (x0, y0)
+    uint32_t max_tx, max_ty;          // the most any origin needs
+    uint32_t split, threads, pieces, pieces_fixed;
+    uint64_t grid, grid_origins;
+};
+// nullptr when the arguments are good, else what is wrong with them.
+static const char *plan_roi(int W, int H, int n_frames, int x0, int y0, int rw, int rh, RoiPlan &pl) {
+    if (n_frames < 0) return "n_frames < 0";
+    if (!geometry(W, H, pl.g)) return "bad frame size";
+    if (rw < 1 || rh < 1 || rw > W || rh > H) return "window size outside [1, W] x [1, H]";
+    if (x0 < 0 || y0 < 0 || x0 > W - rw || y0 > H - rh) return "window origin outside [0, W-rw] x [0, H-rh]";
+    pl.dg = roi_index_geometry(pl.g.w, pl.g.h);
+    if (pl.dg.cpf > kMaxChunksPerFrame) return "frame too large";
+    pl.tx0 = (uint32_t)x0 >> 3;
+    pl.ty0 = (uint32_t)y0 >> 3;
+    pl.ntx = (uint32_t)(x0 + rw - 1) / 8u + 1u - pl.tx0;
+    pl.nty = (uint32_t)(y0 + rh - 1) / 8u + 1u - pl.ty0;
+    // x mod 8 reaches min(7, W - rw) over the origins a window of this width can have
+    const uint32_t mx = (uint32_t)(W - rw) < 7u ? (uint32_t)(W - rw) : 7u, my = (uint32_t)(H - rh) < 7u ? (uint32_t)(H - rh) : 7u;
+    pl.max_tx = (mx + (uint32_t)rw + 7u) / 8u;
+    pl.max_ty = (my + (uint32_t)rh + 7u) / 8u;
+    pl.split = index_split_for(n_frames, pl.dg.cpf);
+    pl.threads = pl.max_tx <= kRoiNarrowThreads ? kRoiNarrowThreads : kRoiWideThreads;
+    pl.pieces = (pl.max_tx + pl.threads - 1u) / pl.threads;
+    pl.pieces_fixed = (pl.ntx + pl.threads - 1u) / pl.threads;
+    pl.grid = (uint64_t)n_frames * pl.nty * pl.pieces_fixed;
+    pl.grid_origins = (uint64_t)n_frames * pl.max_ty * pl.pieces;
+    if (pl.grid_origins >= (1ull << 31)) return "too many workgroups in one call";
+    if ((uint64_t)n_frames * (pl.dg.cpf + 1u) >= (1ull << 31)) return "too many chunks in one call";
+    return nullptr;
+}
+
+int dbde_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_roi_plan_t *plan) {
+    RoiPlan pl;
+    if (!plan || plan_roi(W, H, n_frames, x0, y0, rw, rh, pl)) return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->tile_x = (int32_t)pl.tx0;
+    plan->tile_y = (int32_t)pl.ty0;
+    plan->tiles_x = (int32_t)pl.ntx;
+    plan->tiles_y = (int32_t)pl.nty;
+    plan->max_tiles_x = (int32_t)pl.max_tx;
+    plan->max_tiles_y = (int32_t)pl.max_ty;
+    plan->chunks_per_frame = pl.dg.cpf;
+    plan->chunk_tiles = pl.dg.ct;
+    plan->chunk_pieces = pl.dg.ct == pl.g.w || pl.dg.pieces > 1u ? pl.dg.pieces : 0u;
+    plan->index_split = pl.split;
+    plan->threads = pl.threads;
+    plan->pieces_x = pl.pieces;
+    plan->grid = pl.grid;
+    plan->grid_origins = pl.grid_origins;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+                        int W, int H, int n_frames, int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                        uint8_t *d_out, dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    RoiPlan pl;
+    const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl);
+    if (why)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "decode_roi: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", why, W, H, n_frames,
+                    rw, rh, x0, y0);
+    if (!d_stream || !d_frame_offsets || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "decode_roi: null pointer");
+    if (n_frames == 0) return DBDE_HIP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t cpf = pl.dg.cpf;
+    int rc = grow(ctx, ctx->chunk_off, ctx->chunk_off_n, (size_t)n_frames * (cpf + 1u), sizeof(uint32_t));
+    if (rc) return rc;
+    rc = grow(ctx, ctx->frame_ok, ctx->frame_ok_n, (size_t)n_frames, sizeof(uint32_t));
+    if (rc) return rc;
+
+    IdxParams ip;
+    ip.stream = d_stream;
+    ip.frame_offsets = d_frame_offsets;
+    ip.stream_bytes = stream_bytes;
+    ip.chunk_off = ctx->chunk_off;
+    ip.frame_ok = ctx->frame_ok;
+    ip.results = d_results;
+    ip.T = pl.g.T;
+    ip.chunks_per_frame = cpf;
+    ip.min_bytes = 1;
+    ip.geom = pl.dg;
+    ip.split = 1;
+    ip.frame_ctr = nullptr;
+    ip.frame_flag = nullptr;
+    if (pl.split > 1u) {
+        const size_t before = ctx->idx_ctr_n;
+        rc = grow(ctx, ctx->idx_ctr, ctx->idx_ctr_n, 2 * (size_t)n_frames, sizeof(uint32_t));
+        if (rc) return rc;
+        if (ctx->idx_ctr_n != before)   // fresh block: the kernel keeps it zero from here on
+            HIP_TRY(ctx, hipMemsetAsync(ctx->idx_ctr, 0, ctx->idx_ctr_n * sizeof(uint32_t), ctx->stream));
+        ip.split = pl.split;
+        ip.frame_ctr = ctx->idx_ctr;
+        ip.frame_flag = ctx->idx_ctr + n_frames;
+    }
+    span_begin(ctx, 1);
+    HIP_TRY(ctx, launch_decode_index(ip, n_frames, ctx->stream));
+    span_end(ctx);
+
+    RoiParams p;
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.origins = d_origins;
+    p.out = d_out;
+    p.W = W;
+    p.H = H;
+    p.x0 = x0;
+    p.y0 = y0;
+    p.rw = rw;
+    p.rh = rh;
+    p.w = pl.g.w;
+    p.h = pl.g.h;
+    p.T = pl.g.T;
+    p.geom = pl.dg;
+    p.rows = d_origins ? pl.max_ty : pl.nty;
+    p.pieces = d_origins ? pl.pieces : pl.pieces_fixed;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_decode_roi(p, (uint32_t)n_frames, pl.threads, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
 int dbde_hip_index_stream_async(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, int W, int H,
                                 int max_frames, uint64_t *d_frame_offsets, uint32_t *d_n_found) {
     if (!ctx) return DBDE_HIP_ERR_ARG;
@@ -1205,6 +1344,34 @@ size_t dbde_hip_unpack_image(dbde_hip_ctx *ctx, const uint8_t *packed, int W, in
     if (!used) return 0;
     if (!d2h(ctx, image, ctx->st_img, (size_t)g.pixels, ctx->h_img)) return 0;
     return used;
+}
+
+size_t dbde_hip_unpack_image_roi(dbde_hip_ctx *ctx, const uint8_t *packed, int W, int H, int x0, int y0, int rw, int rh,
+                                 uint8_t *image) {
+    RoiPlan pl;
+    if (!ctx || !packed || !image || plan_roi(W, H, 1, x0, y0, rw, rh, pl)) return 0;
+    const Geometry &g = pl.g;
+    // as dbde_hip_unpack_image: the host reads only what it needs to know how many bytes to move
+    if ((int32_t)get32(packed) != (int32_t)g.T) return 0;
+    if ((int32_t)get32(packed + 4 + g.T) != (int32_t)g.T) return 0;
+    const int32_t n64 = (int32_t)get32(packed + 8 + 2 * (size_t)g.T);
+    if (n64 < 0 || (uint64_t)n64 > 8ull * g.T) return 0;
+    const size_t body = 12 + 2 * (size_t)g.T + 8 * (size_t)n64;
+    const size_t win = (size_t)rw * (size_t)rh;
+    if (hipSetDevice(ctx->device) != hipSuccess) return 0;
+    if (ensure_staging(ctx, win, 20 + body + 128)) return 0;
+    if (hipMemcpyAsync(ctx->st_pack, ctx->d_hdr, 20, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) return 0;
+    if (!h2d(ctx, ctx->st_pack + 20, packed, body, ctx->h_pack)) return 0;
+    uint64_t *d_off = ctx->scratch64 + 2;   // a zero in device memory
+    volatile dbde_hip_frame_result *h_res = reinterpret_cast<volatile dbde_hip_frame_result *>(ctx->h_words + 1);
+    h_res->consumed = 0;
+    if (dbde_hip_decode_roi(ctx, ctx->st_pack, 20 + body, d_off, W, H, 1, x0, y0, rw, rh, nullptr, ctx->st_img,
+                            const_cast<dbde_hip_frame_result *>(h_res)) != DBDE_HIP_OK) return 0;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return 0;
+    const uint64_t consumed = h_res->consumed;
+    if (consumed <= 20) return 0;
+    if (!d2h(ctx, image, ctx->st_img, win, ctx->h_img)) return 0;
+    return (size_t)(consumed - 20);
 }
 
 dbde_hip_frame_header dbde_hip_unpack_frame(dbde_hip_ctx *ctx, uint8_t **packed, int W, int H, uint8_t *image) {

@@ -124,6 +124,24 @@ int dbde_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t st
                            const uint64_t *d_frame_offsets, int W, int H, int n_frames,
                            uint8_t *d_images, dbde_hip_frame_result *d_results);
 
+/* Window (region-of-interest) decode: the rw x rh window at (x, y) of each of n_frames frames, decoding only the tiles
+ * the window covers.  Frame f starts at d_stream + d_frame_offsets[f] (any byte alignment); its window
+ * goes to d_out + f*rw*rh, row-major, pitch rw, any byte alignment, and equals rows [y, y+rh) x columns [x, x+rw) of
+ * the image dbde_hip_decode_frames would write, byte for byte.
+ *   d_origins: optional device int32 [n_frames][2] (x, y) per frame, CLAMPED into [0, W-rw] x [0, H-rh] (a tracker's
+ *              moving window).  NULL -> (x0, y0) for every frame.  (x0, y0) must lie in [0, W-rw] x [0, H-rh] either way
+ *              (pass 0, 0 with per-frame origins); a host origin outside the frame is DBDE_HIP_ERR_ARG.
+ *   d_results: as in dbde_hip_decode_frames (header fields; consumed = the whole frame's length), may be NULL.
+ * Validation is dbde_hip_decode_frames' own (the same index kernel): a rejected frame reports the same result entry
+ * and leaves its window untouched.  No byte at or beyond stream_bytes is read; nothing outside the n_frames*rw*rh
+ * output is written.  n_frames == 0 does nothing.  rw / rh below 1 or above W / H, or a frame too large for the
+ * index (more than 32768 chunks), is DBDE_HIP_ERR_ARG.  Asynchronous on the context's stream; timing hook: the index
+ * kernel in slot 1, the window kernel in slot 2. */
+int dbde_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                        const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                        int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                        uint8_t *d_out, dbde_hip_frame_result *d_results);
+
 /* Builds the frame index of a concatenated frame sequence starting at d_stream (no video
  * header): hops 20 + 12 + 2T + 8*n64 from frame to frame (README.md:12-23) until max_frames
  * or the end of stream_bytes.  Writes offsets (device, max_frames) and returns the number of
@@ -182,6 +200,10 @@ void dbde_hip_unpack_8x8_partial(dbde_hip_ctx *ctx, uint8_t depth, uint8_t minva
 /* dbde_unpack_image (dbde_util.h:33, dbde_util.cpp:291-328): bytes consumed, 0 on failure. */
 size_t dbde_hip_unpack_image(dbde_hip_ctx *ctx, const uint8_t *packed, int W, int H,
                              uint8_t *image);
+/* The window form of dbde_hip_unpack_image (no reference counterpart): one packed frame_data -> the rw x rh window at
+ * (x0, y0), row-major at pitch rw.  Returns the bytes consumed, or 0 on failure (window untouched). */
+size_t dbde_hip_unpack_image_roi(dbde_hip_ctx *ctx, const uint8_t *packed, int W, int H,
+                                 int x0, int y0, int rw, int rh, uint8_t *image);
 /* dbde_unpack_frame (dbde_util.h:35, dbde_util.cpp:339-345): *packed is advanced exactly as
  * the reference advances it (by 20 only when the frame data is rejected). */
 dbde_hip_frame_header dbde_hip_unpack_frame(dbde_hip_ctx *ctx, uint8_t **packed, int W, int H,
@@ -410,6 +432,24 @@ int dbde_hip_encode_plan(int width, int height, int n_frames, uint64_t image_add
                          uint64_t slot_stride, int resident_workgroups, dbde_hip_launch_plan *plan);
 int dbde_hip_decode_plan(int width, int height, int n_frames, uint64_t image_address, int n_cu,
                          dbde_hip_launch_plan *plan);
+
+/* What a window decode with these arguments runs (pure host arithmetic, like dbde_hip_decode_plan): validates the
+ * arguments as dbde_hip_decode_roi does (DBDE_HIP_ERR_ARG otherwise) and reports the tile window, the index geometry
+ * and the window kernel's launch. */
+typedef struct dbde_hip_roi_plan_t {
+    int32_t tile_x, tile_y;           /* first tile column / row of the window at (x0, y0) */
+    int32_t tiles_x, tiles_y;         /* tiles across / down that window covers */
+    int32_t max_tiles_x, max_tiles_y; /* the most any origin in [0, W-rw] x [0, H-rh] needs (per-frame origins) */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (each starts a tile row or a 512-tile piece of one) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk (the frame's width in tiles, or 512) */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks (frames too tall otherwise) */
+    uint32_t index_split;             /* index: workgroups per frame (1 = one per frame) */
+    uint32_t threads;                 /* window kernel: workgroup size = tiles per workgroup (64 or 256) */
+    uint32_t pieces_x;                /* window kernel: workgroups per window tile row (per-frame origins: the most) */
+    uint64_t grid;                    /* window kernel: workgroups with the origin (x0, y0) */
+    uint64_t grid_origins;            /* ... with per-frame origins (the most any origin needs) */
+} dbde_hip_roi_plan_t;
+int dbde_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_roi_plan_t *plan);
 
 /* ---- kernel timing hook for bench.py ---------------------------------------------------- */
 /* When enabled, every encode / decode call brackets its kernels with HIP events on the
