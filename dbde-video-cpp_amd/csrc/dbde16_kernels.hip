@@ -425,9 +425,6 @@ __global__ __launch_bounds__(kChunkTiles16) void dec16_kernel(DecParams16 p) {
     const bool rows16 = (p.W & 7) == 0 && (reinterpret_cast<uintptr_t>(p.images) & 15u) == 0u;   // every tile row a 16-byte aligned store
     // A row's 8*d bits start at byte r*d of the tile payload: two 64-bit windows, one per 4-pixel half (the second
     // starts 4*d bits = d/2 bytes, and 4 bits when d is odd, later).
-#ifndef DBDE16_ALIGNED_READS
-#define DBDE16_ALIGNED_READS 1   // A/B switch: 0 = two unaligned ds_read_b64 per row and 64-bit shifts per pixel
-#endif
     if (swz) {   // depth 16 everywhere, rows 8-byte aligned: a row is its sixteen bytes plus the minimum
         typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
         const uint32_t mn2 = mn * 0x00010001u;
@@ -455,7 +452,6 @@ __global__ __launch_bounds__(kChunkTiles16) void dec16_kernel(DecParams16 p) {
         }
         return;
     }
-#if DBDE16_ALIGNED_READS
     // Each window comes out of the three ALIGNED dwords that hold it (v_alignbyte, as in the 8-bit decoder: LDS reads
     // of 8 bytes at odd addresses are what made mixed depths the slow content here); a pixel is v_alignbit at i*d
     // (shift counts are taken modulo 32: from 32 on the window's high dword is shifted instead), two pixels per dword,
@@ -503,41 +499,6 @@ __global__ __launch_bounds__(kChunkTiles16) void dec16_kernel(DecParams16 p) {
             }
         }
     }
-#else
-    uint64_t lo[8], hi[8];
-    {
-        const uint32_t la = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint8_t *)s_in + byte0;
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            asm volatile("ds_read_b64 %0, %1" : "=v"(lo[r]) : "v"(la + (uint32_t)r * d) : "memory");
-            asm volatile("ds_read_b64 %0, %1" : "=v"(hi[r]) : "v"(la + (uint32_t)r * d + (d >> 1)) : "memory");
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-    DIAG_MARK(3);
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const uint64_t h2 = hi[r] >> ((d & 1u) * 4u);
-        uint32_t px[8];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            px[i] = ((uint32_t)((lo[r] >> (i * d)) & fmask) + mn) & 0xFFFFu;       // modulo 2^16, as the spec says
-            px[4 + i] = ((uint32_t)((h2 >> (i * d)) & fmask) + mn) & 0xFFFFu;
-        }
-        const int yy = 8 * (int)ty + r;
-        if (yy < p.H) {
-            uint16_t *row = img + (size_t)yy * (size_t)p.W + x0t;
-            if (x0t + 8 <= p.W) {
-                u32x4_t o;
-                o[0] = px[0] | (px[1] << 16); o[1] = px[2] | (px[3] << 16); o[2] = px[4] | (px[5] << 16); o[3] = px[6] | (px[7] << 16);
-                if (rows16) __builtin_nontemporal_store(o, reinterpret_cast<u32x4_t *>(row));
-                else __builtin_nontemporal_store(o, reinterpret_cast<u32x4_unaligned *>(row));
-            } else {
-                for (int i = 0; i < 8; i++) if (x0t + i < p.W) row[i] = (uint16_t)px[i];
-            }
-        }
-    }
-#endif
 #ifdef DBDE_DIAG
     if (tid == 0 && (c & 63u) == 5u) {   // a sample of workgroups: fetch issue | barrier | LDS reads | unpack + stores (issue)
         DIAG_MARK(4);

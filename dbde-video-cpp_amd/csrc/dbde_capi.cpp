@@ -92,6 +92,7 @@ struct dbde_hip_ctx {
     uint32_t enc_grid = 0;           // resident workgroups for the persistent encoder
     uint32_t enc16_grid = 0;         // the same for the DBDE16 encoder (queried at its first call)
     int n_cu = 0;
+    int mid_dec_per_cu[2][3] = {};   // resident workgroups per CU of decode_mid_kernel (decode_mid_blocks_per_cu)
     uint64_t *diag = nullptr;        // [16] phase cycle sums of diagnostic launches
     bool timing = false;
     std::vector<TimedSpan> spans;
@@ -238,6 +239,7 @@ int dbde_hip_create(int device, void *stream, dbde_hip_ctx **out) {
         ctx->enc_grid = (uint32_t)(per_cu * prop.multiProcessorCount);
         if (ctx->enc_grid > kEncMaxGrid) ctx->enc_grid = kEncMaxGrid;   // one mode flag per workgroup (attach_lookback)
         ctx->n_cu = prop.multiProcessorCount;
+        decode_mid_blocks_per_cu(ctx->mid_dec_per_cu);
     }
     if (const char *e = getenv("DBDE_HIP_EXPERIMENT")) ctx->exp_flags = (uint32_t)strtoul(e, nullptr, 0);
     void *p = nullptr;
@@ -387,7 +389,7 @@ static int attach_lookback(dbde_hip_ctx *ctx, EncParams &p, uint32_t n_chunks, b
     const size_t lb_need = (kHeader + 8 * (size_t)n_chunks + 15) & ~(size_t)15;
     {   // grown in place: on failure ctx->lb is null and ctx->lb_bytes 0, never a freed pointer
         const size_t had = ctx->lb_bytes;
-        int rc = grow(ctx, ctx->lb, ctx->lb_bytes, lb_need, 1, !(ctx->exp_flags & 128u));   // (experiment bit 7: plain cached memory)
+        int rc = grow(ctx, ctx->lb, ctx->lb_bytes, lb_need, 1, true);
         if (rc) return rc;
         if (ctx->lb_bytes != had) ctx->lb_fresh = true;
     }
@@ -431,25 +433,17 @@ struct EncPlan {
 #define DBDE_ROW_FILL 90
 #endif
 #ifndef DBDE_FRAMES_ENCODE_TILES
-// Frames of 65 .. this many tiles with 8-byte aligned rows encode / decode with whole frames per workgroup and staged,
-// coalesced traffic (encode_frames_kernel / decode_frames_kernel); above it the chunk kernels' 512 / 1024 tile slots are
-// filled well enough by one frame.
-#define DBDE_FRAMES_ENCODE_TILES 640   // measured (mixed, encode): 81 tiles 0.39 -> 0.51, 144 0.44 -> 0.56, 256 0.49 -> 0.65, 300 0.32 -> 0.51, 396 0.39 -> 0.57, 625 0.47 -> 0.48
-#endif
-#ifndef DBDE_FRAMES_DECODE_TILES
-// The decode side is built and tested ($DBDE_HIP_EXPERIMENT bit 8 switches it on) but NOT taken by default: against the
-// forms it would replace it measured equal at 81 tiles (0.39; incompressible 0.42 -> 0.49) and slower from 144 tiles on
+// Frames of 65 .. this many tiles with 8-byte aligned rows encode with whole frames per workgroup and staged, coalesced
+// traffic (encode_frames_kernel); above it the chunk kernels' 512 / 1024 tile slots are filled well enough by one frame.
+// (Its decode-side twin measured equal at 81 tiles (0.39; incompressible 0.42 -> 0.49) and slower from 144 tiles on
 // (0.43 -> 0.37; 300 tiles: 0.55 with its index kernel counted -> 0.44) -- six dependent phases per workgroup, each a
-// memory or LDS round trip, where decode_mid_kernel and the chunk decoder have three.
-#define DBDE_FRAMES_DECODE_TILES 640
-#endif
-// rows 8-byte aligned, frames and base whole 16-byte blocks: what the staged whole-frame kernels take
-#ifndef DBDE_GROUP_ROWS4_ALL
-#define DBDE_GROUP_ROWS4_ALL 1   // rows of 4 mod 8 bytes: every frame up to 256 tiles (the alternative there is encode_mid_kernel: 84x84 0.33 -> 0.44 / 0.30 -> 0.50, 124x124 0.37 -> 0.53 / 0.32 -> 0.59, 100x75 0.325 -> 0.316 / 0.29 -> 0.37)
+// memory or LDS round trip, where decode_mid_kernel and the chunk decoder have three -- and was removed.)
+#define DBDE_FRAMES_ENCODE_TILES 640   // measured (mixed, encode): 81 tiles 0.39 -> 0.51, 144 0.44 -> 0.56, 256 0.49 -> 0.65, 300 0.32 -> 0.51, 396 0.39 -> 0.57, 625 0.47 -> 0.48
 #endif
 #ifndef DBDE_GROUP_ENCODE_TILES
 #define DBDE_GROUP_ENCODE_TILES 85    // largest frame (tiles) of the persistent small-frame encoder where frames above 64 tiles fill 90 % of its lanes (77 .. 85 tiles: three frames)
 #endif
+// rows 8-byte aligned, frames and base whole 16-byte blocks: what the staged whole-frame encoder takes
 static bool frames_geometry(const Geometry &g, int W, uintptr_t images) {
     return W % 8 == 0 && g.pixels % 16 == 0 && (images & 15u) == 0 && g.T > 64u;
 }
@@ -457,9 +451,6 @@ static EncPlan plan_encode(const Geometry &g, int W, int n_frames, uintptr_t ima
                            uint32_t enc_grid) {
     EncPlan pl;
     pl.fast_in = (W % 16 == 0) && ((images & 15u) == 0);
-#ifdef DBDE_FORCE_GENERIC   // A/B builds only: the any-geometry kernels on aligned images
-    pl.fast_in = false;
-#endif
     // chunk geometry of the encoder (EncParams): plain runs of 1024 tiles, or -- any-geometry path, W >= 16 --
     // 512 tile PAIRS that never leave a tile row
     pl.enc_cpf = (g.T + kEncChunkTiles - 1) / kEncChunkTiles;
@@ -472,17 +463,11 @@ static EncPlan plan_encode(const Geometry &g, int W, int n_frames, uintptr_t ima
         // address): a wave owns 63 pairs, its 64th lane feeds the 63rd.  Taken when the last pair of a tile row holds at
         // most 13 pixel columns -- the up to 3 bytes its moved fetch is short of are then padding (dbde_kernels.hip).
         // Rows at even addresses (W and the base even) read at the full rate as they are and keep 64 pairs.
-#ifndef DBDE_NO_RAW4
         const uint32_t last_cols = (uint32_t)W - 16u * (pl.lanes_per_row - 1u);
         // (32-bit offsets inside a frame: geometry() admits frames of up to 8 GiB)
         if (last_cols <= 13u && ((W | (int)(images & 1u)) & 1) && g.pixels < (1ull << 31)) pl.pairs_per_wave = 63;
-#ifdef DBDE_ROW_ALWAYS   // A/B builds: the segment form on rows at even addresses too
-        if (last_cols <= 13u && g.pixels < (1ull << 31)) pl.pairs_per_wave = 63;
-#endif
-#endif
         const uint32_t ppc = pl.pairs_per_wave * (kEncChunkTiles / 128u);
         pl.enc_cpf = (uint32_t)(((uint64_t)g.h * pl.lanes_per_row + ppc - 1u) / ppc);
-#ifndef DBDE_NO_ROW
         // kInRow: one wave per segment of a tile row (addresses and shifts in scalar registers) when that keeps at least
         // DBDE_ROW_FILL percent of the lanes busy -- 1921 wide: 121 pairs = 61 + 60 of 128 lanes
         if (pl.pairs_per_wave == 63u) {
@@ -495,14 +480,11 @@ static EncPlan plan_encode(const Geometry &g, int W, int n_frames, uintptr_t ima
                 pl.enc_cpf = (uint32_t)(((uint64_t)g.h * nseg + spc - 1u) / spc);
             }
         }
-#endif
     }
     pl.n_chunks64 = (uint64_t)n_frames * pl.enc_cpf;
     pl.aligned_out = ((out & 7u) == 0) && (g.T % 4 == 0) && (slot_stride % 8 == 0);
     pl.kernel = 0;
     const bool rows4 = W % 4 == 0 && (images & 3u) == 0 && (out & 15u) == 0 && slot_stride % 16 == 0;
-    if (false) {}
-#ifndef DBDE_NO_GROUP
     // Small frames in slots, 8-byte aligned rows, frames and buffers whole 16-byte blocks: persistent workgroups, the next
     // group's pixels in flight while a group is encoded (encode_group_kernel: one tile per lane, 256 / T frames per
     // workgroup).  Measured against what it replaces (mixed / incompressible): 64x64 0.40 -> 0.53 / 0.33 -> 0.56, 32x32 0.35
@@ -511,18 +493,15 @@ static EncPlan plan_encode(const Geometry &g, int W, int n_frames, uintptr_t ima
     // (96x96, one frame of 144 tiles per workgroup: 0.51 -> 0.42; 128x128 at full fill 0.62 -> 0.56, incompressible 0.54 ->
     // 0.58), and single-tile frames keep the per-wave kernel (8x8: 0.17 -> 0.09, 256 frame images per workgroup).
     // (rows and image bases of 4-byte multiples suffice since the round's last hours: DESIGN 4.1)
-    else if (slot_stride != 0 && rows4 && g.T >= 4u &&
-             (g.T <= 64u || (g.T <= (unsigned)DBDE_GROUP_ENCODE_TILES && (256u / g.T) * g.T * 10u >= 256u * 9u) ||
-              (DBDE_GROUP_ROWS4_ALL && W % 8 != 0 && g.T <= 256u))) pl.kernel = 5;
-#endif
+    // Rows of 4 mod 8 bytes take it for every frame up to 256 tiles (against encode_mid_kernel there: 84x84 0.33 -> 0.44 /
+    // 0.30 -> 0.50, 124x124 0.37 -> 0.53 / 0.32 -> 0.59, 100x75 0.325 -> 0.316 / 0.29 -> 0.37).
+    if (slot_stride != 0 && rows4 && g.T >= 4u &&
+        (g.T <= 64u || (g.T <= (unsigned)DBDE_GROUP_ENCODE_TILES && (256u / g.T) * g.T * 10u >= 256u * 9u) ||
+         (W % 8 != 0 && g.T <= 256u))) pl.kernel = 5;
     else if (g.T <= 64u && slot_stride != 0) pl.kernel = 2;     // tiny frames in slots: several frames per wave, nothing shared
-#ifndef DBDE_NO_FRAMES
     else if (slot_stride != 0 && g.T <= (unsigned)DBDE_FRAMES_ENCODE_TILES && frames_geometry(g, W, images) && (out & 15u) == 0 &&
              slot_stride % 16 == 0) pl.kernel = 4;              // 65 .. 700 tiles, aligned rows: whole frames per workgroup, staged
-#endif
-#ifndef DBDE_NO_MID
     else if (g.T <= (unsigned)DBDE_MID_ENCODE_TILES && slot_stride != 0) pl.kernel = 3;   // 65 .. 256 tiles in slots: whole frames per workgroup
-#endif
     else if (pl.n_chunks64 < enc_grid) pl.kernel = 1;           // fewer chunks than resident workgroups: one workgroup per chunk
     return pl;
 }
@@ -638,9 +617,9 @@ struct DecPlan {
     DecGeom dg;
     uint64_t n_chunks64;
     bool self_index, fused;
-    int kernel;            // 0 = chunk kernels, 3 = decode_mid_kernel, 4 = decode_frames_kernel
+    int kernel;            // 0 = chunk kernels, 3 = decode_mid_kernel
 };
-static DecPlan plan_decode(const Geometry &g, int W, int n_frames, uintptr_t ib, int n_cu, uint32_t exp_flags) {
+static DecPlan plan_decode(const Geometry &g, int W, int n_frames, uintptr_t ib, int n_cu) {
     DecPlan pl;
     // How the pixels reach the image (decode_kernel<IMG>): direct register -> image stores are only FAST when a
     // wave's 1 KB covers whole cache lines (W, the frame size and the base multiples of 128).  Other widths get
@@ -657,9 +636,7 @@ static DecPlan plan_decode(const Geometry &g, int W, int n_frames, uintptr_t ib,
         const uint32_t used384 = g.w <= kChunkTilesSmall ? (kChunkTilesSmall / g.w) * g.w : 0u;
         // (16-byte aligned rows are left out: there plain chunks with direct 16-byte stores, below, beat the better-filled
         // small workgroup on mixed content -- 1440 / 2704 wide: 0.70 / 0.70 against 0.68 / 0.67)
-#ifndef DBDE_NO_SMALL_WG
         if (W % 16 != 0 && (uint64_t)used384 * kChunkTiles > (uint64_t)used512 * kChunkTilesSmall) cap = kChunkTilesSmall;
-#endif
         const uint32_t used = cap == kChunkTiles ? used512 : used384, rows = cap / g.w;
         if (used * 100u >= cap * (unsigned)DBDE_STAGED_FILL) {
             // image rows that are not 8-byte aligned are staged tile-aligned at pitch 8 w + 16: that image must fit the
@@ -673,12 +650,6 @@ static DecPlan plan_decode(const Geometry &g, int W, int n_frames, uintptr_t ib,
     // 16-byte aligned rows that neither cover whole cache lines per wave nor fill staged chunks: still ONE 16-byte store
     // per lane and image row (the direct form) instead of two 8-byte ones (1440 / 1600 wide: 0.62 -> 0.69 / 0.73)
     if (img_mode == 2 && W % 16 == 0 && (ib & 15u) == 0) img_mode = 0;
-#ifdef DBDE_FORCE_GENERIC
-    img_mode = 2;
-#endif
-#ifdef DBDE_FORCE_LINEAR
-    img_mode = 1;
-#endif
     pl.img_mode = img_mode;
     pl.cap = cap;
     pl.dg = dec_geometry(g.w, g.h, img_mode == 1, kChunkTiles, cap);
@@ -693,7 +664,7 @@ static DecPlan plan_decode(const Geometry &g, int W, int n_frames, uintptr_t ib,
     // Few LARGE frames (one 4096x3072 frame per call: 384 chunks): the decode workgroups build the index among
     // themselves (decode_kernel<IMG, kIdxFused>) -- no index kernel, no launch boundary.  Taken when the launch fits the
     // device's workgroup slots (four per CU); correctness does not depend on that, only the latency does.
-    pl.fused = !pl.self_index && pl.n_chunks64 <= 4ull * (uint64_t)n_cu && !(exp_flags & 8u);
+    pl.fused = !pl.self_index && pl.n_chunks64 <= 4ull * (uint64_t)n_cu;
     // tiny frames (the tile-level entry points, thumbnails) and those just above: whole frames per wave / per workgroup
     pl.kernel = g.T <= (unsigned)DBDE_MID_DECODE_TILES ? 3 : 0;
     // ... and larger frames whose chunks would store tile by tile (rows that are not 8-byte aligned and whole-tile-row chunks
@@ -702,9 +673,6 @@ static DecPlan plan_decode(const Geometry &g, int W, int n_frames, uintptr_t ib,
     // 220x215 (756) 0.36 -> 0.39 / 0.39 -> 0.46; not at 1024 tiles (250x250: 0.51 -> 0.44), not where the chunks stage
     // (300x200: 0.59 -> 0.42) -- profiles/r04b_gain.sh
     if (img_mode == 2 && g.T <= (unsigned)DBDE_MID_DECODE_TILES_UNSTAGED) pl.kernel = 3;
-#ifndef DBDE_NO_FRAMES
-    if ((exp_flags & 256u) && g.T > 64u && g.T <= (unsigned)DBDE_FRAMES_DECODE_TILES && frames_geometry(g, W, ib)) pl.kernel = 4;
-#endif
     return pl;
 }
 
@@ -716,7 +684,7 @@ int dbde_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t st
     if (!d_stream || !d_frame_offsets || !d_images || n_frames < 0 || !geometry(W, H, g))
         return fail(ctx, DBDE_HIP_ERR_ARG, "decode_frames: bad argument (W=%d H=%d n=%d)", W, H, n_frames);
     if (n_frames == 0) return DBDE_HIP_OK;
-    const DecPlan pl = plan_decode(g, W, n_frames, reinterpret_cast<uintptr_t>(d_images), ctx->n_cu, ctx->exp_flags);
+    const DecPlan pl = plan_decode(g, W, n_frames, reinterpret_cast<uintptr_t>(d_images), ctx->n_cu);
     const int img_mode = pl.img_mode;
     const DecGeom dg = pl.dg;
     const uint32_t dcpf = dg.cpf;   // whole tile rows (or pieces of a wide one) per chunk, one decode workgroup each
@@ -732,8 +700,7 @@ int dbde_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t st
         tp.images = d_images; tp.results = d_results; tp.frame_pixels = g.pixels;
         tp.W = W; tp.H = H; tp.w = g.w; tp.h = g.h; tp.T = g.T;
         span_begin(ctx, 2);
-        if (pl.kernel == 4) HIP_TRY(ctx, launch_decode_frames(tp, (uint32_t)n_frames, ctx->stream));
-        else HIP_TRY(ctx, launch_decode_mid(tp, (uint32_t)n_frames, (ctx->exp_flags & 1024u) ? 0u : (uint32_t)ctx->n_cu, ctx->stream));   // (experiment bit 10: three workgroups)
+        HIP_TRY(ctx, launch_decode_mid(tp, (uint32_t)n_frames, (ctx->exp_flags & 1024u) ? 0u : (uint32_t)ctx->n_cu, ctx->mid_dec_per_cu, ctx->stream));   // (experiment bit 10: three workgroups)
         span_end(ctx);
         return DBDE_HIP_OK;
     }
@@ -1087,7 +1054,7 @@ int dbde_hip_encode_plan(int W, int H, int n_frames, uint64_t image_address, uin
 int dbde_hip_decode_plan(int W, int H, int n_frames, uint64_t image_address, int n_cu, dbde_hip_launch_plan *plan) {
     Geometry g;
     if (!plan || n_frames < 1 || n_cu < 1 || !geometry(W, H, g)) return DBDE_HIP_ERR_ARG;
-    const DecPlan pl = plan_decode(g, W, n_frames, (uintptr_t)image_address, n_cu, 0u);
+    const DecPlan pl = plan_decode(g, W, n_frames, (uintptr_t)image_address, n_cu);
     memset(plan, 0, sizeof *plan);
     plan->kernel = pl.kernel;
     if (pl.kernel == 0) {
@@ -1098,7 +1065,7 @@ int dbde_hip_decode_plan(int W, int H, int n_frames, uint64_t image_address, int
         plan->chunk_tiles = pl.dg.ct;
         plan->n_chunks = pl.n_chunks64;
     } else {
-        plan->threads = pl.kernel == 4 ? (int32_t)frames_threads_for(g.T) : (int32_t)mid_decode_threads_for(g.T);
+        plan->threads = (int32_t)mid_decode_threads_for(g.T);
     }
     return DBDE_HIP_OK;
 }

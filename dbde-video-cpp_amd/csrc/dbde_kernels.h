@@ -173,12 +173,14 @@ hipError_t launch_encode_mid(const EncParams &p, uint32_t n_frames, hipStream_t 
 uint32_t mid_threads_for(uint32_t T, uint32_t max_threads = 1024u);
 uint32_t mid_encode_threads_for(uint32_t T);
 uint32_t mid_decode_threads_for(uint32_t T);   // the decoder's choice (persistent workgroups: smaller ones, more of them per CU)
-// (persistent workgroups, n_cu * 2048 / threads of them; n_cu = 0: three, for tests of the pipelined loop on small batches)
-hipError_t launch_decode_mid(const struct DecParams &p, uint32_t n_frames, uint32_t n_cu, hipStream_t s);
-// Frames of 65 .. 1024 tiles with 8-byte aligned rows, whole frames per workgroup, pixels and stream bytes staged through
-// LDS as aligned 16-byte blocks (encode: one slot per frame).  frames_threads_for: 256 or 512 threads (512 / 1024 tile slots).
+// (persistent workgroups, n_cu * per_cu of them; n_cu = 0: three, for tests of the pipelined loop on small batches)
+// per_cu: resident workgroups per CU of decode_mid_kernel [unstaged, staged][256, 512, 1024 threads], as
+// decode_mid_blocks_per_cu reports them (asked once per context)
+void decode_mid_blocks_per_cu(int (&per_cu)[2][3]);
+hipError_t launch_decode_mid(const struct DecParams &p, uint32_t n_frames, uint32_t n_cu, const int (&per_cu)[2][3], hipStream_t s);
+// Frames of 65 .. 1024 tiles with 8-byte aligned rows, one slot per frame, whole frames per workgroup, pixels and stream
+// bytes staged through LDS as aligned 16-byte blocks.  frames_threads_for: 256 or 512 threads (512 / 1024 tile slots).
 hipError_t launch_encode_frames(const EncParams &p, uint32_t n_frames, hipStream_t s);
-hipError_t launch_decode_frames(const struct DecParams &p, uint32_t n_frames, hipStream_t s);
 uint32_t frames_threads_for(uint32_t T);
 // Frames of 1 .. 256 tiles with 8-byte aligned rows, one slot per frame: one tile per lane, persistent 256-thread workgroups,
 // the next group's pixels in flight (LDS-DMA into the other of two buffers) while a group is encoded (n_cu = 0: three workgroups, tests)

@@ -19,18 +19,6 @@
 
 #include "dbde_bits.h"
 
-#ifndef DBDE_POLL
-#define DBDE_POLL 0   // where the encoder polls its mailbox (0 = round-1 order, A/B builds only)
-#endif
-#ifndef DBDE_LINE_ALIGNED_STORES
-#define DBDE_LINE_ALIGNED_STORES 1   // A/B switch: 0 = payload stores start at the wave's first 16-byte boundary
-#endif
-#ifndef DBDE_UNALIGNED_OUT_WORDS
-#define DBDE_UNALIGNED_OUT_WORDS 0   // A/B switch: 1 = frames at any alignment leave word by word (8-byte stores at whatever address)
-#endif
-#ifndef DBDE_NT
-#define DBDE_NT 1   // non-temporal hint on the streamed-once traffic (pixels, payload, decoded images)
-#endif
 
 namespace dbde {
 
@@ -135,9 +123,6 @@ __device__ __forceinline__ uint32_t swz8(uint32_t slot) { return slot ^ ((slot >
 __device__ __forceinline__ uint32_t swz16(uint32_t slot) { return slot ^ ((slot >> 4) & 15u); }    // 256-B groups
 // qword index -> swizzled qword index (the half inside the slot is kept)
 __device__ __forceinline__ uint32_t swzq8(uint32_t q) { return (swz8(q >> 1) << 1) | (q & 1u); }
-#ifndef DBDE_ENC_SWZ_ALL
-#define DBDE_ENC_SWZ_ALL 0   // A/B switch: 1 = the encoder's payload image swizzled for every wave (round-2 start)
-#endif
 __device__ __forceinline__ uint32_t swzq16(uint32_t q) { return (swz16(q >> 1) << 1) | (q & 1u); }
 
 // Any of the four depth bytes of x above the format's maximum (8, or 16 for DBDE16)?  Non-zero if so.
@@ -631,8 +616,7 @@ __device__ __forceinline__ void load_chunk(const EncParams &p, const ChunkRef &k
             const uint8_t *sbase = img + (ptrdiff_t)(int32_t)(off - b);     // (signed: up to 3 bytes in front of the frame)
             const uint8_t *src = sbase + (size_t)(pinned ? end_off : lane_off);
             typedef u32x4_t __attribute__((aligned(1))) u32x4_unaligned;
-            const u32x4_t q = DBDE_NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4_unaligned *>(src))
-                                      : *reinterpret_cast<const u32x4_unaligned *>(src);
+            const u32x4_t q = __builtin_nontemporal_load(reinterpret_cast<const u32x4_unaligned *>(src));
             va[2 * r] = q[0]; va[2 * r + 1] = q[1];
             vb[2 * r] = q[2]; vb[2 * r + 1] = q[3];
         }
@@ -666,12 +650,10 @@ __device__ __forceinline__ void load_chunk(const EncParams &p, const ChunkRef &k
             }
             u32x4_t q;
             if (IN_MODE == kInFast) {
-                q = DBDE_NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(src))
-                            : *reinterpret_cast<const u32x4_t *>(src);
+                q = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t *>(src));
             } else {   // any byte alignment (kInRaw4: dword aligned but for pinned rows): global memory takes it, the compiler must be told
                 typedef u32x4_t __attribute__((aligned(1))) u32x4_unaligned;
-                q = DBDE_NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4_unaligned *>(src))
-                            : *reinterpret_cast<const u32x4_unaligned *>(src);
+                q = __builtin_nontemporal_load(reinterpret_cast<const u32x4_unaligned *>(src));
             }
             va[2 * r] = q[0]; va[2 * r + 1] = q[1];
             vb[2 * r] = q[2]; vb[2 * r + 1] = q[3];
@@ -815,7 +797,7 @@ __device__ __forceinline__ void pack_tile(const uint32_t (&v)[16], uint32_t mn, 
     for (int r = 0; r < 8; r++) {
         const uint64_t row = pack_row_dot(v[2 * r] - m4, v[2 * r + 1] - m4, d, w_lo, w_hi, is8);
         const uint64_t merged = acc | (row << fill);
-        pay[DBDE_ENC_SWZ_ALL ? swzq8(qq) : qq] = merged;
+        pay[qq] = merged;
         const uint32_t nf = fill + nb;
         const bool emit = nf >= 64u;
         const uint64_t spill = (row >> 1) >> (63u - fill);   // the bits of row beyond the word (0 when fill == 0)
@@ -933,34 +915,23 @@ __device__ __forceinline__ void store_wave_part(const EncParams &p, const ChunkR
         // front of the first 128-byte boundary (h of them, 0..7) leave with the LAST h lanes of a first, partial
         // instruction, so that every other store instruction of the wave covers whole cache lines (a 1 KB wave store
         // that straddles lines runs at little more than half the rate of an aligned one, profiles/mempattern.hip)
-#if DBDE_LINE_ALIGNED_STORES
         const uint32_t h = (uint32_t)((128u - (uint32_t)(reinterpret_cast<uintptr_t>(dst + 8u * lead) & 127u)) & 127u) >> 4;
         for (int base = h ? (int)h - 64 : 0; base < (int)npairs; base += 64) {
             const int i = base + lane;
             if (i < 0 || i >= (int)npairs) continue;
-#else
-        for (uint32_t i = lane; i < npairs; i += 64u) {
-#endif
             const uint32_t q = lead + 2u * (uint32_t)i;
             ulonglong2 v2;
             v2.x = pay[swz ? swzq8(q) : q];
             v2.y = pay[swz ? swzq8(q + 1u) : q + 1u];
-            if (DBDE_NT) {
-                u32x4_t o;
-                o[0] = (uint32_t)v2.x; o[1] = (uint32_t)(v2.x >> 32); o[2] = (uint32_t)v2.y; o[3] = (uint32_t)(v2.y >> 32);
-                __builtin_nontemporal_store(o, reinterpret_cast<u32x4_t *>(dst + 8ull * q));
-            } else {
-                *reinterpret_cast<ulonglong2 *>(dst + 8ull * q) = v2;
-            }
+            u32x4_t o;
+            o[0] = (uint32_t)v2.x; o[1] = (uint32_t)(v2.x >> 32); o[2] = (uint32_t)v2.y; o[3] = (uint32_t)(v2.y >> 32);
+            __builtin_nontemporal_store(o, reinterpret_cast<u32x4_t *>(dst + 8ull * q));
         }
         if ((rest & 1u) && lane == 63) {
             const uint32_t q = wtot - 1u;
             *reinterpret_cast<uint64_t *>(dst + 8ull * q) = pay[swz ? swzq8(q) : q];
         }
     } else {
-#if DBDE_UNALIGNED_OUT_WORDS   // (round 1-4a form: one 8-byte store per word at whatever address it has)
-        for (uint32_t q = lane; q < wtot; q += 64u) store_u64_any(dst + 8ull * q, pay[swz ? swzq8(q) : q]);
-#else
         // Any alignment of the frame (tile counts that are no multiple of 4, odd slot strides or bases): per-lane 8-byte stores
         // at 2 or 4 mod 8 cost the encoder 12-15 % (1008x1000 0.63 against 1008x1008 0.72, profiles/r04b_unaligned.sh).  The
         // wave's byte range leaves as ALIGNED 16-byte blocks instead, whole cache lines per store instruction as above; a
@@ -1002,8 +973,7 @@ __device__ __forceinline__ void store_wave_part(const EncParams &p, const ChunkR
                     o[3] = __builtin_amdgcn_alignbyte(low ? d4 : d5, low ? d3 : d4, rr);
                 }
                 if (!first && !last) {
-                    if (DBDE_NT) __builtin_nontemporal_store(o, reinterpret_cast<u32x4_t *>(blk0 + 16ll * j));
-                    else *reinterpret_cast<u32x4_t *>(blk0 + 16ll * j) = o;
+                    __builtin_nontemporal_store(o, reinterpret_cast<u32x4_t *>(blk0 + 16ll * j));
                 } else {
                     // o holds the range's bytes from the block's first valid one on: n of them go to where that one belongs
                     uint8_t *to = first ? dst : blk0 + 16ll * j;
@@ -1019,7 +989,6 @@ __device__ __forceinline__ void store_wave_part(const EncParams &p, const ChunkR
                 }
             }
         }
-#endif
     }
 }
 
@@ -1286,30 +1255,15 @@ __global__ __launch_bounds__(kEncThreads, 4) void encode_kernel(EncParams p) {
                 }
             }
         };
-        // Order (DBDE_POLL, A/B builds).  The shipped order is 0: lane 0 polls prev's mailbox FIRST -- prev's AGG was
-        // published a whole step ago, so the scanner has normally answered -- then every wave issues its prefetch and
-        // reduces cur.  Vector-memory results return in issue order, so a poll issued behind the prefetch would wait
-        // for the pixels.  The alternatives (1: poll after the statistics; 2: wave 0 reduces cur first, polls, and only
-        // then prefetches) measured equal or worse in round 2 (the prefetch then arrives late); the wait
-        // that remains is the in-order prefix itself, not the position of the poll.
-#if DBDE_POLL == 0
+        // Order: lane 0 polls prev's mailbox FIRST -- prev's AGG was published a whole step ago, so the scanner has
+        // normally answered -- then every wave issues its prefetch and reduces cur.  Vector-memory results return in
+        // issue order, so a poll issued behind the prefetch would wait for the pixels.  The alternatives (poll after the
+        // statistics; wave 0 reduces cur first, polls, and only then prefetches) measured equal or worse in round 2
+        // (the prefetch then arrives late); the wait that remains is the in-order prefix itself, not the
+        // position of the poll.
         mailbox();
         load_nxt();
         statistics();
-#elif DBDE_POLL == 1
-        load_nxt();
-        statistics();
-        mailbox();
-#else
-        if (wave == 0) {
-            statistics();
-            mailbox();
-            load_nxt();
-        } else {
-            load_nxt();
-            statistics();
-        }
-#endif
 #ifdef DBDE_DIAG
         const uint64_t dg_b0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -1386,7 +1340,7 @@ __global__ __launch_bounds__(kEncThreads, 4) void encode_kernel(EncParams p) {
         prev_meta = PIX == 2 ? dA | (mnA << 16) : dA | (dB << 8) | (mnA << 16) | (mnB << 24);
         prev_wbase = wbase;
         prev_wtot = wtot;
-        prev_swz = all8 || DBDE_ENC_SWZ_ALL;
+        prev_swz = all8;
         prev_total = cur_total;
         cur = nxt;
         nxt = chunk_ref<PIX>(p, lb_ok ? next_id : 0xFFFFFFFFu, tid);
@@ -1591,7 +1545,7 @@ __global__ __launch_bounds__(kEncThreads, 4) void encode_small_kernel(EncParams 
         glob += sh.pre[q][1];
     }
     if (k.valid) {
-        store_wave_part<ALIGNED_OUT>(p, k, dA | (dB << 8) | (mnA << 16) | (mnB << 24), wbase, wtot, inf, glob, pay, lane, all8 || DBDE_ENC_SWZ_ALL);
+        store_wave_part<ALIGNED_OUT>(p, k, dA | (dB << 8) | (mnA << 16) | (mnB << 24), wbase, wtot, inf, glob, pay, lane, all8);
         if (tid == 64 * (kEncWaves - 1) && (k.cf == 0u || k.cf == p.chunks_per_frame - 1u))
             write_frame_fields<ALIGNED_OUT>(p, k.f, k.cf, inf + total, glob - inf);
     }
@@ -2074,13 +2028,6 @@ __device__ __forceinline__ uint32_t swz_byte16(uint32_t A) { return A ^ ((A >> 4
 // byte alignment ops (v_alignbyte) instead of 64-bit shifts; the two 4d-bit halves are split
 // with v_alignbit and expanded with v_bfe.  The minimum is added byte-wise with wrap-around, as
 // the reference's _mm_add_epi8 does (dbde_util.cpp:245-277).
-#ifndef DBDE_DEC_SWZ_ALL
-#define DBDE_DEC_SWZ_ALL 0   // A/B switch: 1 = the decoder's payload image swizzled for every chunk (round-2 start)
-#endif
-#ifndef DBDE_DEC_SWZ_REGULAR
-#define DBDE_DEC_SWZ_REGULAR 1   // A/B switch: 0 = swizzle for all-depth-8 chunks only
-#endif
-#ifndef DBDE_UNPACK_PLAIN
 // byte k of x <- low byte of (g >> sh): one SDWA shift writes the field where it belongs and leaves the other bytes
 __device__ __forceinline__ void put_byte1(uint32_t &x, uint32_t sh, uint32_t g) {
     asm("v_lshrrev_b32_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(x) : "v"(sh), "v"(g));
@@ -2091,7 +2038,6 @@ __device__ __forceinline__ void put_byte2(uint32_t &x, uint32_t sh, uint32_t g) 
 __device__ __forceinline__ void put_byte3(uint32_t &x, uint32_t sh, uint32_t g) {
     asm("v_lshrrev_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(x) : "v"(sh), "v"(g));
 }
-#endif
 
 template <bool SWZ>
 __device__ __forceinline__ void unpack_tile_from_lds(const uint8_t *s_img, uint32_t byte_base, uint32_t d,
@@ -2099,11 +2045,6 @@ __device__ __forceinline__ void unpack_tile_from_lds(const uint8_t *s_img, uint3
     const uint32_t mn4 = mn * 0x01010101u;
     const bool d8 = d >= 8u;
     uint32_t a = byte_base;
-#ifdef DBDE_UNPACK_PLAIN
-    const uint32_t m1 = ((1u << d) - 1u) * 0x00010001u;            // d-bit fields in 16-bit lanes
-    const uint32_t m2 = (1u << (2u * d)) - 1u;                     // 2d <= 16
-    const uint32_t m4 = d >= 8u ? 0xFFFFFFFFu : ((1u << (4u * d)) - 1u);
-#else
     // four d-bit fields of a 4d-bit group -> the low d bits of four bytes: byte k takes the low byte of (group >> k*d)
     // (three SDWA shifts), what lies above the field goes with one mask; the minimum is added byte-wise with the
     // carries cut at bit 7 (add_bytes), the three masks folded into per-tile constants
@@ -2111,7 +2052,6 @@ __device__ __forceinline__ void unpack_tile_from_lds(const uint8_t *s_img, uint3
     const uint32_t md7 = md & 0x7F7F7F7Fu, mdh = md & 0x80808080u;
     const uint32_t mnlo = mn4 & 0x7F7F7F7Fu, mnhi = mn4 & 0x80808080u;
     const uint32_t d2 = 2u * d, d3 = 3u * d;
-#endif
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         uint32_t t0, t1, t2;   // the three dwords that hold bytes [a, a+8)
@@ -2127,24 +2067,12 @@ __device__ __forceinline__ void unpack_tile_from_lds(const uint8_t *s_img, uint3
         }
         const uint32_t r_lo = __builtin_amdgcn_alignbyte(t1, t0, a);   // bytes [a, a+4)
         const uint32_t r_hi = __builtin_amdgcn_alignbyte(t2, t1, a);   // bytes [a+4, a+8)
-#ifdef DBDE_UNPACK_PLAIN
-        const uint32_t g_lo = r_lo & m4;
-        const uint32_t g_hi = (d8 ? r_hi : __builtin_amdgcn_alignbit(r_hi, r_lo, 4u * d)) & m4;
-        // 4d-bit field -> two 2d-bit fields in 16-bit lanes -> four d-bit fields in bytes
-        const uint32_t f_lo = (g_lo & m2) | (__builtin_amdgcn_ubfe(g_lo, 2u * d, 2u * d) << 16);
-        const uint32_t f_hi = (g_hi & m2) | (__builtin_amdgcn_ubfe(g_hi, 2u * d, 2u * d) << 16);
-        const uint32_t x = (f_lo & m1) | (((f_lo >> d) & m1) << 8);
-        const uint32_t y = (f_hi & m1) | (((f_hi >> d) & m1) << 8);
-        v[2 * r] = add_bytes(x, mn4);
-        v[2 * r + 1] = add_bytes(y, mn4);
-#else
         const uint32_t g_hi = d8 ? r_hi : __builtin_amdgcn_alignbit(r_hi, r_lo, 4u * d);   // (the shift count is taken modulo 32)
         uint32_t x = r_lo, y = g_hi;
         put_byte1(x, d, r_lo); put_byte2(x, d2, r_lo); put_byte3(x, d3, r_lo);
         put_byte1(y, d, g_hi); put_byte2(y, d2, g_hi); put_byte3(y, d3, g_hi);
         v[2 * r] = (((x & md7) + mnlo) ^ (x & mdh)) ^ mnhi;
         v[2 * r + 1] = (((y & md7) + mnlo) ^ (y & mdh)) ^ mnhi;
-#endif
         a += d;
     }
 }
@@ -2275,11 +2203,7 @@ __global__ __launch_bounds__(THREADS) void decode_kernel(DecParams p) {
     const uint32_t c = SELF_INDEX ? blockIdx.x : xcd_local_chunk(blockIdx.x, p.n_chunks);
     const uint32_t f = c / p.chunks_per_frame;
     const uint32_t cf = c - f * p.chunks_per_frame;
-#ifdef DBDE_DEC_FAKE_INDEX   // (probe: what the index round trip costs -- one slot per frame at abbench's stride, every tile of depth 8)
-    const uint64_t foff = (uint64_t)f * (((32ull + 66ull * p.T) + 255ull) / 256ull * 256ull);
-#else
     const uint64_t foff = p.frame_offsets[f];
-#endif
     const uint8_t *fb = p.stream + foff;
     const uint32_t t_begin = dec_chunk_begin(p.geom, cf);
     const uint32_t n_tiles = dec_chunk_begin(p.geom, cf + 1u) - t_begin;   // <= 512
@@ -2485,19 +2409,12 @@ __global__ __launch_bounds__(THREADS) void decode_kernel(DecParams p) {
         SF_MARK(3);
     } else {
         // everything the address arithmetic needs, requested together
-#ifdef DBDE_DEC_FAKE_INDEX
-        const uint32_t ok = 1u;
-        w_begin = 8u * t_begin; w_end = 8u * (t_begin + n_tiles);
-#else
         const uint32_t ok = p.frame_ok[f];
         const uint32_t *co = p.chunk_off + (size_t)f * (p.chunks_per_frame + 1u) + cf;
         w_begin = co[0]; w_end = co[1];
-#endif
-#ifndef DBDE_IDX_SERIAL
         // ... and really together: without this the compiler sinks the loads behind the branch (three dependent
         // scalar round trips before the first payload byte is requested)
         asm volatile("" :: "s"(ok), "s"(w_begin), "s"(w_end), "s"((uint32_t)foff));
-#endif
         if (!ok) return;   // rejected frame: image untouched (dbde_util.cpp:296-303)
     }
 
@@ -2522,7 +2439,7 @@ __global__ __launch_bounds__(THREADS) void decode_kernel(DecParams p) {
     // nothing, that is all).  Any other chunk is read at offsets as irregular as its depths, or at strides that
     // measured no slower, and the swizzle would only be address arithmetic in the unpack (6 VALU per tile row:
     // mixed 0.75 -> 0.78, uniform depth 2 / 3 0.72 / 0.75 -> 0.77 / 0.78).
-    const bool swz = DBDE_DEC_SWZ_ALL || chunk_words == 8u * n_tiles || (DBDE_DEC_SWZ_REGULAR && (chunk_words == 4u * n_tiles || chunk_words == 7u * n_tiles));
+    const bool swz = chunk_words == 8u * n_tiles || chunk_words == 4u * n_tiles || chunk_words == 7u * n_tiles;
     const uint32_t n16r = (n16 + 15u) & ~15u;
     // Never read past the extent the caller declared (dbde_hip.h: stream_bytes is the READABLE extent): the
     // whole-slot DMA stops before a slot that straddles the end; that slot (the last one of the last chunk
@@ -2537,7 +2454,7 @@ __global__ __launch_bounds__(THREADS) void decode_kernel(DecParams p) {
             const uint32_t wave_slot0 = (uint32_t)j * G::kThreads + (uint32_t)wave * 64u;
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) void *)(asrc + 16ull * src_slot),
-                (__attribute__((address_space(3))) void *)(&s_in[2u * wave_slot0]), 16, 0, DBDE_NT ? 2 : 0);
+                (__attribute__((address_space(3))) void *)(&s_in[2u * wave_slot0]), 16, 0, 2 /* nt */);
         }
     }
     if (n16_dma != n16 && tid < 16) {   // the straddling slot, byte by byte: logical slot L lives at physical swz16(L)
@@ -2604,8 +2521,7 @@ __global__ __launch_bounds__(THREADS) void decode_kernel(DecParams p) {
                     o[0] = va[2 * r]; o[1] = va[2 * r + 1]; o[2] = vb[2 * r]; o[3] = vb[2 * r + 1];
                     // (single-frame launches, whose image nobody reads back: plain stores measured +1.4 us per round trip, the sc0 / sc1 / nt
                     // combinations within 0.5 us of each other -- the 4 us in which these stores retire are the memory side's)
-                    if (DBDE_NT) __builtin_nontemporal_store(o, reinterpret_cast<u32x4_t *>(base + (size_t)yy * (size_t)p.W));
-                    else *reinterpret_cast<u32x4_t *>(base + (size_t)yy * (size_t)p.W) = o;
+                    __builtin_nontemporal_store(o, reinterpret_cast<u32x4_t *>(base + (size_t)yy * (size_t)p.W));
                 }
             }
         }
@@ -2671,8 +2587,7 @@ __global__ __launch_bounds__(THREADS) void decode_kernel(DecParams p) {
                 if (yy < (uint32_t)p.H) {
                     u32x4_t o;
                     o[0] = va[2 * r]; o[1] = va[2 * r + 1]; o[2] = vb[2 * r]; o[3] = vb[2 * r + 1];
-                    if (DBDE_NT) __builtin_nontemporal_store(o, reinterpret_cast<u32x4_t *>(base + (size_t)yy * (size_t)p.W));
-                    else *reinterpret_cast<u32x4_t *>(base + (size_t)yy * (size_t)p.W) = o;
+                    __builtin_nontemporal_store(o, reinterpret_cast<u32x4_t *>(base + (size_t)yy * (size_t)p.W));
                 }
             }
         }
@@ -2734,8 +2649,7 @@ __global__ __launch_bounds__(THREADS) void decode_kernel(DecParams p) {
                 if (16u * j + 16u <= head || 16u * j >= head + bytes) continue;   // (blocks of the first line before the range)
                 if (16u * j >= head && 16u * j + 16u <= head + bytes) {
                     const u32x4_t q = *reinterpret_cast<const u32x4_t *>(l0 + 16u * j);
-                    if (DBDE_NT) __builtin_nontemporal_store(q, reinterpret_cast<u32x4_t *>(a0 + 16ull * j));
-                    else *reinterpret_cast<u32x4_t *>(a0 + 16ull * j) = q;
+                    __builtin_nontemporal_store(q, reinterpret_cast<u32x4_t *>(a0 + 16ull * j));
                 } else {       // first / last block of the range: only the bytes that belong to it
 #pragma unroll
                     for (uint32_t b = 0; b < 16u; b++) {
@@ -2824,8 +2738,7 @@ __global__ __launch_bounds__(THREADS) void decode_kernel(DecParams p) {
                 if (!live[k]) continue;
                 const bool first = 16u * j < g7, last = 16u * j + 16u > g7 + bytes;
                 if (!first && !last) {
-                    if (DBDE_NT) __builtin_nontemporal_store(q, reinterpret_cast<u32x4_t *>(a0 + 16ull * j));
-                    else *reinterpret_cast<u32x4_t *>(a0 + 16ull * j) = q;
+                    __builtin_nontemporal_store(q, reinterpret_cast<u32x4_t *>(a0 + 16ull * j));
                 } else {
                     // q holds the range's bytes from the block's first valid one: n of them go to dst (any alignment)
                     uint8_t *dst = first ? g_first : a0 + 16ull * j;
@@ -2864,15 +2777,6 @@ struct MidMeta {
     uint32_t nb, nm, n64;     // the frame's three I32 fields (every lane of a frame asks for the same words)
 };
 
-#ifndef DBDE_MID_NT
-#define DBDE_MID_NT DBDE_NT   // A/B switch: the staged image leaves with non-temporal stores
-#endif
-#ifndef DBDE_MID_STAGE_ROWS
-#define DBDE_MID_STAGE_ROWS 4   // image rows (and bases) that are multiples of this many bytes take the staged form (A/B: 8 = the round-4b start)
-#endif
-#ifndef DBDE_MID_NO_STAGE
-#define DBDE_MID_NO_STAGE 0   // A/B switch: 1 = tile rows stored straight from the registers at every width
-#endif
 #ifndef DBDE_MID_WAVES
 #define DBDE_MID_WAVES 6   // (the register allocator's target; the 256-thread instance comes out at 64 VGPRs = eight waves per SIMD without scratch, asked for eight it spills)
 #endif
@@ -2991,11 +2895,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : DBDE_MID_WAVES) void
         const uint32_t poff = (uint32_t)(reinterpret_cast<uintptr_t>(pay) & 3u);
         const uint8_t *psrc = pay - poff;
         const uint32_t npc_all = (8u * d + poff + 15u) >> 4;
-#ifdef DBDE_MID_ABLATE_LOADS
-        const bool whole = false;
-#else
         const bool whole = ok && d != 0u && psrc + 16u * npc_all <= s_end;   // every piece lies inside the readable extent
-#endif
         const uint32_t npc = whole ? npc_all : 0u;
         u32x4_t q0 = {0u, 0u, 0u, 0u}, q1 = q0, q2 = q0, q3 = q0, q4 = q0;
         if (npc > 0u) __builtin_memcpy(&q0, psrc, 16);
@@ -3018,11 +2918,9 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : DBDE_MID_WAVES) void
             if (npc > 3u) sl[3] = q3;
             if (npc > 4u) sl[4] = q4;
         }
-#ifndef DBDE_MID_ABLATE_LOADS
         if (ok && d != 0u && !whole) {   // the stream's last bytes: nothing past the extent
             for (uint32_t b = 0; b < 8u * d; b++) s_lds[slot + poff + b] = pay[b];
         }
-#endif
         uint32_t v[16];
 #pragma unroll
         for (int i = 0; i < 16; i++) v[i] = 0;
@@ -3036,9 +2934,6 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : DBDE_MID_WAVES) void
 #pragma unroll
             for (int r = 0; r < 8; r++) {
                 const uint32_t lo = v[2 * r], hi = v[2 * r + 1];
-#ifdef DBDE_MID_ABLATE_STORES
-                if (lo == 0x12345678u && hi == 0x9ABCDEF0u) {
-#else
                 if (STAGED) {
                     if ((uint32_t)r < rv) {   // (rows of W % 8 == 0: 8-byte aligned; of W % 8 == 4: two dwords, the row's last tile one)
                         const uint32_t a = px0 + (uint32_t)r * Wu;
@@ -3049,7 +2944,6 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : DBDE_MID_WAVES) void
                         }
                     }
                 } else if ((uint32_t)r < rv) {   // only the valid region is written (dbde_util.cpp:281-289)
-#endif
                     uint8_t *row = dst + (size_t)r * Wu;
                     const uint64_t q = ((uint64_t)hi << 32) | lo;
                     if (rm == 8u) store_u64_any(row, q);
@@ -3075,11 +2969,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : DBDE_MID_WAVES) void
                     uint8_t *dst = g0 - sh + 16ull * j;
                     if (16u * j >= sh && 16u * j + 16u <= sh + nbytes) {
                         const u32x4_t q = *reinterpret_cast<const u32x4_t *>(s_lds + 16u * j);
-#ifdef DBDE_MID_ABLATE_STORES
-                        if (q[0] != 0x12345678u || q[3] != 0x9ABCDEF1u) continue;
-#endif
-                        if (DBDE_MID_NT) __builtin_nontemporal_store(q, reinterpret_cast<u32x4_t *>(dst));
-                        else *reinterpret_cast<u32x4_t *>(dst) = q;
+                        __builtin_nontemporal_store(q, reinterpret_cast<u32x4_t *>(dst));
                     } else {
 #pragma unroll
                         for (uint32_t k = 0; k < 4u; k++) {
@@ -3108,20 +2998,32 @@ __global__ __launch_bounds__(THREADS, THREADS == 1024 ? 4 : DBDE_MID_WAVES) void
     }
 }
 
-hipError_t launch_decode_mid(const DecParams &p, uint32_t n_frames, uint32_t n_cu, hipStream_t s) {
+void decode_mid_blocks_per_cu(int (&per_cu)[2][3]) {
+    auto ask = [](auto kernel, int threads) {
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, 0) != hipSuccess || n < 1) n = 1;
+        return n;
+    };
+    per_cu[0][0] = ask(decode_mid_kernel<256, false>, 256);
+    per_cu[0][1] = ask(decode_mid_kernel<512, false>, 512);
+    per_cu[0][2] = ask(decode_mid_kernel<1024, false>, 1024);
+    per_cu[1][0] = ask(decode_mid_kernel<256, true>, 256);
+    per_cu[1][1] = ask(decode_mid_kernel<512, true>, 512);
+    per_cu[1][2] = ask(decode_mid_kernel<1024, true>, 1024);
+}
+
+hipError_t launch_decode_mid(const DecParams &p, uint32_t n_frames, uint32_t n_cu, const int (&per_cu)[2][3], hipStream_t s) {
     DecParams q = p;
     q.n_chunks = n_frames;
     const uint32_t th = mid_decode_threads_for(p.T), per_wg = th / p.T;
     uint32_t groups = (n_frames + per_wg - 1u) / per_wg;
-    // 8-byte aligned image rows: pixels staged in LDS, aligned 16-byte stores (decode_mid_kernel<., true>)
-    const bool staged = p.W % DBDE_MID_STAGE_ROWS == 0 && (reinterpret_cast<uintptr_t>(p.images) & (DBDE_MID_STAGE_ROWS - 1)) == 0u && !DBDE_MID_NO_STAGE;
+    // 4-byte aligned image rows and base: pixels staged in LDS, aligned 16-byte stores (decode_mid_kernel<., true>)
+    const bool staged = p.W % 4 == 0 && (reinterpret_cast<uintptr_t>(p.images) & 3u) == 0u;
     auto go = [&](auto kernel, uint32_t threads) {
         // persistent: as many workgroups as the device holds (n_cu = 0, tests: three, so that small batches walk the
         // pipelined loop too)
-        static int resident_per_cu[2][3] = {{0, 0, 0}, {0, 0, 0}};   // (asked once per instance)
-        int &per_cu = resident_per_cu[staged ? 1 : 0][threads == 256u ? 0 : (threads == 512u ? 1 : 2)];
-        if (per_cu < 1 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)threads, 0) != hipSuccess || per_cu < 1)) per_cu = 1;
-        const uint32_t resident = n_cu ? n_cu * (uint32_t)per_cu : 3u;
+        const int wg = per_cu[staged ? 1 : 0][threads == 256u ? 0 : (threads == 512u ? 1 : 2)];
+        const uint32_t resident = n_cu ? n_cu * (uint32_t)wg : 3u;
         hipLaunchKernelGGL(kernel, dim3(groups < resident ? groups : resident), dim3(threads), 0, s, q);
     };
     if (staged) {
@@ -3137,21 +3039,20 @@ hipError_t launch_decode_mid(const DecParams &p, uint32_t n_frames, uint32_t n_c
 }
 
 // ---------------------------------------------------------------------------------------
-// Frames of 65 .. 1024 tiles, whole frames per workgroup, STAGED: coalesced on both sides (round 4)
+// Frames of 65 .. 1024 tiles, whole frames per workgroup, STAGED: coalesced on both sides (round 4, encode)
 // ---------------------------------------------------------------------------------------
-// encode_mid_kernel / decode_mid_kernel fetch a tile with eight strided 8-byte loads per lane and emit its payload with
-// per-lane 8-byte stores: the access shape the chunk kernels were built to avoid, 0.37-0.50 of peak, and only up to 256
-// (160) tiles; above that a frame took a whole 1024-tile chunk with most lanes idle (160x120: 0.36).  Here a workgroup of
-// 256 or 512 threads owns as many whole frames as fit its 512 / 1024 tile slots (two tiles per lane) and
+// encode_mid_kernel fetches a tile with eight strided 8-byte loads per lane and emits its payload with per-lane 8-byte
+// stores: the access shape the chunk kernels were built to avoid, 0.37-0.50 of peak, and only up to 256 tiles; above that
+// a frame took a whole 1024-tile chunk with most lanes idle (160x120: 0.36).  Here a workgroup of 256 or 512 threads owns
+// as many whole frames as fit its 512 / 1024 tile slots (two tiles per lane) and
 //   * the frames' pixels -- ONE contiguous byte range, frames follow each other in the batch -- travel as whole 16-byte
-//     blocks between global memory and an LDS image; tiles are cut out of (put into) that image with aligned 8-byte LDS
-//     accesses (taken when rows are 8-byte aligned: W % 8 == 0, frames and base multiples of 16 bytes);
-//   * a frame's stream bytes travel as aligned 16-byte blocks too: the encoder assembles every frame in LDS -- header,
+//     blocks from global memory into an LDS image; tiles are cut out of that image with aligned 8-byte LDS accesses (taken
+//     when rows are 8-byte aligned: W % 8 == 0, frames and base multiples of 16 bytes);
+//   * a frame's stream bytes leave as aligned 16-byte blocks too: the encoder assembles every frame in LDS -- header,
 //     fields, depth and minimum bytes as they lie in the frame; payload words 8-byte aligned beside them -- and the
-//     copy-out shifts the payload into place (five aligned dwords and four v_alignbyte per block, as the staged decoder
-//     does); the decoder lands the frame's bytes where LDS and global addresses agree mod 16 and unpacks from there.
-// One slot per frame on the encode side (nothing is shared between frames: no workspace, nothing to wait for); the decoder
-// takes any frame offsets.  Validation is the reference's (dbde_util.cpp:295-303) plus depth <= 8 and the readable extent.
+//     copy-out shifts the payload into place (five aligned dwords and four v_alignbyte per block).
+// One slot per frame (nothing is shared between frames: no workspace, nothing to wait for).  The decode side of this pair
+// measured no faster than decode_mid_kernel and the chunk decoder it would replace and was removed.
 // 16 bytes at offset o of a frame whose first `meta` = 32 + 2T bytes lie at m and whose payload words lie 8-byte aligned at
 // LDS byte address pay0 (pay: the same place as a pointer): whole blocks of the fields' image as they are; payload blocks
 // as five aligned dwords shifted into place; the one block that holds the end of the minimum array byte by byte.
@@ -3221,7 +3122,7 @@ __global__ __launch_bounds__(THREADS) void encode_frames_kernel(EncParams p) {
         const uint32_t n16 = nf * (P >> 4);
         for (uint32_t i = tid; i < n16; i += THREADS)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + 16ull * i),
-                                             (__attribute__((address_space(3))) void *)(s_px + 2u * (i - lane)), 16, 0, DBDE_NT ? 2 : 0);
+                                             (__attribute__((address_space(3))) void *)(s_px + 2u * (i - lane)), 16, 0, 2 /* nt */);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (a barrier does not drain vector memory)
     }
     __syncthreads();
@@ -3302,8 +3203,7 @@ __global__ __launch_bounds__(THREADS) void encode_frames_kernel(EncParams p) {
             const u32x4_t q = frame_block(m, pay0, pay, meta, o);
             uint8_t *dst = out + o;
             if (o + 16u <= len) {
-                if (DBDE_NT) __builtin_nontemporal_store(q, reinterpret_cast<u32x4_t *>(dst));
-                else *reinterpret_cast<u32x4_t *>(dst) = q;
+                __builtin_nontemporal_store(q, reinterpret_cast<u32x4_t *>(dst));
             } else {   // the frame's last, partial block: its bytes and nothing behind them (lengths are even)
                 uint32_t n = len - o;
                 uint64_t lo = ((uint64_t)q[1] << 32) | q[0];
@@ -3370,7 +3270,7 @@ __global__ __launch_bounds__(kGroupThreads, 4) void encode_group_kernel(EncParam
         const uint32_t j0 = sh ? 1u : 0u, j1 = total >> 4;           // whole blocks [j0, j1)
         for (uint32_t i = tid; j0 + i < j1; i += TH)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src0 + 16ull * (j0 + i)),
-                                             (__attribute__((address_space(3))) void *)(&s_buf[b][2u * (j0 + i - lane)]), 16, 0, DBDE_NT ? 2 : 0);
+                                             (__attribute__((address_space(3))) void *)(&s_buf[b][2u * (j0 + i - lane)]), 16, 0, 2 /* nt */);
         uint8_t *img = reinterpret_cast<uint8_t *>(s_buf[b]);
         if (ROWS4 && wave == 0u) {
             const uint32_t head = sh ? (16u - sh) >> 2 : 0u;         // dwords in front of the first whole block
@@ -3465,8 +3365,7 @@ __global__ __launch_bounds__(kGroupThreads, 4) void encode_group_kernel(EncParam
                 const u32x4_t q = frame_block(m, pay0, pay, meta, o);
                 uint8_t *dst = out + o;
                 if (o + 16u <= len) {
-                    if (DBDE_NT) __builtin_nontemporal_store(q, reinterpret_cast<u32x4_t *>(dst));
-                    else *reinterpret_cast<u32x4_t *>(dst) = q;
+                    __builtin_nontemporal_store(q, reinterpret_cast<u32x4_t *>(dst));
                 } else {   // the frame's last, partial block: its bytes and nothing behind them (lengths are even)
                     const uint32_t n = len - o;
                     uint64_t lo = ((uint64_t)q[1] << 32) | q[0];
@@ -3508,7 +3407,7 @@ hipError_t launch_encode_group(const EncParams &p, uint32_t n_frames, uint32_t n
 // five on 256 (88 %) 0.50; 110 tiles 0.42 -> 0.49 / 0.415 -> 0.50; 132 tiles (90 % -> 77 %) 0.44 -> 0.49 / 0.41 -> 0.50; 144 tiles
 // 0.56 -> 0.60 / 0.51 -> 0.59; 300 tiles (88 % -> 59 %: one frame per workgroup) 0.51 -> 0.51 / 0.48 -> 0.53; never slower.
 #ifndef DBDE_FRAMES_512_FROM
-#define DBDE_FRAMES_512_FROM 513   // A/B switch: smallest frame (tiles) that takes the 512-thread workgroup
+#define DBDE_FRAMES_512_FROM 513   // smallest frame (tiles) that takes the 512-thread workgroup
 #endif
 uint32_t frames_threads_for(uint32_t T) {
     return T >= (unsigned)DBDE_FRAMES_512_FROM ? 512u : 256u;
@@ -3523,196 +3422,6 @@ hipError_t launch_encode_frames(const EncParams &p, uint32_t n_frames, hipStream
     const dim3 grid((n_frames + per_wg - 1u) / per_wg);
     if (th == 256u) hipLaunchKernelGGL(encode_frames_kernel<256>, grid, dim3(256), 0, s, q);
     else hipLaunchKernelGGL(encode_frames_kernel<512>, grid, dim3(512), 0, s, q);
-    return hipGetLastError();
-}
-
-// The mirror: as many whole frames as fit the workgroup's tile slots, each frame's bytes landed in LDS where LDS and global
-// addresses agree mod 16 (aligned 16-byte blocks; the first and last block of a frame byte by byte where they would reach
-// outside the readable extent), validated and unpacked from there, pixels staged in the same memory and written as whole
-// 16-byte blocks of the frames' contiguous image range.
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void decode_frames_kernel(DecParams p) {
-    typedef FramesLds<THREADS> G;
-    constexpr int NW = THREADS / 64;
-    // stream images of the frames: 32 + 66 T bytes each at most, + 16 of alignment slack and 16 of over-read each; later the pixels
-    constexpr uint32_t kBytes = (G::kCap * 66u + (G::kMaxFrames + 1u) * 352u + 255u) & ~255u;   // (+ up to 255 bytes per frame: each image starts a 256-byte swizzle group)
-    __shared__ __attribute__((aligned(16))) uint8_t s_buf[kBytes];
-    __shared__ uint32_t s_tot[NW];
-    __shared__ uint32_t s_fbase[G::kMaxFrames + 1], s_fend[G::kMaxFrames + 1], s_len[G::kMaxFrames + 1], s_ok[G::kMaxFrames + 1], s_at[G::kMaxFrames + 2];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t T = p.T, F = G::kCap / T;
-    const uint32_t f0 = blockIdx.x * F;
-    const uint32_t nf = p.n_chunks - f0 < F ? p.n_chunks - f0 : F;      // (n_chunks carries the frame count here)
-    const uint32_t P = (uint32_t)p.frame_pixels, W = (uint32_t)p.W;
-    const uint32_t meta = 32u + 2u * T;
-    const uint8_t *s_end = p.stream + p.stream_bytes;
-
-    // ---- how long each frame is (its n64 field), where its image starts in LDS ----
-    if (tid < nf) {
-        const uint64_t off = p.frame_offsets[f0 + tid];
-        uint32_t len = 0, ok = 0;
-        if (in_extent(off, meta, p.stream_bytes)) {
-            const uint32_t n64 = load_u32_bytes(p.stream + off + 28u + 2u * T);
-            if (n64 <= 8u * T && in_extent(off, (uint64_t)meta + 8ull * n64, p.stream_bytes)) { len = meta + 8u * n64; ok = 1u; }
-        }
-        s_len[tid] = len;       // 0: rejected without looking further (truncated, or a word count no depth array can have)
-        s_ok[tid] = ok;
-    }
-    __syncthreads();
-    if (tid == 0) {   // LDS byte where frame g's aligned cover starts: a whole 256-byte swizzle group, room for the shift and the unpack's over-read
-        uint32_t at = 0, all8 = 1u;
-        for (uint32_t g = 0; g < nf; g++) {
-            s_at[g] = at;
-            at += (s_len[g] + 15u + 48u + 255u) & ~255u;
-            if (s_len[g] && s_len[g] != meta + 64u * T) all8 = 0u;
-        }
-        s_at[nf] = at;
-        s_at[nf + 1u] = all8;
-    }
-    __syncthreads();
-    // Every tile of depth 8: lanes would read the image at a 128-byte stride, all of them on the same banks -- the image is
-    // XOR-swizzled at 16-byte granularity then (on the SOURCE side of the DMA, as decode_kernel does); any other content
-    // is read at offsets as irregular as its depths and stays linear (the swizzle would only be address arithmetic).
-    const bool swz = s_at[nf + 1u] != 0u;
-    auto phys = [&](uint32_t a) -> uint32_t { return swz ? swz_byte16(a) : a; };
-    // ---- the frames' bytes: aligned 16-byte blocks of global memory, by LDS-DMA, to the same offset mod 16 in LDS ----
-    for (uint32_t g = 0; g < nf; g++) {
-        const uint32_t len = s_len[g];
-        if (!len) continue;
-        const uint8_t *src = p.stream + p.frame_offsets[f0 + g];
-        const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 15u);
-        const uint8_t *a0 = src - sh;
-        const uint32_t slot0 = s_at[g] >> 4;                      // (a multiple of 16 slots: groups never straddle frames)
-        const uint32_t n16 = (sh + len + 15u) >> 4, n16r = (n16 + 15u) & ~15u;
-        for (uint32_t i = tid; i < n16r; i += THREADS) {
-            const uint32_t li = swz ? swz16(slot0 + i) - slot0 : i;   // physical slot i of the frame's image <- logical slot li (the permutation is on ABSOLUTE slots and stays inside a group of 16)
-            const uint8_t *a = a0 + 16ull * li;
-            if (li < n16 && a >= p.stream && a + 16 <= s_end)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)a,
-                                                 (__attribute__((address_space(3))) void *)(s_buf + 16u * (slot0 + i - lane)), 16, 0, DBDE_NT ? 2 : 0);
-        }
-        // the (at most two) blocks that reach outside the readable extent: their inside bytes only
-        if (tid < 32u) {
-            const uint32_t li = tid < 16u ? 0u : n16 - 1u, b = tid & 15u;
-            const uint8_t *a = a0 + 16ull * li;
-            if ((a < p.stream || a + 16 > s_end) && (tid < 16u || n16 > 1u))
-                s_buf[phys(16u * (slot0 + li) + b)] = (a + b >= p.stream && a + b < s_end) ? a[b] : (uint8_t)0;
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    // ---- two tiles per lane: depth, minimum; offsets and the reference's validation by a scan over the depths ----
-    uint32_t d[2], mnv[2], fl[2], tt[2], fimg[2];
-    bool has[2];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const uint32_t t = 2u * tid + (uint32_t)k;
-        has[k] = t < nf * T;
-        uint32_t rem;
-        fl[k] = has[k] ? div_magic(t, T, p.magic_W, rem) : 0u;        // (magic_W carries floor(2^32 / T) here)
-        tt[k] = has[k] ? rem : 0u;
-        has[k] = has[k] && s_ok[fl[k]] != 0u;
-        const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p.stream + p.frame_offsets[f0 + fl[k]]) & 15u);
-        fimg[k] = s_at[fl[k]] + sh;                                     // LDS byte of the frame's first byte
-        d[k] = has[k] ? s_buf[phys(fimg[k] + 24u + tt[k])] : 0u;
-        mnv[k] = has[k] ? s_buf[phys(fimg[k] + 28u + T + tt[k])] : 0u;
-    }
-    // payload words (low 20 bits) and "a depth above 8" count (above them) in one scan
-    const uint32_t item0 = d[0] | (d[0] > 8u ? 1u << 20 : 0u), item1 = d[1] | (d[1] > 8u ? 1u << 20 : 0u);
-    uint32_t block_total;
-    const uint32_t incl = block_scan_incl<NW>(item0 + item1, s_tot, (int)lane, (int)wave, block_total);
-    const uint32_t excl[2] = {incl - item0 - item1, incl - item1};
-    const uint32_t item[2] = {item0, item1};
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        if (has[k] && tt[k] == 0u) s_fbase[fl[k]] = excl[k];
-        if (has[k] && tt[k] == T - 1u) s_fend[fl[k]] = excl[k] + item[k];
-    }
-    __syncthreads();
-    // the verdict of every frame (dbde_util.cpp:295-303, + depth <= 8), its result record
-    if (tid < nf) {
-        const uint64_t off = p.frame_offsets[f0 + tid];
-        bool ok = s_ok[tid] != 0u;
-        uint32_t total = 0;
-        if (ok) {
-            const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p.stream + off) & 15u);
-            const uint32_t fb = s_at[tid] + sh;
-            auto rd32 = [&](uint32_t a) -> uint32_t {
-                return (uint32_t)s_buf[phys(fb + a)] | ((uint32_t)s_buf[phys(fb + a + 1u)] << 8) | ((uint32_t)s_buf[phys(fb + a + 2u)] << 16) |
-                       ((uint32_t)s_buf[phys(fb + a + 3u)] << 24);
-            };
-            const uint32_t span = s_fend[tid] - s_fbase[tid];
-            total = span & 0xFFFFFu;
-            const int32_t nb = (int32_t)rd32(20u), nm = (int32_t)rd32(24u + T), n64 = (int32_t)rd32(28u + 2u * T);
-            ok = nb == (int32_t)T && nm == (int32_t)T && n64 == (int32_t)total && (span >> 20) == 0u;
-        }
-        s_ok[tid] = ok ? 1u : 0u;
-        if (p.results) {
-            uint32_t field = 0;
-            uint64_t index = 0, elapsed = 0;
-            if (in_extent(off, 20, p.stream_bytes)) {
-                const uint8_t *fb = p.stream + off;
-                field = load_u32_bytes(fb);
-                index = load_u64_bytes(fb + 4);
-                elapsed = f64_to_u64_x86(__longlong_as_double((long long)load_u64_bytes(fb + 12)));
-            }
-            FrameResultDev *r = reinterpret_cast<FrameResultDev *>(p.results) + f0 + tid;
-            r->u64s = (field == 2u && ok) ? 2u : 0xFFFFFFFFu;   // dbde_util.cpp:335,342
-            r->pad_ = 0;
-            r->index = index;
-            r->elapsed_ns = elapsed;
-            r->consumed = ok ? (uint64_t)meta + 8ull * total : 20ull;
-        }
-    }
-    __syncthreads();
-
-    // ---- unpack (a tile row is the 8 d-bit integer at byte r d of the tile's payload) ----
-    uint32_t v[2][16];
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        has[k] = has[k] && s_ok[fl[k]] != 0u;
-        const uint32_t words = (excl[k] - s_fbase[fl[k]]) & 0xFFFFFu;
-        if (has[k]) {
-            if (swz) unpack_tile_from_lds<true>(s_buf, fimg[k] + meta + 8u * words, 8u, mnv[k], v[k]);
-            else unpack_tile_from_lds<false>(s_buf, fimg[k] + meta + 8u * words, d[k] > 8u ? 8u : d[k], mnv[k], v[k]);
-        }
-    }
-    __syncthreads();   // every tile is in registers: the memory changes hands
-
-    // ---- the pixels into the frames' image (aligned 8-byte rows), then out as whole 16-byte blocks ----
-    // (a rejected frame's image stays untouched, dbde_util.cpp:296-303: its blocks are not written)
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        if (!has[k]) continue;
-        const uint32_t ty = tt[k] / p.w, tx = tt[k] - ty * p.w;      // (once per tile: no launch constant kept for it)
-        const uint32_t base = fl[k] * P + 8u * tx;
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const uint32_t yy = 8u * ty + (uint32_t)r;
-            if (yy < (uint32_t)p.H) *reinterpret_cast<uint2 *>(s_buf + base + yy * W) = make_uint2(v[k][2 * r], v[k][2 * r + 1]);
-        }
-    }
-    __syncthreads();
-    for (uint32_t g = 0; g < nf; g++) {
-        if (!s_ok[g]) continue;
-        u32x4_t *dst = reinterpret_cast<u32x4_t *>(p.images + (size_t)(f0 + g) * P);
-        const u32x4_t *src = reinterpret_cast<const u32x4_t *>(s_buf + g * P);
-        for (uint32_t i = tid; i < (P >> 4); i += THREADS) {
-            if (DBDE_NT) __builtin_nontemporal_store(src[i], dst + i);
-            else dst[i] = src[i];
-        }
-    }
-}
-
-hipError_t launch_decode_frames(const DecParams &p, uint32_t n_frames, hipStream_t s) {
-    DecParams q = p;
-    q.n_chunks = n_frames;
-    q.magic_W = div_magic_of(p.T);
-    const uint32_t th = frames_threads_for(p.T), per_wg = (2u * th) / p.T;
-    const dim3 grid((n_frames + per_wg - 1u) / per_wg);
-    if (th == 256u) hipLaunchKernelGGL(decode_frames_kernel<256>, grid, dim3(256), 0, s, q);
-    else hipLaunchKernelGGL(decode_frames_kernel<512>, grid, dim3(512), 0, s, q);
     return hipGetLastError();
 }
 

@@ -13,7 +13,7 @@ for spec in "$@"; do
     if [ "${name#rev_}" != "$name" ]; then   # rev_<git revision>: the library as it was at that revision (same-box A/B against history)
         tmp=$(mktemp -d)
         git archive ${name#rev_} dbde-video-cpp_amd/csrc include | tar -x -C $tmp
-        make -s -C $tmp/dbde-video-cpp_amd/csrc
+        make -s -C $tmp/dbde-video-cpp_amd/csrc EXTRA="$flags"
         cp $tmp/dbde-video-cpp_amd/libdbde_hip.so $out/
         rm -rf $tmp
     elif [ "$name" == "r01" ]; then

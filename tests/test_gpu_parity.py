@@ -867,7 +867,7 @@ def test_seeded_fuzz_against_oracle(codec, oracle):
                                    # ... frames that are no whole 16-byte blocks: the persistent encoder's image shifts from group to group
                                    (20, 10, 200), (28, 9, 150)])
 @pytest.mark.parametrize("mode", ["noise8", "mixed", "smooth", "flat"])
-def test_tiny_frames_many_per_wave(codec, codec_staged_decode, codec_three_workgroups, oracle, W, H, n, mode):
+def test_tiny_frames_many_per_wave(codec, codec_three_workgroups, oracle, W, H, n, mode):
     """Frames of at most 64 tiles (the reference's randomized test is 1024 single-tile frames, dbde_util_test.cpp:66-96):
     one tile per lane, several frames per wave in both directions (encode_tiny_kernel for slots, decode_mid_kernel: whole frames per 256-thread workgroup);
     every frame byte for byte against the oracle, both layouts, partial tiles, a frame count that leaves lanes idle."""
@@ -884,8 +884,8 @@ def test_tiny_frames_many_per_wave(codec, codec_staged_decode, codec_three_workg
             for f in range(n):
                 assert frames3[f].tobytes() == frames[f].tobytes(), (W, H, mode, "three workgroups", f)
         total = int((offs[-1] + sizes[-1]).item())
-        # (the default forms, the staged whole-frame decoder where it applies, three persistent workgroups walking their loop)
-        for dec in (codec, codec_staged_decode, codec_three_workgroups):
+        # (the default forms, three persistent workgroups walking their loop)
+        for dec in (codec, codec_three_workgroups):
             canvas = torch.full_like(imgs, 0xEE)
             back, res = dec.decode_frames(buf, lead, total, offs, W, H, n, images=canvas)
             dec.sync()
@@ -900,7 +900,7 @@ def test_tiny_frames_many_per_wave(codec, codec_staged_decode, codec_three_workg
                                    (72, 72, 7), (200, 168, 7), (100, 75, 50), (104, 100, 33), (200, 150, 19), (168, 161, 10), (224, 200, 5), (176, 144, 1),
                                    (520, 65, 9), (8, 5200, 3)])
 @pytest.mark.parametrize("mode", ["noise8", "mixed", "smooth", "flat"])
-def test_mid_frames_many_per_workgroup(codec, codec_staged_decode, codec_three_workgroups, oracle, W, H, n, mode):
+def test_mid_frames_many_per_workgroup(codec, codec_three_workgroups, oracle, W, H, n, mode):
     """Frames of 65 .. 512 tiles (72 .. 180 pixels a side): one tile per lane, as many whole frames per 256 / 512 / 1024
     thread workgroup as fit (encode_mid_kernel for slots; decode_mid_kernel where it is the faster form); every frame
     byte for byte against the oracle, both layouts, partial tiles, frame counts that leave the last workgroup part empty."""
@@ -917,10 +917,10 @@ def test_mid_frames_many_per_workgroup(codec, codec_staged_decode, codec_three_w
             for f in range(n):
                 assert frames3[f].tobytes() == frames[f].tobytes(), (W, H, mode, "three workgroups", f)
         total = int((offs[-1] + sizes[-1]).item())
-        # the default forms, the staged whole-frame decoder where it applies, and decode_mid_kernel on three persistent
-        # workgroups: every workgroup walks its software-pipelined loop several times (metadata of the next group and the
-        # offset of the one after it in flight), the last iterations with groups that do not exist
-        for dec in (codec, codec_staged_decode, codec_three_workgroups):
+        # the default forms and decode_mid_kernel on three persistent workgroups: every workgroup walks its
+        # software-pipelined loop several times (metadata of the next group and the offset of the one after it in
+        # flight), the last iterations with groups that do not exist
+        for dec in (codec, codec_three_workgroups):
             canvas = torch.full_like(imgs, 0xEE)
             back, res = dec.decode_frames(buf, lead, total, offs, W, H, n, images=canvas)
             dec.sync()
@@ -948,30 +948,15 @@ def codec_three_workgroups(dv):
     c.close()
 
 
-@pytest.fixture(scope="module")
-def codec_staged_decode(dv):
-    """A context whose decode calls take decode_frames_kernel where the geometry allows ($DBDE_HIP_EXPERIMENT bit 8: the
-    staged whole-frame decoder is built and correct but not the default, it measured no faster)."""
-    import os
-    old = os.environ.get("DBDE_HIP_EXPERIMENT")
-    os.environ["DBDE_HIP_EXPERIMENT"] = str(256 | int(old or "0", 0))
-    c = dv.Codec(0)
-    if old is None:
-        del os.environ["DBDE_HIP_EXPERIMENT"]
-    else:
-        os.environ["DBDE_HIP_EXPERIMENT"] = old
-    yield c
-    c.close()
-
-
-@pytest.mark.parametrize("which", ["default", "staged", "three_workgroups"])
+@pytest.mark.parametrize("which", ["default", "three_workgroups"])
 @pytest.mark.parametrize("W,H,n", [(72, 72, 50), (160, 120, 23), (96, 96, 61), (200, 150, 9), (60, 60, 40), (100, 76, 30)])
-def test_staged_frame_decoder_takes_any_offsets_and_rejects_like_the_reference(codec, codec_staged_decode, codec_three_workgroups, oracle, W, H, n, which):
-    codec = {"default": codec, "staged": codec_staged_decode, "three_workgroups": codec_three_workgroups}[which]
-    """decode_frames_kernel: frames wherever they lie (concatenated: every alignment mod 16; a stream base that is odd), a
-    readable extent that ends with the last frame, and malformed frames among good ones -- nb / nm / n64 wrong, a depth
-    byte above 8, a truncated frame, a wild offset: rejected with u64s = 0xFFFFFFFF and consumed = 20 (dbde_util.cpp:
-    295-303, 335, 342), their images untouched, their neighbours decoded."""
+def test_staged_frame_decoder_takes_any_offsets_and_rejects_like_the_reference(codec, codec_three_workgroups, oracle, W, H, n, which):
+    codec = {"default": codec, "three_workgroups": codec_three_workgroups}[which]
+    """The decoders these shapes take (decode_mid_kernel; the chunk decoder for 300 and 475 tiles): frames wherever they
+    lie (concatenated: every alignment mod 16; a stream base that is odd), a readable extent that ends with the last
+    frame, and malformed frames among good ones -- nb / nm / n64 wrong, a depth byte above 8, a truncated frame, a wild
+    offset: rejected with u64s = 0xFFFFFFFF and consumed = 20 (dbde_util.cpp: 295-303, 335, 342), their images
+    untouched, their neighbours decoded."""
     import torch
     T = ((W + 7) // 8) * ((H + 7) // 8)
     imgs = codec.synth_frames("mixed", SEED, 3, n, W, H)

@@ -186,3 +186,21 @@ def test_small_frame_decoder_keeps_its_prefetch_in_flight(listing, mangled):
     latch = max(i for i in range(head) if lines[i].startswith(".LBB"))
     assert "in Loop: Header=" in lines[latch], lines[latch]
     assert not [ln for ln in lines[latch:head] if re.match(r"s_waitcnt.*vmcnt", ln)], lines[latch:head]
+
+
+def test_traffic_record_belongs_to_these_kernels(listing):
+    """bench.py replays the HBM bytes of profiles/hbm_traffic.json only while the record is keyed to the kernel sources.
+    The key must be these sources', and every recorded kernel (encode_kernel / decode_kernel instances) must compile
+    to the instruction streams the record's pass measured (isa_sha, written by profiles/rekey.py).  A change to
+    dbde_kernels.hip that leaves those kernels' code alone only needs `python3 profiles/rekey.py`; one that changes it
+    needs a new PMC pass."""
+    import json
+    import sys
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "profiles"))
+    import bench
+    import rekey
+    rec = json.load(open(os.path.join(ROOT, "profiles", "hbm_traffic.json")))
+    assert bench.kernels_fingerprint() == rec["kernels_sha"], "hbm_traffic.json is keyed to other sources: profiles/rekey.py"
+    assert rekey.isa_sha(rekey.bodies(os.path.join(CSRC, "dbde_kernels.s"))) == rec["isa_sha"], \
+        "the recorded kernels' instruction streams are not the ones the traffic pass measured"
