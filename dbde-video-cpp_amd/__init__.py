@@ -55,6 +55,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_scatter_join", "dbde_hip_scatter_sync", "dbde_hip_scatter_blocks", "dbde_hip_scatter_check",
     "dbde_hip_scatter_plan", "dbde_hip_create_on_own_stream", "dbde_hip_set_host_staging",
     "dbde_hip_decode_roi", "dbde_hip_unpack_image_roi", "dbde_hip_roi_plan",
+    "dbde16_hip_decode_roi", "dbde16_hip_roi_plan",
 ]
 
 
@@ -165,6 +166,10 @@ def lib():
     L.dbde_hip_decode_roi.restype = i
     L.dbde_hip_roi_plan.argtypes = [i, i, i, i, i, i, i, C.POINTER(RoiPlan)]
     L.dbde_hip_roi_plan.restype = i
+    L.dbde16_hip_decode_roi.argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, vp, vp]
+    L.dbde16_hip_decode_roi.restype = i
+    L.dbde16_hip_roi_plan.argtypes = [i, i, i, i, i, i, i, C.POINTER(RoiPlan)]
+    L.dbde16_hip_roi_plan.restype = i
     L.dbde_hip_unpack_frame.argtypes = [vp, C.POINTER(vp), i, i, vp]
     L.dbde_hip_pack_frame_header.restype = sz
     L.dbde_hip_pack_frame_header.argtypes = [C.POINTER(FrameHeader), vp]
@@ -331,6 +336,16 @@ def roi_plan(W, H, n_frames, x, y, rw, rh):
     rc = lib().dbde_hip_roi_plan(W, H, n_frames, x, y, rw, rh, C.byref(pl))
     if rc != OK:
         raise ValueError(f"dbde_hip_roi_plan({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}) -> {rc}")
+    return pl.as_dict()
+
+
+def roi16_plan(W, H, n_frames, x, y, rw, rh):
+    """dbde16_hip_roi_plan: roi_plan for DBDE16 windows (dbde16_hip_decode_roi).
+    Raises ValueError where dbde16_hip_decode_roi would return DBDE_HIP_ERR_ARG."""
+    pl = RoiPlan()
+    rc = lib().dbde16_hip_roi_plan(W, H, n_frames, x, y, rw, rh, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"dbde16_hip_roi_plan({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}) -> {rc}")
     return pl.as_dict()
 
 
@@ -569,6 +584,21 @@ class Codec:
                                              W, H, n, images.data_ptr(), results.data_ptr())
         self._check(rc, "dbde16_hip_decode_frames")
         return images, results
+
+    def decode_roi16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, origins=None, out=None,
+                     results=None):
+        """DBDE16 window decode: the rw x rh window at (x, y) of n frames (frame f at
+        stream.data_ptr()+stream_offset+offsets[f]); origins as in decode_roi.  Returns (windows int16 (n, rh, rw)
+        holding the U16 bits, as decode_frames16 does; results (n, 4) int64)."""
+        if out is None:
+            out = torch.empty((n, rh, rw), dtype=torch.int16, device=self.device)
+        if results is None:
+            results = torch.empty((n, 4), dtype=torch.int64, device=self.device)
+        rc = self.L.dbde16_hip_decode_roi(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                          W, H, n, x, y, rw, rh, origins.data_ptr() if origins is not None else None,
+                                          out.data_ptr(), results.data_ptr())
+        self._check(rc, "dbde16_hip_decode_roi")
+        return out, results
 
     # ---- host-pointer API: the reference's functions -------------------------------------
     def pack_frame(self, index, image, W, H):

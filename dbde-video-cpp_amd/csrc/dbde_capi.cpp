@@ -803,8 +803,10 @@ struct RoiPlan {
     uint32_t split, threads, pieces, pieces_fixed;
     uint64_t grid, grid_origins;
 };
-// nullptr when the arguments are good, else what is wrong with them.
-static const char *plan_roi(int W, int H, int n_frames, int x0, int y0, int rw, int rh, RoiPlan &pl) {
+// nullptr when the arguments are good, else what is wrong with them.  wide: tiles per workgroup of windows more than 64
+// tiles across (kRoiWideThreads for DBDE, kRoi16WideThreads for DBDE16).
+static const char *plan_roi(int W, int H, int n_frames, int x0, int y0, int rw, int rh, RoiPlan &pl,
+                            uint32_t wide = kRoiWideThreads) {
     if (n_frames < 0) return "n_frames < 0";
     if (!geometry(W, H, pl.g)) return "bad frame size";
     if (rw < 1 || rh < 1 || rw > W || rh > H) return "window size outside [1, W] x [1, H]";
@@ -820,7 +822,7 @@ static const char *plan_roi(int W, int H, int n_frames, int x0, int y0, int rw, 
     pl.max_tx = (mx + (uint32_t)rw + 7u) / 8u;
     pl.max_ty = (my + (uint32_t)rh + 7u) / 8u;
     pl.split = index_split_for(n_frames, pl.dg.cpf);
-    pl.threads = pl.max_tx <= kRoiNarrowThreads ? kRoiNarrowThreads : kRoiWideThreads;
+    pl.threads = pl.max_tx <= kRoiNarrowThreads ? kRoiNarrowThreads : wide;
     pl.pieces = (pl.max_tx + pl.threads - 1u) / pl.threads;
     pl.pieces_fixed = (pl.ntx + pl.threads - 1u) / pl.threads;
     pl.grid = (uint64_t)n_frames * pl.nty * pl.pieces_fixed;
@@ -830,9 +832,7 @@ static const char *plan_roi(int W, int H, int n_frames, int x0, int y0, int rw, 
     return nullptr;
 }
 
-int dbde_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_roi_plan_t *plan) {
-    RoiPlan pl;
-    if (!plan || plan_roi(W, H, n_frames, x0, y0, rw, rh, pl)) return DBDE_HIP_ERR_ARG;
+static void report_roi_plan(const RoiPlan &pl, dbde_hip_roi_plan_t *plan) {
     memset(plan, 0, sizeof *plan);
     plan->tile_x = (int32_t)pl.tx0;
     plan->tile_y = (int32_t)pl.ty0;
@@ -848,19 +848,34 @@ int dbde_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh
     plan->pieces_x = pl.pieces;
     plan->grid = pl.grid;
     plan->grid_origins = pl.grid_origins;
+}
+
+int dbde_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_roi_plan_t *plan) {
+    RoiPlan pl;
+    if (!plan || plan_roi(W, H, n_frames, x0, y0, rw, rh, pl)) return DBDE_HIP_ERR_ARG;
+    report_roi_plan(pl, plan);
     return DBDE_HIP_OK;
 }
 
-int dbde_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
-                        int W, int H, int n_frames, int x0, int y0, int rw, int rh, const int32_t *d_origins,
-                        uint8_t *d_out, dbde_hip_frame_result *d_results) {
+int dbde16_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_roi_plan_t *plan) {
+    RoiPlan pl;
+    if (!plan || plan_roi(W, H, n_frames, x0, y0, rw, rh, pl, kRoi16WideThreads)) return DBDE_HIP_ERR_ARG;
+    report_roi_plan(pl, plan);
+    return DBDE_HIP_OK;
+}
+
+// Both window decoders: the index (min_bytes: 1 = DBDE, 2 = DBDE16) in timing slot 1, the window kernel in slot 2.
+static int decode_roi_common(dbde_hip_ctx *ctx, const char *name, uint32_t min_bytes, const uint8_t *d_stream,
+                             size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
+                             int y0, int rw, int rh, const int32_t *d_origins, void *d_out,
+                             dbde_hip_frame_result *d_results) {
     if (!ctx) return DBDE_HIP_ERR_ARG;
     RoiPlan pl;
-    const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl);
+    const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl, min_bytes == 2u ? kRoi16WideThreads : kRoiWideThreads);
     if (why)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "decode_roi: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", why, W, H, n_frames,
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", name, why, W, H, n_frames,
                     rw, rh, x0, y0);
-    if (!d_stream || !d_frame_offsets || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "decode_roi: null pointer");
+    if (!d_stream || !d_frame_offsets || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
     if (n_frames == 0) return DBDE_HIP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint32_t cpf = pl.dg.cpf;
@@ -878,7 +893,7 @@ int dbde_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t strea
     ip.results = d_results;
     ip.T = pl.g.T;
     ip.chunks_per_frame = cpf;
-    ip.min_bytes = 1;
+    ip.min_bytes = min_bytes;
     ip.geom = pl.dg;
     ip.split = 1;
     ip.frame_ctr = nullptr;
@@ -904,7 +919,7 @@ int dbde_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t strea
     p.chunk_off = ctx->chunk_off;
     p.frame_ok = ctx->frame_ok;
     p.origins = d_origins;
-    p.out = d_out;
+    p.out = static_cast<uint8_t *>(d_out);
     p.W = W;
     p.H = H;
     p.x0 = x0;
@@ -918,9 +933,24 @@ int dbde_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t strea
     p.rows = d_origins ? pl.max_ty : pl.nty;
     p.pieces = d_origins ? pl.pieces : pl.pieces_fixed;
     span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_decode_roi(p, (uint32_t)n_frames, pl.threads, ctx->stream));
+    HIP_TRY(ctx, min_bytes == 2u ? launch_decode_roi16(p, (uint32_t)n_frames, pl.threads, ctx->stream)
+                                 : launch_decode_roi(p, (uint32_t)n_frames, pl.threads, ctx->stream));
     span_end(ctx);
     return DBDE_HIP_OK;
+}
+
+int dbde_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+                        int W, int H, int n_frames, int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                        uint8_t *d_out, dbde_hip_frame_result *d_results) {
+    return decode_roi_common(ctx, "decode_roi", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
+                             rh, d_origins, d_out, d_results);
+}
+
+int dbde16_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                          const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                          const int32_t *d_origins, uint16_t *d_out, dbde_hip_frame_result *d_results) {
+    return decode_roi_common(ctx, "decode_roi16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0,
+                             rw, rh, d_origins, d_out, d_results);
 }
 
 int dbde_hip_index_stream_async(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, int W, int H,

@@ -271,6 +271,18 @@ int dbde16_hip_encode_frames(dbde_hip_ctx *ctx, const uint16_t *d_images, int W,
 int dbde16_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
                              const uint64_t *d_frame_offsets, int W, int H, int n_frames,
                              uint16_t *d_images, dbde_hip_frame_result *d_results);
+/* Window (region-of-interest) decode of DBDE16 frames: dbde_hip_decode_roi's contract with U16 pixels.
+ * Frame f's window goes to d_out + f*rw*rh pixels, row-major, pitch rw pixels; d_out may be any 2-byte aligned address.
+ * Validation is dbde16_hip_decode_frames' own (the same index kernel, U16 minima): a rejected frame reports the same
+ * result entry and leaves its window untouched.  d_origins (optional) as in dbde_hip_decode_roi, clamped into the
+ * frame; NULL -> (x0, y0) for every frame.  No byte at or beyond stream_bytes is read; nothing outside the
+ * n_frames*rw*rh output pixels is written.  n_frames == 0 does nothing.  A window size or origin outside the frame, a
+ * null pointer, or a frame of more than 32768 index chunks is DBDE_HIP_ERR_ARG before anything is launched.
+ * Asynchronous on the context's stream; timing hook: the index kernel in slot 1, the window kernel in slot 2. */
+int dbde16_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                          const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                          int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                          uint16_t *d_out, dbde_hip_frame_result *d_results);
 
 /* ---- multi-GPU: variable-length gather of the compressed stream to a root (RCCL over xGMI) ------------------- */
 /* Frames are independent, so the path shards by contiguous frame blocks (rank g of G owns frames
@@ -450,6 +462,9 @@ typedef struct dbde_hip_roi_plan_t {
     uint64_t grid_origins;            /* ... with per-frame origins (the most any origin needs) */
 } dbde_hip_roi_plan_t;
 int dbde_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_roi_plan_t *plan);
+/* The same for dbde16_hip_decode_roi: its arguments, its index geometry and the 16-bit window kernel's launch (windows
+ * more than 64 tiles across take 128 tiles per workgroup there, not 256: a U16 tile needs twice the LDS). */
+int dbde16_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_roi_plan_t *plan);
 
 /* ---- kernel timing hook for bench.py ---------------------------------------------------- */
 /* When enabled, every encode / decode call brackets its kernels with HIP events on the

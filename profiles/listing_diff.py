@@ -17,7 +17,7 @@ with tempfile.TemporaryDirectory() as tmp:
     subprocess.run(["make", "-s", "-C", f"{tmp}/dbde-video-cpp_amd/csrc", "asm"], check=True, capture_output=True)
     subprocess.run(["make", "-s", "-C", f"{ROOT}/dbde-video-cpp_amd/csrc", "asm"], check=True, capture_output=True)
     bad = 0
-    for f in ("dbde_kernels.s", "dbde16_kernels.s"):
+    for f in ("dbde_kernels.s", "dbde16_kernels.s", "dbde_roi_kernels.s"):
         old, new = bodies(f"{tmp}/dbde-video-cpp_amd/csrc/{f}"), bodies(f"{ROOT}/dbde-video-cpp_amd/csrc/{f}")
         for k, v in old.items():
             cands = [k, k.replace("EEEvNS_9EncParamsE", "ELi1EEEvNS_9EncParamsE"), k.replace("EEEvNS_9DecParamsE", "ELi256EEEvNS_9DecParamsE")]
