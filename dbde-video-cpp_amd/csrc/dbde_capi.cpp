@@ -1423,6 +1423,19 @@ size_t dbde_hip_pack_video_header(const dbde_hip_video_header *vh, uint8_t *targ
     return 28;
 }
 
+// The reference's `(uint64_t)el` (dbde_util.cpp:334) as g++ compiles it for x86-64, the host twin of the device
+// f64_to_u64_x86: cvttsd2si below 2^63, else cvttsd2si(v - 2^63) ^ 2^63; out of range and NaN give the "integer
+// indefinite" 2^63, so 2^64 and above (+inf included) read as 0.  A plain cast here does not do that: how a compiler
+// converts an out-of-range double is its own choice (clang's branch-free form gives 2^63 from 2^64 on).
+static uint64_t f64_to_u64_x86_host(double v) {
+    const double two63 = 9223372036854775808.0;
+    const bool high = v >= two63;       // false for NaN
+    const double a = high ? v - two63 : v;
+    uint64_t r = 0x8000000000000000ull;
+    if (a >= -two63 && a < two63) r = (uint64_t)(long long)a;   // truncates toward zero
+    return high ? (r ^ 0x8000000000000000ull) : r;
+}
+
 dbde_hip_frame_header dbde_hip_unpack_frame_header(uint8_t **packed) {
     dbde_hip_frame_header fh;
     const uint8_t *p = *packed;
@@ -1431,7 +1444,7 @@ dbde_hip_frame_header dbde_hip_unpack_frame_header(uint8_t **packed) {
     const uint64_t bits = get64(p + 12);
     double el;
     memcpy(&el, &bits, 8);
-    fh.elapsed_ns = (uint64_t)el;
+    fh.elapsed_ns = f64_to_u64_x86_host(el);
     if (fh.u64s != 2) fh.u64s = 0xFFFFFFFFu;
     *packed += 20;
     return fh;
