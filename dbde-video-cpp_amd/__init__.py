@@ -56,6 +56,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_scatter_plan", "dbde_hip_create_on_own_stream", "dbde_hip_set_host_staging",
     "dbde_hip_decode_roi", "dbde_hip_unpack_image_roi", "dbde_hip_roi_plan",
     "dbde16_hip_decode_roi", "dbde16_hip_roi_plan",
+    "dbde_hip_project", "dbde_hip_project_plan",
 ]
 
 
@@ -170,6 +171,10 @@ def lib():
     L.dbde16_hip_decode_roi.restype = i
     L.dbde16_hip_roi_plan.argtypes = [i, i, i, i, i, i, i, C.POINTER(RoiPlan)]
     L.dbde16_hip_roi_plan.restype = i
+    L.dbde_hip_project.argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
+    L.dbde_hip_project.restype = i
+    L.dbde_hip_project_plan.argtypes = [i, i, i, i, i, i, i, C.c_uint, i, C.POINTER(ProjectPlan)]
+    L.dbde_hip_project_plan.restype = i
     L.dbde_hip_unpack_frame.argtypes = [vp, C.POINTER(vp), i, i, vp]
     L.dbde_hip_pack_frame_header.restype = sz
     L.dbde_hip_pack_frame_header.argtypes = [C.POINTER(FrameHeader), vp]
@@ -431,6 +436,75 @@ def unpack_video_header(packed):
     return cur.value - buf.ctypes.data, (vh.u64s, vh.height, vh.width, vh.frame_hz)
 
 
+STATS = {"max": 1, "min": 2, "sum": 4, "sumsq": 8}
+
+
+def stats_mask(stats):
+    """("max", "min", "sum", "sumsq") names (or an int bitmask) -> dbde_hip_project_plan's bitmask."""
+    if isinstance(stats, int):
+        return stats
+    if isinstance(stats, str):
+        stats = (stats,)
+    mask = 0
+    for name in stats:
+        if name not in STATS:
+            raise ValueError(f"unknown statistic {name!r} (one of {sorted(STATS)})")
+        mask |= STATS[name]
+    return mask
+
+
+class ProjectPlan(C.Structure):
+    """dbde_hip_project_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32),
+                ("index_split", C.c_uint32), ("threads", C.c_uint32), ("pieces_x", C.c_uint32),
+                ("segments", C.c_uint32), ("frames_per_segment", C.c_uint32), ("max_frames_per_segment", C.c_uint32),
+                ("reserved_", C.c_uint32), ("grid", C.c_uint64), ("combine_grid", C.c_uint64),
+                ("workspace_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved_"}
+
+
+def project_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, stats=("max", "min", "sum", "sumsq"), n_cu=256):
+    """dbde_hip_project_plan: the tile window, index geometry, launch and workspace of a projection (host arithmetic
+    only).  rw / rh default to the rest of the frame.  Raises ValueError where dbde_hip_project would return
+    DBDE_HIP_ERR_ARG."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    pl = ProjectPlan()
+    rc = lib().dbde_hip_project_plan(W, H, n_frames, x, y, rw, rh, stats_mask(stats), n_cu, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"dbde_hip_project_plan({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, {stats}) -> {rc}")
+    return pl.as_dict()
+
+
+class Projection:
+    """Device tensors of a temporal projection (Codec.project): max / min uint8 (rh, rw), sum / sumsq int64 (rh, rw)
+    (the values stay below 2^63), count int64 (1,).  A statistic that was not asked for is None."""
+
+    def __init__(self, max=None, min=None, sum=None, sumsq=None, count=None):
+        self.max, self.min, self.sum, self.sumsq, self.count = max, min, sum, sumsq, count
+
+    @classmethod
+    def empty(cls, rh, rw, stats, device):
+        mask = stats_mask(stats)
+        u8 = lambda: torch.empty((rh, rw), dtype=torch.uint8, device=device)    # noqa: E731
+        i64 = lambda: torch.empty((rh, rw), dtype=torch.int64, device=device)   # noqa: E731
+        return cls(u8() if mask & 1 else None, u8() if mask & 2 else None, i64() if mask & 4 else None,
+                   i64() if mask & 8 else None, torch.zeros(1, dtype=torch.int64, device=device))
+
+    def mean(self):
+        """Per-pixel mean (float64, on the device); NaN where no frame contributed."""
+        return self.sum.to(torch.float64) / self.count.to(torch.float64)
+
+    def std(self):
+        """Per-pixel population standard deviation (float64, on the device); NaN where no frame contributed."""
+        n = self.count.to(torch.float64)
+        m = self.sum.to(torch.float64) / n
+        return (self.sumsq.to(torch.float64) / n - m * m).clamp_(min=0.0).sqrt_()
+
+
 class DbdeError(RuntimeError):
     pass
 
@@ -530,6 +604,27 @@ class Codec:
                                         W, H, n, x, y, rw, rh, origins.data_ptr() if origins is not None else None,
                                         out.data_ptr(), results.data_ptr())
         self._check(rc, "dbde_hip_decode_roi")
+        return out, results
+
+    def project(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x=0, y=0, rw=None, rh=None,
+                stats=("max", "min", "sum", "sumsq"), out=None, accumulate=False, results=None):
+        """Temporal projection of the rw x rh window at (x, y) over n frames (frame f at
+        stream.data_ptr()+stream_offset+offsets[f]): per-pixel max, min, sum and sum of squares of the accepted frames.
+        rw / rh default to the rest of the frame.  out: a Projection to write into (accumulate=True continues it);
+        its statistics are the ones computed.  Returns (Projection, results (n, 4) int64) like decode_frames."""
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out= (the projection to continue)")
+            out = Projection.empty(rh, rw, stats, self.device)
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        rc = self.L.dbde_hip_project(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                     W, H, n, x, y, rw, rh, 1 if accumulate else 0, ptr(out.max), ptr(out.min),
+                                     ptr(out.sum), ptr(out.sumsq), ptr(out.count), ptr(results) if n > 0 else None)
+        self._check(rc, "dbde_hip_project")
         return out, results
 
     def index_stream(self, stream, stream_offset, stream_bytes, W, H, max_frames):

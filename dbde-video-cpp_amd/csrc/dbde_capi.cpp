@@ -16,6 +16,7 @@
 
 #include "dbde16_kernels.h"
 #include "dbde_kernels.h"
+#include "dbde_project_kernels.h"
 #include "dbde_roi_kernels.h"
 
 using namespace dbde;
@@ -66,6 +67,8 @@ struct dbde_hip_ctx {
     uint32_t *idx_ctr = nullptr;     // [2 * n]: arrival counters, then flags, of the split index kernel (kept zero)
     size_t idx_ctr_n = 0;
     unsigned long long *fuse_rec = nullptr;   // records of the fused index + decode launch (epoch-tagged, never cleared)
+    uint8_t *proj_ws = nullptr;      // per-segment partials of dbde_hip_project
+    size_t proj_ws_bytes = 0;
     size_t fuse_rec_n = 0;
     uint32_t fuse_epoch = 0;
     // sticky failure word (device) + scratch
@@ -286,6 +289,7 @@ void dbde_hip_destroy(dbde_hip_ctx *ctx) {
     if (ctx->frame_ok) (void)hipFree(ctx->frame_ok);
     if (ctx->idx_ctr) (void)hipFree(ctx->idx_ctr);
     if (ctx->fuse_rec) (void)hipFree(ctx->fuse_rec);
+    if (ctx->proj_ws) (void)hipFree(ctx->proj_ws);
     if (ctx->sticky) (void)hipFree(ctx->sticky);
     if (ctx->st_img) (void)hipFree(ctx->st_img);
     if (ctx->st_pack) (void)hipFree(ctx->st_pack);
@@ -864,20 +868,12 @@ int dbde16_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int 
     return DBDE_HIP_OK;
 }
 
-// Both window decoders: the index (min_bytes: 1 = DBDE, 2 = DBDE16) in timing slot 1, the window kernel in slot 2.
-static int decode_roi_common(dbde_hip_ctx *ctx, const char *name, uint32_t min_bytes, const uint8_t *d_stream,
-                             size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
-                             int y0, int rw, int rh, const int32_t *d_origins, void *d_out,
-                             dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    RoiPlan pl;
-    const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl, min_bytes == 2u ? kRoi16WideThreads : kRoiWideThreads);
-    if (why)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", name, why, W, H, n_frames,
-                    rw, rh, x0, y0);
-    if (!d_stream || !d_frame_offsets || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (n_frames == 0) return DBDE_HIP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+// The decode index kernel with the window decoder's chunk geometry (pl.dg, roi_index_geometry) and index split, in
+// timing slot 1: validation, results and per-chunk payload offsets (ctx->chunk_off, ctx->frame_ok) of n_frames > 0
+// frames, exactly as dbde_hip_decode_frames validates them.  Shared by the window decoders and dbde_hip_project.
+static int roi_index(dbde_hip_ctx *ctx, const RoiPlan &pl, uint32_t min_bytes, const uint8_t *d_stream,
+                     size_t stream_bytes, const uint64_t *d_frame_offsets, int n_frames,
+                     dbde_hip_frame_result *d_results) {
     const uint32_t cpf = pl.dg.cpf;
     int rc = grow(ctx, ctx->chunk_off, ctx->chunk_off_n, (size_t)n_frames * (cpf + 1u), sizeof(uint32_t));
     if (rc) return rc;
@@ -911,6 +907,25 @@ static int decode_roi_common(dbde_hip_ctx *ctx, const char *name, uint32_t min_b
     span_begin(ctx, 1);
     HIP_TRY(ctx, launch_decode_index(ip, n_frames, ctx->stream));
     span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+// Both window decoders: the index (min_bytes: 1 = DBDE, 2 = DBDE16) in timing slot 1, the window kernel in slot 2.
+static int decode_roi_common(dbde_hip_ctx *ctx, const char *name, uint32_t min_bytes, const uint8_t *d_stream,
+                             size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
+                             int y0, int rw, int rh, const int32_t *d_origins, void *d_out,
+                             dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    RoiPlan pl;
+    const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl, min_bytes == 2u ? kRoi16WideThreads : kRoiWideThreads);
+    if (why)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", name, why, W, H, n_frames,
+                    rw, rh, x0, y0);
+    if (!d_stream || !d_frame_offsets || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if (n_frames == 0) return DBDE_HIP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = roi_index(ctx, pl, min_bytes, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results);
+    if (rc) return rc;
 
     RoiParams p;
     p.stream = d_stream;
@@ -951,6 +966,134 @@ int dbde16_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t str
                           const int32_t *d_origins, uint16_t *d_out, dbde_hip_frame_result *d_results) {
     return decode_roi_common(ctx, "decode_roi16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0,
                              rw, rh, d_origins, d_out, d_results);
+}
+
+// ---- temporal projections ---------------------------------------------------------------------------------
+struct ProjectPlan {
+    RoiPlan roi;                      // arguments, tile window and index geometry: the window decoder's (plan_roi)
+    uint32_t stats;
+    uint32_t pieces, rows, segments, fps;
+    uint64_t grid, combine_grid, workspace;
+};
+// Frames per segment: a segment is cut only to fill the device (about 4 workgroups per CU) and never below
+// kProjMinFramesPerSegment frames, whose partials would cost more traffic than they save; never above the U32 bound.
+static constexpr uint32_t kProjMinFramesPerSegment = 32;
+static const char *plan_project(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
+                                ProjectPlan &pl) {
+    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi)) return why;
+    if (stats < 1u || stats > kProjAll) return "no statistic (or an unknown one) requested";
+    pl.stats = stats;
+    pl.pieces = (pl.roi.ntx + kProjTiles - 1u) / kProjTiles;
+    pl.rows = pl.roi.nty;
+    const uint64_t base = (uint64_t)pl.pieces * pl.rows, n = (uint64_t)n_frames;
+    const uint64_t target = 4ull * (uint64_t)(n_cu > 0 ? n_cu : 1);
+    uint64_t seg = base >= target ? 1u : (target + base - 1u) / base;
+    const uint64_t by_len = (n + kProjMinFramesPerSegment - 1u) / kProjMinFramesPerSegment;
+    if (seg > by_len) seg = by_len;
+    const uint64_t by_bound = (n + kProjMaxFramesPerSegment - 1u) / kProjMaxFramesPerSegment;
+    if (seg < by_bound) seg = by_bound;
+    if (seg < 1u) seg = 1u;
+    uint64_t fps = (n + seg - 1u) / seg;
+    if (fps > 0u) seg = (n + fps - 1u) / fps;   // no empty segment
+    if (seg >= (1ull << 31)) return "too many workgroups in one call";
+    pl.segments = (uint32_t)seg;
+    pl.fps = (uint32_t)fps;
+    pl.grid = base * seg;
+    if (pl.grid >= (1ull << 31)) return "too many workgroups in one call";
+    const uint64_t pixels = (uint64_t)rw * (uint64_t)rh;
+    pl.combine_grid = seg > 1u ? (pixels + kProjCombineThreads - 1u) / kProjCombineThreads : 0u;
+    if (pl.combine_grid >= (1ull << 31)) return "too many workgroups in one call";
+    pl.workspace = project_workspace_bytes(stats, pl.segments, pixels);
+    return nullptr;
+}
+
+int dbde_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
+                          dbde_hip_project_plan_t *plan) {
+    ProjectPlan pl;
+    if (!plan || plan_project(W, H, n_frames, x0, y0, rw, rh, stats, n_cu, pl)) return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->tile_x = (int32_t)pl.roi.tx0;
+    plan->tile_y = (int32_t)pl.roi.ty0;
+    plan->tiles_x = (int32_t)pl.roi.ntx;
+    plan->tiles_y = (int32_t)pl.roi.nty;
+    plan->chunks_per_frame = pl.roi.dg.cpf;
+    plan->chunk_tiles = pl.roi.dg.ct;
+    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
+    plan->index_split = pl.roi.split;
+    plan->threads = kProjThreads;
+    plan->pieces_x = pl.pieces;
+    plan->segments = pl.segments;
+    plan->frames_per_segment = pl.fps;
+    plan->max_frames_per_segment = kProjMaxFramesPerSegment;
+    plan->grid = pl.grid;
+    plan->combine_grid = pl.combine_grid;
+    plan->workspace_bytes = pl.workspace;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+                     int W, int H, int n_frames, int x0, int y0, int rw, int rh, int accumulate, uint8_t *d_max,
+                     uint8_t *d_min, uint64_t *d_sum, uint64_t *d_sumsq, uint64_t *d_count,
+                     dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    const unsigned stats = (d_max ? kProjMax : 0u) | (d_min ? kProjMin : 0u) | (d_sum ? kProjSum : 0u) |
+                           (d_sumsq ? kProjSumSq : 0u);
+    ProjectPlan pl;
+    if (const char *why = plan_project(W, H, n_frames, x0, y0, rw, rh, stats, ctx->n_cu, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "project: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", why, W, H, n_frames,
+                    rw, rh, x0, y0);
+    if (!d_stream || !d_frame_offsets || !d_count) return fail(ctx, DBDE_HIP_ERR_ARG, "project: null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_sum) | reinterpret_cast<uintptr_t>(d_sumsq) |
+         reinterpret_cast<uintptr_t>(d_count)) & 7u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "project: U64 outputs must be 8-byte aligned");
+    if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n_frames > 0) {
+        int rc = roi_index(ctx, pl.roi, 1u, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results);
+        if (rc) return rc;
+    }
+    ProjParams p;
+    memset(&p, 0, sizeof p);
+    if (pl.workspace) {
+        int rc = grow(ctx, ctx->proj_ws, ctx->proj_ws_bytes, (size_t)pl.workspace, 1);
+        if (rc) return rc;
+        const uint64_t n = (uint64_t)pl.segments * (uint64_t)rw * (uint64_t)rh;
+        const uint64_t u8 = (n + 15u) & ~(uint64_t)15, u32 = (4u * n + 15u) & ~(uint64_t)15;
+        uint8_t *w = ctx->proj_ws;
+        if (d_max) { p.ws_max = w; w += u8; }
+        if (d_min) { p.ws_min = w; w += u8; }
+        if (d_sum) { p.ws_sum = reinterpret_cast<uint32_t *>(w); w += u32; }
+        if (d_sumsq) { p.ws_sumsq = reinterpret_cast<uint32_t *>(w); w += u32; }
+    }
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.n_frames = (uint32_t)n_frames;
+    p.x0 = x0;
+    p.y0 = y0;
+    p.rw = rw;
+    p.rh = rh;
+    p.T = pl.roi.g.T;
+    p.w = pl.roi.g.w;
+    p.geom = pl.roi.dg;
+    p.tx0 = pl.roi.tx0;
+    p.ty0 = pl.roi.ty0;
+    p.rows = pl.rows;
+    p.pieces = pl.pieces;
+    p.segments = pl.segments;
+    p.fps = pl.fps;
+    p.accumulate = accumulate ? 1 : 0;
+    p.out_max = d_max;
+    p.out_min = d_min;
+    p.out_sum = d_sum;
+    p.out_sumsq = d_sumsq;
+    p.out_count = d_count;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_project(p, stats, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
 }
 
 int dbde_hip_index_stream_async(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, int W, int H,

@@ -1,0 +1,55 @@
+// dbde_project_kernels.h -- launch interface of the temporal projections (dbde_hip_project), dbde_project_kernels.hip.
+//
+// A projection reduces the rw x rh window of a batch of frames pixel by pixel over the frames: maximum, minimum, sum
+// and sum of squares.  Validation and the per-chunk payload offsets come from the decode index kernel
+// (dbde_kernels.hip) run with the window decoder's chunk geometry (roi_index_geometry), exactly as dbde_hip_decode_roi
+// runs it; the projection kernel reads the window's tiles and accumulates them in registers, writing no image.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dbde_kernels.h"
+
+namespace dbde {
+
+// Statistics bitmask (dbde_hip_project_plan's `stats`).
+constexpr uint32_t kProjMax = 1u, kProjMin = 2u, kProjSum = 4u, kProjSumSq = 8u, kProjAll = 15u;
+
+// One lane per tile row: a workgroup takes kProjTiles consecutive tiles of one window tile row, 8 lanes per tile.
+constexpr uint32_t kProjThreads = 256;
+constexpr uint32_t kProjTiles = kProjThreads / 8u;
+// Frames one workgroup reduces into its U32 per-lane sums: 65,536 * 255^2 < 2^32, so the sums of squares are exact.
+constexpr uint32_t kProjMaxFramesPerSegment = 65536;
+// Threads per workgroup of the combine kernel (one window pixel per thread).
+constexpr uint32_t kProjCombineThreads = 256;
+
+struct ProjParams {
+    const uint8_t *stream;
+    const uint64_t *frame_offsets;  // [n_frames]
+    uint64_t stream_bytes;          // readable extent of stream
+    const uint32_t *chunk_off;      // [n_frames][cpf + 1] from launch_decode_index
+    const uint32_t *frame_ok;       // [n_frames]
+    uint32_t n_frames;
+    int x0, y0, rw, rh;
+    uint32_t T;
+    uint32_t w;                     // tiles across the frame
+    DecGeom geom;                   // the index's chunk geometry (roi_index_geometry)
+    uint32_t tx0, ty0;              // the window's first tile column / row
+    uint32_t rows, pieces;          // window tile rows; workgroups (of kProjTiles tiles) across one
+    uint32_t segments, fps;         // frame segments; frames per segment (the last may hold fewer)
+    int accumulate;                 // 1: combine into what the outputs hold
+    // outputs (segments == 1: written by the projection kernel; otherwise by the combine kernel); NULL = not computed
+    uint8_t *out_max, *out_min;
+    uint64_t *out_sum, *out_sumsq, *out_count;
+    // per-segment partials [segments][rh * rw] (segments > 1 only), present for the requested statistics
+    uint8_t *ws_max, *ws_min;
+    uint32_t *ws_sum, *ws_sumsq;
+};
+
+// The projection kernel (one instance per statistics set, `stats` = kProj* mask, 1..15): grid = pieces * rows *
+// segments workgroups of kProjThreads; with segments > 1 the combine kernel follows on the same stream.
+hipError_t launch_project(const ProjParams &p, uint32_t stats, hipStream_t s);
+// Bytes of the per-segment partials of a window of `pixels` pixels (0 for one segment).
+uint64_t project_workspace_bytes(uint32_t stats, uint32_t segments, uint64_t pixels);
+
+}  // namespace dbde

@@ -142,6 +142,35 @@ int dbde_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t strea
                         int x0, int y0, int rw, int rh, const int32_t *d_origins,
                         uint8_t *d_out, dbde_hip_frame_result *d_results);
 
+/* Temporal projection: the per-pixel maximum, minimum, sum and sum of squares over n_frames frames of
+ * the rw x rh window at (x0, y0), reduced straight from the compressed bytes (no image is written).
+ * Inputs and outputs:
+ *   Frame f starts at d_stream + d_frame_offsets[f] (any byte alignment; concatenated and slot layouts alike).  No byte
+ *   at or beyond stream_bytes is read.  The window and its argument rules are dbde_hip_decode_roi's (plan_roi); there
+ *   are no per-frame origins.  The whole frame is 0, 0, W, H.
+ *   Each output is rh x rw, row-major, pitch rw: d_max and d_min U8 at any byte alignment, d_sum and d_sumsq U64,
+ *   8-byte aligned.  A NULL output is not computed and its buffer is never touched; at least one of the four must be
+ *   non-NULL.  d_count (one U64, required) receives the number of frames that contributed.  d_results (optional) is
+ *   filled exactly as dbde_hip_decode_frames fills it: same validation, same entries.
+ * What is reduced: only frames dbde_hip_decode_frames accepts; a rejected frame reports its usual result entry and
+ *   adds nothing.  The pixels reduced are exactly the bytes dbde_hip_decode_frames would write (minima that wrap modulo
+ *   256 included).
+ * accumulate = 0: the outputs and *d_count are overwritten with this call's projection, also for n_frames == 0 or when
+ *   every frame is rejected (the empty projection: max 0, min 255, sums 0, count 0).  accumulate = 1: this call's
+ *   projection is combined into what the buffers hold (max of maxima, min of minima, sums and count added;
+ *   n_frames == 0 changes nothing).  Frames [0, n) in one call give the same result as any split into consecutive
+ *   calls with accumulate = 1 after the first: every result is an exact integer.
+ * Overflow: the U64 sums are exact for any count a user can reach; inside the kernel a workgroup sums at most 65,536
+ *   frames in U32 (65,536 * 255^2 < 2^32), a bound the plan enforces.
+ * Errors: DBDE_HIP_ERR_ARG as dbde_hip_decode_roi, and for no statistic, a NULL d_count or an unaligned U64 output.
+ * Asynchronous on the context's stream; workspace as dbde_hip_decode_roi (the context's, grown on demand), plus the
+ * per-segment partials the plan reports.  Timing hook: the index kernel in slot 1, the projection kernels in slot 2. */
+int dbde_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                     const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                     int x0, int y0, int rw, int rh, int accumulate,
+                     uint8_t *d_max, uint8_t *d_min, uint64_t *d_sum, uint64_t *d_sumsq,
+                     uint64_t *d_count, dbde_hip_frame_result *d_results);
+
 /* Builds the frame index of a concatenated frame sequence starting at d_stream (no video
  * header): hops 20 + 12 + 2T + 8*n64 from frame to frame (README.md:12-23) until max_frames
  * or the end of stream_bytes.  Writes offsets (device, max_frames) and returns the number of
@@ -465,6 +494,31 @@ int dbde_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh
 /* The same for dbde16_hip_decode_roi: its arguments, its index geometry and the 16-bit window kernel's launch (windows
  * more than 64 tiles across take 128 tiles per workgroup there, not 256: a U16 tile needs twice the LDS). */
 int dbde16_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_roi_plan_t *plan);
+
+/* What dbde_hip_project runs (pure host arithmetic, like dbde_hip_roi_plan): validates exactly what dbde_hip_project
+ * validates (DBDE_HIP_ERR_ARG otherwise) and reports the tile window, the index geometry, the projection launch and its
+ * workspace.  stats: bitmask of the statistics, max 1, min 2, sum 4, sumsq 8 (dbde_hip_project: its non-NULL outputs).
+ * n_cu: compute units of the device (dbde_hip_project uses its context's). */
+enum { DBDE_HIP_PROJECT_MAX = 1, DBDE_HIP_PROJECT_MIN = 2, DBDE_HIP_PROJECT_SUM = 4, DBDE_HIP_PROJECT_SUMSQ = 8 };
+typedef struct dbde_hip_project_plan_t {
+    int32_t tile_x, tile_y;           /* first tile column / row of the window */
+    int32_t tiles_x, tiles_y;         /* tiles across / down the window covers */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t threads;                 /* projection kernel: workgroup size (8 lanes per tile: threads / 8 tiles) */
+    uint32_t pieces_x;                /* projection kernel: workgroups across a window tile row */
+    uint32_t segments;                /* frame segments, each reduced by its own workgroups */
+    uint32_t frames_per_segment;      /* frames of every segment but the last (which may hold fewer) */
+    uint32_t max_frames_per_segment;  /* the kernel's U32 bound on frames_per_segment */
+    uint32_t reserved_;
+    uint64_t grid;                    /* projection kernel: pieces_x * tiles_y * segments workgroups */
+    uint64_t combine_grid;            /* combine kernel: workgroups (0 = one segment, no combine) */
+    uint64_t workspace_bytes;         /* per-segment partials (0 for one segment) */
+} dbde_hip_project_plan_t;
+int dbde_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats,
+                          int n_cu, dbde_hip_project_plan_t *plan);
 
 /* ---- kernel timing hook for bench.py ---------------------------------------------------- */
 /* When enabled, every encode / decode call brackets its kernels with HIP events on the

@@ -1,0 +1,58 @@
+"""CPU, compile only: the gfx950 listing of the projection kernels (`make asm`, dbde_project_kernels.s; no GPU).
+
+dbde_hip_project launches one project_kernel instance per statistics set (every non-empty subset of max, min, sum and
+sumsq: 15) and the combine kernel.  Their resources are part of the design: no instance may use scratch
+or a dynamic stack, each keeps its LDS within 512 bytes (the offsets exchange and the frame count), and each keeps its
+VGPRs within 128, so that at least 4 waves per SIMD -- 4 workgroups of 256 threads per CU -- stay resident.
+"""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "dbde-video-cpp_amd", "csrc")
+
+LDS_BUDGET = 512      # bytes per workgroup
+VGPR_BUDGET = 128     # per lane: 4 waves per SIMD
+
+
+@pytest.fixture(scope="module")
+def kernels():
+    r = subprocess.run(["make", "-s", "-C", CSRC, "asm"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    meta = open(os.path.join(CSRC, "dbde_project_kernels.s")).read()
+    out = {}
+    for m in re.finditer(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", meta, re.S):
+        fields = dict(re.findall(r"\.amdhsa_(\w+) (\d+)", m.group(2)))
+        out[m.group(1)] = {k: int(v) for k, v in fields.items()}
+    return out
+
+
+def instances(kernels):
+    got = {}
+    for name, f in kernels.items():
+        m = re.match(r"_ZN4dbde14project_kernelILj(\d+)EEEvNS_10ProjParamsE$", name)
+        if m:
+            got[int(m.group(1))] = f
+    return got
+
+
+def test_one_instance_per_statistics_set(kernels):
+    assert sorted(instances(kernels)) == list(range(1, 16))
+    assert "_ZN4dbde22project_combine_kernelENS_10ProjParamsE" in kernels
+
+
+def test_no_scratch_and_within_budget(kernels):
+    for name, f in kernels.items():
+        assert f["private_segment_fixed_size"] == 0, (name, "scratch")
+        assert not f.get("uses_dynamic_stack", 0), name
+        assert f["group_segment_fixed_size"] <= LDS_BUDGET, (name, f["group_segment_fixed_size"])
+        assert f["next_free_vgpr"] <= VGPR_BUDGET, (name, f["next_free_vgpr"])
+
+
+def test_fewer_statistics_cost_fewer_registers(kernels):
+    """An unrequested statistic has no accumulators: max + min alone needs fewer VGPRs than all four."""
+    inst = instances(kernels)
+    assert inst[3]["next_free_vgpr"] < inst[15]["next_free_vgpr"]
