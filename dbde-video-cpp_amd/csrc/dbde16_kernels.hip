@@ -14,21 +14,19 @@
 // assembled / taken apart as two 4-pixel halves of 4*d <= 64 bits.
 #include "dbde16_kernels.h"
 
+#include "dbde_bits.h"
+#include "dbde_device.h"
+
 namespace dbde16 {
+
+using dbde::cut_row16;
+using dbde::pk_max_u16;
+using dbde::pk_min_u16;
+using dbde::wave_scan_incl;
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef u32x4_t __attribute__((aligned(1))) u32x4_unaligned;
 
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {   // DPP inclusive scan over the wave
-    uint32_t t = x;
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x111, 0xF, 0xF, false);
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x112, 0xF, 0xF, false);
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x114, 0xF, 0xF, false);
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x118, 0xF, 0xF, false);
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x142, 0xA, 0xF, false);
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x143, 0xC, 0xF, false);
-    return t;
-}
 __device__ __forceinline__ void store_u32_bytes(uint8_t *p, uint32_t v) { __builtin_memcpy(p, &v, 4); }
 __device__ __forceinline__ void store_u64_any(uint8_t *p, uint64_t v) { __builtin_memcpy(p, &v, 8); }
 
@@ -55,14 +53,6 @@ __device__ __forceinline__ void load_tile16(const uint16_t *img, int W, int H, u
     }
 }
 
-__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-}
-__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-}
 __device__ __forceinline__ void tile_minmax16(const uint32_t (&v)[32], uint32_t &mn, uint32_t &mx) {
     uint32_t lo = v[0], hi = v[0];
 #pragma unroll
@@ -452,10 +442,8 @@ __global__ __launch_bounds__(kChunkTiles16) void dec16_kernel(DecParams16 p) {
         }
         return;
     }
-    // Each window comes out of the three ALIGNED dwords that hold it (v_alignbyte, as in the 8-bit decoder: LDS reads
-    // of 8 bytes at odd addresses are what made mixed depths the slow content here); a pixel is v_alignbit at i*d
-    // (shift counts are taken modulo 32: from 32 on the window's high dword is shifted instead), two pixels per dword,
-    // the minimum added with v_pk_add_u16 (modulo 2^16, as the spec says).
+    // Each half comes out of the three ALIGNED dwords that hold it (dbde_device.h's cut_row16: LDS reads of 8 bytes at odd
+    // addresses are what made mixed depths the slow content here), all of a thread's rows read before the first is cut.
     uint32_t lw[8][3], hw[8][3];
 #pragma unroll
     for (int r = 0; r < 8; r++) {
@@ -466,26 +454,12 @@ __global__ __launch_bounds__(kChunkTiles16) void dec16_kernel(DecParams16 p) {
         hw[r][0] = qh[0]; hw[r][1] = qh[1]; hw[r][2] = qh[2];
     }
     DIAG_MARK(3);
-    const uint32_t m32 = (uint32_t)fmask, mn2 = mn * 0x00010001u, sh_odd = (d & 1u) * 4u;
-    const bool c2 = 2u * d >= 32u, c3 = 3u * d >= 32u;
-    auto four = [&](uint32_t x0, uint32_t x1, uint32_t &o0, uint32_t &o1) __attribute__((always_inline)) {
-        typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-        const uint32_t p0 = x0 & m32;
-        const uint32_t p1 = __builtin_amdgcn_alignbit(x1, x0, d) & m32;
-        const uint32_t p2 = __builtin_amdgcn_alignbit(c2 ? 0u : x1, c2 ? x1 : x0, 2u * d) & m32;
-        const uint32_t p3 = __builtin_amdgcn_alignbit(c3 ? 0u : x1, c3 ? x1 : x0, 3u * d) & m32;
-        o0 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, p0 | (p1 << 16)) + __builtin_bit_cast(u16x2, mn2));
-        o1 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, p2 | (p3 << 16)) + __builtin_bit_cast(u16x2, mn2));
-    };
+    const uint32_t m32 = (uint32_t)fmask, mn2 = mn * 0x00010001u;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const uint32_t a = byte0 + (uint32_t)r * d, ah = a + (d >> 1);
-        const uint32_t x0 = __builtin_amdgcn_alignbyte(lw[r][1], lw[r][0], a), x1 = __builtin_amdgcn_alignbyte(lw[r][2], lw[r][1], a);
-        const uint32_t w0 = __builtin_amdgcn_alignbyte(hw[r][1], hw[r][0], ah), w1 = __builtin_amdgcn_alignbyte(hw[r][2], hw[r][1], ah);
-        const uint32_t h0 = __builtin_amdgcn_alignbit(w1, w0, sh_odd), h1 = w1 >> sh_odd;
         uint32_t o0, o1, o2, o3;
-        four(x0, x1, o0, o1);
-        four(h0, h1, o2, o3);
+        cut_row16(lw[r], hw[r], a, ah, d, m32, mn2, o0, o1, o2, o3);
         const u32x4_t o = {o0, o1, o2, o3};
         const int yy = 8 * (int)ty + r;
         if (yy < p.H) {

@@ -680,6 +680,56 @@ static DecPlan plan_decode(const Geometry &g, int W, int n_frames, uintptr_t ib,
     return pl;
 }
 
+// Index split of the decode index kernel: few frames are cut into pieces so that the index pass fills the device too
+// (>= 4 chunks per piece, about 1024 workgroups in all); from 256 frames on, one workgroup per frame.
+static uint32_t index_split_for(int n_frames, uint32_t cpf) {
+    if (n_frames < 1 || n_frames >= 256 || cpf < 8u) return 1u;
+    uint32_t sp = 1024u / (uint32_t)n_frames;
+    const uint32_t most = (cpf + 3u) / 4u;
+    return sp > most ? most : (sp < 1u ? 1u : sp);
+}
+
+// The decode index kernel in timing slot 1: validation, results and per-chunk payload offsets (ctx->chunk_off,
+// ctx->frame_ok) of n_frames > 0 frames cut into the chunks of dg.  min_bytes: 1 = DBDE, 2 = DBDE16.  split: workgroups
+// per frame (1, or the split form's index_split_for).  Shared by every decoder that runs the index as a launch of its own.
+static int run_index(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+                     int n_frames, dbde_hip_frame_result *d_results, const DecGeom &dg, uint32_t min_bytes,
+                     uint32_t split) {
+    int rc = grow(ctx, ctx->chunk_off, ctx->chunk_off_n, (size_t)n_frames * (dg.cpf + 1u), sizeof(uint32_t));
+    if (rc) return rc;
+    rc = grow(ctx, ctx->frame_ok, ctx->frame_ok_n, (size_t)n_frames, sizeof(uint32_t));
+    if (rc) return rc;
+
+    IdxParams ip;
+    ip.stream = d_stream;
+    ip.frame_offsets = d_frame_offsets;
+    ip.stream_bytes = stream_bytes;
+    ip.chunk_off = ctx->chunk_off;
+    ip.frame_ok = ctx->frame_ok;
+    ip.results = d_results;
+    ip.T = dg.T;
+    ip.chunks_per_frame = dg.cpf;
+    ip.min_bytes = min_bytes;
+    ip.geom = dg;
+    ip.split = 1;
+    ip.frame_ctr = nullptr;
+    ip.frame_flag = nullptr;
+    if (split > 1u) {
+        const size_t before = ctx->idx_ctr_n;
+        rc = grow(ctx, ctx->idx_ctr, ctx->idx_ctr_n, 2 * (size_t)n_frames, sizeof(uint32_t));
+        if (rc) return rc;
+        if (ctx->idx_ctr_n != before)   // fresh block: the kernel keeps it zero from here on
+            HIP_TRY(ctx, hipMemsetAsync(ctx->idx_ctr, 0, ctx->idx_ctr_n * sizeof(uint32_t), ctx->stream));
+        ip.split = split;
+        ip.frame_ctr = ctx->idx_ctr;
+        ip.frame_flag = ctx->idx_ctr + n_frames;
+    }
+    span_begin(ctx, 1);
+    HIP_TRY(ctx, launch_decode_index(ip, n_frames, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
 int dbde_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
                            const uint64_t *d_frame_offsets, int W, int H, int n_frames, uint8_t *d_images,
                            dbde_hip_frame_result *d_results) {
@@ -720,45 +770,9 @@ int dbde_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t st
         ctx->fuse_epoch++;
     }
     if (!self_index && !fused) {
-        int rc = grow(ctx, ctx->chunk_off, ctx->chunk_off_n, (size_t)n_chunks64 + (size_t)n_frames, sizeof(uint32_t));
+        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, dg, 1u,
+                           index_split_for(n_frames, dcpf));
         if (rc) return rc;
-        rc = grow(ctx, ctx->frame_ok, ctx->frame_ok_n, (size_t)n_frames, sizeof(uint32_t));
-        if (rc) return rc;
-
-        IdxParams ip;
-        ip.stream = d_stream;
-        ip.frame_offsets = d_frame_offsets;
-        ip.stream_bytes = stream_bytes;
-        ip.chunk_off = ctx->chunk_off;
-        ip.frame_ok = ctx->frame_ok;
-        ip.results = d_results;
-        ip.T = g.T;
-        ip.chunks_per_frame = dcpf;
-        ip.min_bytes = 1;
-        ip.geom = dg;
-        // Few frames: cut each frame into pieces so that the index pass fills the device too
-        // (>= 4 chunks per piece, about 1024 workgroups in all); from 256 frames on, one workgroup per frame.
-        ip.split = 1;
-        ip.frame_ctr = nullptr;
-        ip.frame_flag = nullptr;
-        if (n_frames < 256 && dcpf >= 8u) {
-            uint32_t sp = 1024u / (uint32_t)n_frames;
-            const uint32_t most = (dcpf + 3u) / 4u;
-            if (sp > most) sp = most;
-            if (sp > 1u) {
-                const size_t before = ctx->idx_ctr_n;
-                rc = grow(ctx, ctx->idx_ctr, ctx->idx_ctr_n, 2 * (size_t)n_frames, sizeof(uint32_t));
-                if (rc) return rc;
-                if (ctx->idx_ctr_n != before)   // fresh block: the kernel keeps it zero from here on
-                    HIP_TRY(ctx, hipMemsetAsync(ctx->idx_ctr, 0, ctx->idx_ctr_n * sizeof(uint32_t), ctx->stream));
-                ip.split = sp;
-                ip.frame_ctr = ctx->idx_ctr;
-                ip.frame_flag = ctx->idx_ctr + n_frames;
-            }
-        }
-        span_begin(ctx, 1);
-        HIP_TRY(ctx, launch_decode_index(ip, n_frames, ctx->stream));
-        span_end(ctx);
     }
 
     DecParams p;
@@ -790,15 +804,6 @@ int dbde_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t st
 }
 
 // ---- window decode ----------------------------------------------------------------------------------------
-// Index split of the decode index kernel, as dbde_hip_decode_frames chooses it: few frames are cut into pieces so that
-// the index pass fills the device too (>= 4 chunks per piece, about 1024 workgroups in all).
-static uint32_t index_split_for(int n_frames, uint32_t cpf) {
-    if (n_frames < 1 || n_frames >= 256 || cpf < 8u) return 1u;
-    uint32_t sp = 1024u / (uint32_t)n_frames;
-    const uint32_t most = (cpf + 3u) / 4u;
-    return sp > most ? most : (sp < 1u ? 1u : sp);
-}
-
 struct RoiPlan {
     Geometry g;
     DecGeom dg;                       // the index's chunks (roi_index_geometry)
@@ -868,48 +873,6 @@ int dbde16_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int 
     return DBDE_HIP_OK;
 }
 
-// The decode index kernel with the window decoder's chunk geometry (pl.dg, roi_index_geometry) and index split, in
-// timing slot 1: validation, results and per-chunk payload offsets (ctx->chunk_off, ctx->frame_ok) of n_frames > 0
-// frames, exactly as dbde_hip_decode_frames validates them.  Shared by the window decoders and dbde_hip_project.
-static int roi_index(dbde_hip_ctx *ctx, const RoiPlan &pl, uint32_t min_bytes, const uint8_t *d_stream,
-                     size_t stream_bytes, const uint64_t *d_frame_offsets, int n_frames,
-                     dbde_hip_frame_result *d_results) {
-    const uint32_t cpf = pl.dg.cpf;
-    int rc = grow(ctx, ctx->chunk_off, ctx->chunk_off_n, (size_t)n_frames * (cpf + 1u), sizeof(uint32_t));
-    if (rc) return rc;
-    rc = grow(ctx, ctx->frame_ok, ctx->frame_ok_n, (size_t)n_frames, sizeof(uint32_t));
-    if (rc) return rc;
-
-    IdxParams ip;
-    ip.stream = d_stream;
-    ip.frame_offsets = d_frame_offsets;
-    ip.stream_bytes = stream_bytes;
-    ip.chunk_off = ctx->chunk_off;
-    ip.frame_ok = ctx->frame_ok;
-    ip.results = d_results;
-    ip.T = pl.g.T;
-    ip.chunks_per_frame = cpf;
-    ip.min_bytes = min_bytes;
-    ip.geom = pl.dg;
-    ip.split = 1;
-    ip.frame_ctr = nullptr;
-    ip.frame_flag = nullptr;
-    if (pl.split > 1u) {
-        const size_t before = ctx->idx_ctr_n;
-        rc = grow(ctx, ctx->idx_ctr, ctx->idx_ctr_n, 2 * (size_t)n_frames, sizeof(uint32_t));
-        if (rc) return rc;
-        if (ctx->idx_ctr_n != before)   // fresh block: the kernel keeps it zero from here on
-            HIP_TRY(ctx, hipMemsetAsync(ctx->idx_ctr, 0, ctx->idx_ctr_n * sizeof(uint32_t), ctx->stream));
-        ip.split = pl.split;
-        ip.frame_ctr = ctx->idx_ctr;
-        ip.frame_flag = ctx->idx_ctr + n_frames;
-    }
-    span_begin(ctx, 1);
-    HIP_TRY(ctx, launch_decode_index(ip, n_frames, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
 // Both window decoders: the index (min_bytes: 1 = DBDE, 2 = DBDE16) in timing slot 1, the window kernel in slot 2.
 static int decode_roi_common(dbde_hip_ctx *ctx, const char *name, uint32_t min_bytes, const uint8_t *d_stream,
                              size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
@@ -924,7 +887,7 @@ static int decode_roi_common(dbde_hip_ctx *ctx, const char *name, uint32_t min_b
     if (!d_stream || !d_frame_offsets || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
     if (n_frames == 0) return DBDE_HIP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = roi_index(ctx, pl, min_bytes, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results);
+    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.dg, min_bytes, pl.split);
     if (rc) return rc;
 
     RoiParams p;
@@ -948,8 +911,7 @@ static int decode_roi_common(dbde_hip_ctx *ctx, const char *name, uint32_t min_b
     p.rows = d_origins ? pl.max_ty : pl.nty;
     p.pieces = d_origins ? pl.pieces : pl.pieces_fixed;
     span_begin(ctx, 2);
-    HIP_TRY(ctx, min_bytes == 2u ? launch_decode_roi16(p, (uint32_t)n_frames, pl.threads, ctx->stream)
-                                 : launch_decode_roi(p, (uint32_t)n_frames, pl.threads, ctx->stream));
+    HIP_TRY(ctx, launch_decode_roi(p, (uint32_t)n_frames, pl.threads, min_bytes, ctx->stream));
     span_end(ctx);
     return DBDE_HIP_OK;
 }
@@ -1049,7 +1011,7 @@ int dbde_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_b
     if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n_frames > 0) {
-        int rc = roi_index(ctx, pl.roi, 1u, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results);
+        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, 1u, pl.roi.split);
         if (rc) return rc;
     }
     ProjParams p;
@@ -1337,27 +1299,9 @@ int dbde16_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t 
     const uint64_t n_chunks64 = (uint64_t)n_frames * dg.cpf;
     if (n_chunks64 >= (1ull << 31)) return fail(ctx, DBDE_HIP_ERR_ARG, "decode16: too many chunks in one call");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = grow(ctx, ctx->chunk_off, ctx->chunk_off_n, (size_t)n_chunks64 + (size_t)n_frames, sizeof(uint32_t));
+    // U16 minima, depth <= 16, nm = 2T; one index workgroup per frame (the split form is a latency tool of the 8-bit path)
+    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, dg, 2u, 1u);
     if (rc) return rc;
-    rc = grow(ctx, ctx->frame_ok, ctx->frame_ok_n, (size_t)n_frames, sizeof(uint32_t));
-    if (rc) return rc;
-    IdxParams ip;
-    ip.stream = d_stream;
-    ip.frame_offsets = d_frame_offsets;
-    ip.stream_bytes = stream_bytes;
-    ip.chunk_off = ctx->chunk_off;
-    ip.frame_ok = ctx->frame_ok;
-    ip.results = d_results;
-    ip.T = g.T;
-    ip.chunks_per_frame = dg.cpf;
-    ip.min_bytes = 2;        // U16 minima, depth <= 16, nm = 2T
-    ip.geom = dg;
-    ip.split = 1;            // one index workgroup per frame (the split form is a latency tool of the 8-bit path)
-    ip.frame_ctr = nullptr;
-    ip.frame_flag = nullptr;
-    span_begin(ctx, 1);
-    HIP_TRY(ctx, launch_decode_index(ip, n_frames, ctx->stream));
-    span_end(ctx);
     dbde16::DecParams16 p;
     p.stream = d_stream;
     p.stream_bytes = stream_bytes;

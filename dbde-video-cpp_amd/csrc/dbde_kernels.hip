@@ -18,6 +18,7 @@
 #include "dbde_kernels.h"
 
 #include "dbde_bits.h"
+#include "dbde_device.h"
 
 
 namespace dbde {
@@ -72,24 +73,6 @@ __device__ __forceinline__ uint32_t load_u32_bytes(const uint8_t *p) {
 }
 __device__ __forceinline__ uint64_t load_u64_bytes(const uint8_t *p) {
     return (uint64_t)load_u32_bytes(p) | ((uint64_t)load_u32_bytes(p + 4) << 32);
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// Wave-wide inclusive scan with DPP row shifts / row broadcasts (gfx9 wave64 idiom): no LDS.
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
-    uint32_t t = x;
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x111, 0xF, 0xF, false);   // row_shr:1
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x112, 0xF, 0xF, false);   // row_shr:2
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x114, 0xF, 0xF, false);   // row_shr:4
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x118, 0xF, 0xF, false);   // row_shr:8
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1,3
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2,3
-    return t;
 }
 
 // Inclusive scan of one value per lane across the 256-thread block.

@@ -22,6 +22,7 @@
 #include "dbde_project_kernels.h"
 
 #include "dbde_bits.h"
+#include "dbde_device.h"
 
 namespace dbde {
 
@@ -29,23 +30,6 @@ namespace {
 
 constexpr uint32_t kProjGroup = 4;                 // frames per pipeline step
 constexpr uint32_t kProjWaves = kProjThreads / 64u;
-
-__device__ __forceinline__ uint32_t proj_wave_scan_incl(uint32_t x) {   // DPP row shifts / broadcasts, no LDS
-    uint32_t t = x;
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x111, 0xF, 0xF, false);   // row_shr:1
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x112, 0xF, 0xF, false);   // row_shr:2
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x114, 0xF, 0xF, false);   // row_shr:4
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x118, 0xF, 0xF, false);   // row_shr:8
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1,3
-    t += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2,3
-    return t;
-}
-
-__device__ __forceinline__ uint32_t proj_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ uint32_t readlane(uint32_t v, uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j); }
 
@@ -55,7 +39,7 @@ __device__ void write_count(const ProjParams &p) {
     const uint32_t tid = threadIdx.x;
     uint32_t c = 0;
     for (uint32_t g = tid; g < p.n_frames; g += kProjThreads) c += p.frame_ok[g] != 0u ? 1u : 0u;
-    c = proj_wave_sum(c);
+    c = wave_sum(c);
     if ((tid & 63u) == 0u) s_c[tid >> 6] = c;
     __syncthreads();
     if (tid == 0) {
@@ -176,8 +160,8 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(ProjParams p) {
 #pragma unroll
         for (uint32_t k = 0; k < G; k++) {
             const uint32_t d = has_tile ? (m.d8[k] > 8u ? 8u : m.d8[k]) : 0u;   // (a validated frame has none above 8)
-            incl[k] = proj_wave_scan_incl(r == 0u ? d : 0u);
-            const uint32_t pw = proj_wave_sum(__builtin_amdgcn_sad_u8(m.pre[k] & pre_keep(m.fb[k]), 0u, 0u));
+            incl[k] = wave_scan_incl(r == 0u ? d : 0u);
+            const uint32_t pw = wave_sum(__builtin_amdgcn_sad_u8(m.pre[k] & pre_keep(m.fb[k]), 0u, 0u));
             if (lane == 63u) s_wsum[buf][k][0][wave] = incl[k];
             if (lane == 0u) s_wsum[buf][k][1][wave] = pw;
         }

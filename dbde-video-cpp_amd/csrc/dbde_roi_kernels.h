@@ -1,8 +1,8 @@
 // dbde_roi_kernels.h -- launch interface of the window (region-of-interest) decoder, dbde_roi_kernels.hip.
 //
 // The window decoder reuses the decode index kernel (dbde_kernels.hip: validation and per-chunk payload offsets,
-// exactly as dbde_hip_decode_frames / dbde16_hip_decode_frames run them) and adds one kernel per pixel size that decodes
-// only the tiles a window covers.
+// exactly as dbde_hip_decode_frames / dbde16_hip_decode_frames run them) and adds one kernel, templated on the pixel
+// size, that decodes only the tiles a window covers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,7 +39,7 @@ struct RoiParams {
     const uint32_t *chunk_off;      // [n_frames][cpf + 1] from launch_decode_index
     const uint32_t *frame_ok;       // [n_frames]
     const int32_t *origins;         // optional [n_frames][2] (x, y), clamped into the frame; NULL -> (x0, y0)
-    uint8_t *out;                   // [n_frames][rh][rw] pixels (U8; U16 for decode_roi16_kernel)
+    uint8_t *out;                   // [n_frames][rh][rw] pixels (U8; U16 for DBDE16 frames)
     int W, H;
     int x0, y0, rw, rh;
     uint32_t w, h, T;
@@ -48,17 +48,17 @@ struct RoiParams {
     uint32_t pieces;                // workgroups per window tile row (the most any origin needs)
 };
 
-// One workgroup per (frame, window tile row, piece of kRoi*Threads tiles); grid = n_frames * rows * pieces.
-hipError_t launch_decode_roi(const RoiParams &p, uint32_t n_frames, uint32_t threads, hipStream_t s);
-
-// DBDE16 (U16 pixels, depth <= 16, U16 minima): the same launch shape and parameters, p.out holding U16 pixels.  A tile
-// carries up to 128 payload bytes and a 16-byte band row, twice the 8-bit kernel's LDS per tile; windows more than 64
-// tiles across take pieces of kRoi16WideThreads tiles (the width is a measured choice).
+// DBDE16 (U16 pixels, depth <= 16, U16 minima): a tile carries up to 128 payload bytes and a 16-byte band row, twice
+// the 8-bit kernel's LDS per tile; windows more than 64 tiles across take pieces of kRoi16WideThreads tiles
+// (the width is a measured choice).
 #ifndef DBDE_ROI16_WIDE_THREADS
 #define DBDE_ROI16_WIDE_THREADS 128
 #endif
 constexpr uint32_t kRoi16WideThreads = DBDE_ROI16_WIDE_THREADS;
 static_assert(kRoi16WideThreads == 64u || kRoi16WideThreads == 128u || kRoi16WideThreads == 256u, "a piece is 64, 128 or 256 tiles");
-hipError_t launch_decode_roi16(const RoiParams &p, uint32_t n_frames, uint32_t threads, hipStream_t s);
+
+// One workgroup per (frame, window tile row, piece of `threads` tiles); grid = n_frames * rows * pieces.  pix: bytes per
+// pixel, 1 = DBDE (threads kRoiNarrowThreads or kRoiWideThreads), 2 = DBDE16 (kRoiNarrowThreads or kRoi16WideThreads).
+hipError_t launch_decode_roi(const RoiParams &p, uint32_t n_frames, uint32_t threads, uint32_t pix, hipStream_t s);
 
 }  // namespace dbde
