@@ -56,7 +56,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_scatter_plan", "dbde_hip_create_on_own_stream", "dbde_hip_set_host_staging",
     "dbde_hip_decode_roi", "dbde_hip_unpack_image_roi", "dbde_hip_roi_plan",
     "dbde16_hip_decode_roi", "dbde16_hip_roi_plan",
-    "dbde_hip_project", "dbde_hip_project_plan",
+    "dbde_hip_project", "dbde_hip_project_plan", "dbde16_hip_project", "dbde16_hip_project_plan",
 ]
 
 
@@ -175,6 +175,10 @@ def lib():
     L.dbde_hip_project.restype = i
     L.dbde_hip_project_plan.argtypes = [i, i, i, i, i, i, i, C.c_uint, i, C.POINTER(ProjectPlan)]
     L.dbde_hip_project_plan.restype = i
+    L.dbde16_hip_project.argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
+    L.dbde16_hip_project.restype = i
+    L.dbde16_hip_project_plan.argtypes = [i, i, i, i, i, i, i, C.c_uint, i, C.POINTER(ProjectPlan)]
+    L.dbde16_hip_project_plan.restype = i
     L.dbde_hip_unpack_frame.argtypes = [vp, C.POINTER(vp), i, i, vp]
     L.dbde_hip_pack_frame_header.restype = sz
     L.dbde_hip_pack_frame_header.argtypes = [C.POINTER(FrameHeader), vp]
@@ -479,19 +483,35 @@ def project_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, stats=("max", "min"
     return pl.as_dict()
 
 
+def project16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, stats=("max", "min", "sum", "sumsq"), n_cu=256):
+    """dbde16_hip_project_plan: project_plan for DBDE16 projections (Codec.project16)."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    pl = ProjectPlan()
+    rc = lib().dbde16_hip_project_plan(W, H, n_frames, x, y, rw, rh, stats_mask(stats), n_cu, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"dbde16_hip_project_plan({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, {stats}) -> {rc}")
+    return pl.as_dict()
+
+
 class Projection:
     """Device tensors of a temporal projection (Codec.project): max / min uint8 (rh, rw), sum / sumsq int64 (rh, rw)
-    (the values stay below 2^63), count int64 (1,).  A statistic that was not asked for is None."""
+    (the values stay below 2^63), count int64 (1,).  A statistic that was not asked for is None.  Codec.project16's
+    max / min are int16 tensors holding the U16 bits (as decode_frames16 returns its images)."""
 
     def __init__(self, max=None, min=None, sum=None, sumsq=None, count=None):
         self.max, self.min, self.sum, self.sumsq, self.count = max, min, sum, sumsq, count
 
     @classmethod
-    def empty(cls, rh, rw, stats, device):
+    def empty(cls, rh, rw, stats, device, pix=1):
+        """Uninitialised outputs for `stats`; pix: bytes per pixel of max / min (1: uint8, 2: int16 for DBDE16)."""
         mask = stats_mask(stats)
-        u8 = lambda: torch.empty((rh, rw), dtype=torch.uint8, device=device)    # noqa: E731
+        if pix not in (1, 2):
+            raise ValueError(f"pix must be 1 or 2, not {pix!r}")
+        mm_dtype = torch.uint8 if pix == 1 else torch.int16
+        mm = lambda: torch.empty((rh, rw), dtype=mm_dtype, device=device)      # noqa: E731
         i64 = lambda: torch.empty((rh, rw), dtype=torch.int64, device=device)   # noqa: E731
-        return cls(u8() if mask & 1 else None, u8() if mask & 2 else None, i64() if mask & 4 else None,
+        return cls(mm() if mask & 1 else None, mm() if mask & 2 else None, i64() if mask & 4 else None,
                    i64() if mask & 8 else None, torch.zeros(1, dtype=torch.int64, device=device))
 
     def mean(self):
@@ -693,6 +713,25 @@ class Codec:
                                           W, H, n, x, y, rw, rh, origins.data_ptr() if origins is not None else None,
                                           out.data_ptr(), results.data_ptr())
         self._check(rc, "dbde16_hip_decode_roi")
+        return out, results
+
+    def project16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x=0, y=0, rw=None, rh=None,
+                  stats=("max", "min", "sum", "sumsq"), out=None, accumulate=False, results=None):
+        """DBDE16 temporal projection: project's arguments and results, with max / min as int16 tensors holding the
+        U16 bits (Projection.empty(..., pix=2)).  .to(torch.int32) & 0xFFFF gives their values."""
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out= (the projection to continue)")
+            out = Projection.empty(rh, rw, stats, self.device, pix=2)
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        rc = self.L.dbde16_hip_project(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                       W, H, n, x, y, rw, rh, 1 if accumulate else 0, ptr(out.max), ptr(out.min),
+                                       ptr(out.sum), ptr(out.sumsq), ptr(out.count), ptr(results) if n > 0 else None)
+        self._check(rc, "dbde16_hip_project")
         return out, results
 
     # ---- host-pointer API: the reference's functions -------------------------------------

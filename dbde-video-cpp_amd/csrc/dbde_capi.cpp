@@ -939,13 +939,17 @@ struct ProjectPlan {
 };
 // Frames per segment: a segment is cut only to fill the device (about 4 workgroups per CU) and never below
 // kProjMinFramesPerSegment frames, whose partials would cost more traffic than they save; never above the U32 bound.
+// pix: 1 = DBDE (dbde_hip_project), 2 = DBDE16 (dbde16_hip_project: kProj16Tiles tiles per workgroup, U16 / U64
+// partials); the segment rule is the same for both.
 static constexpr uint32_t kProjMinFramesPerSegment = 32;
 static const char *plan_project(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
-                                ProjectPlan &pl) {
-    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi)) return why;
+                                uint32_t pix, ProjectPlan &pl) {
+    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, pix == 2u ? kRoi16WideThreads : kRoiWideThreads))
+        return why;
     if (stats < 1u || stats > kProjAll) return "no statistic (or an unknown one) requested";
     pl.stats = stats;
-    pl.pieces = (pl.roi.ntx + kProjTiles - 1u) / kProjTiles;
+    const uint32_t tiles = pix == 2u ? kProj16Tiles : kProjTiles;
+    pl.pieces = (pl.roi.ntx + tiles - 1u) / tiles;
     pl.rows = pl.roi.nty;
     const uint64_t base = (uint64_t)pl.pieces * pl.rows, n = (uint64_t)n_frames;
     const uint64_t target = 4ull * (uint64_t)(n_cu > 0 ? n_cu : 1);
@@ -965,14 +969,14 @@ static const char *plan_project(int W, int H, int n_frames, int x0, int y0, int 
     const uint64_t pixels = (uint64_t)rw * (uint64_t)rh;
     pl.combine_grid = seg > 1u ? (pixels + kProjCombineThreads - 1u) / kProjCombineThreads : 0u;
     if (pl.combine_grid >= (1ull << 31)) return "too many workgroups in one call";
-    pl.workspace = project_workspace_bytes(stats, pl.segments, pixels);
+    pl.workspace = project_workspace_bytes(stats, pl.segments, pixels, pix);
     return nullptr;
 }
 
-int dbde_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
-                          dbde_hip_project_plan_t *plan) {
+static int project_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
+                               uint32_t pix, dbde_hip_project_plan_t *plan) {
     ProjectPlan pl;
-    if (!plan || plan_project(W, H, n_frames, x0, y0, rw, rh, stats, n_cu, pl)) return DBDE_HIP_ERR_ARG;
+    if (!plan || plan_project(W, H, n_frames, x0, y0, rw, rh, stats, n_cu, pix, pl)) return DBDE_HIP_ERR_ARG;
     memset(plan, 0, sizeof *plan);
     plan->tile_x = (int32_t)pl.roi.tx0;
     plan->tile_y = (int32_t)pl.roi.ty0;
@@ -982,7 +986,7 @@ int dbde_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, in
     plan->chunk_tiles = pl.roi.dg.ct;
     plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
     plan->index_split = pl.roi.split;
-    plan->threads = kProjThreads;
+    plan->threads = kProjThreads;   // (DBDE16: 16 lanes per tile, threads / 16 tiles)
     plan->pieces_x = pl.pieces;
     plan->segments = pl.segments;
     plan->frames_per_segment = pl.fps;
@@ -993,39 +997,54 @@ int dbde_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, in
     return DBDE_HIP_OK;
 }
 
-int dbde_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
-                     int W, int H, int n_frames, int x0, int y0, int rw, int rh, int accumulate, uint8_t *d_max,
-                     uint8_t *d_min, uint64_t *d_sum, uint64_t *d_sumsq, uint64_t *d_count,
-                     dbde_hip_frame_result *d_results) {
+int dbde_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
+                          dbde_hip_project_plan_t *plan) {
+    return project_plan_common(W, H, n_frames, x0, y0, rw, rh, stats, n_cu, 1u, plan);
+}
+
+int dbde16_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
+                            dbde_hip_project_plan_t *plan) {
+    return project_plan_common(W, H, n_frames, x0, y0, rw, rh, stats, n_cu, 2u, plan);
+}
+
+// Both projections: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the projection
+// kernels in slot 2.  d_max / d_min hold U8 (pix 1) or U16 (pix 2) pixels.
+static int project_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
+                          size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
+                          int y0, int rw, int rh, int accumulate, void *d_max, void *d_min, uint64_t *d_sum,
+                          uint64_t *d_sumsq, uint64_t *d_count, dbde_hip_frame_result *d_results) {
     if (!ctx) return DBDE_HIP_ERR_ARG;
     const unsigned stats = (d_max ? kProjMax : 0u) | (d_min ? kProjMin : 0u) | (d_sum ? kProjSum : 0u) |
                            (d_sumsq ? kProjSumSq : 0u);
     ProjectPlan pl;
-    if (const char *why = plan_project(W, H, n_frames, x0, y0, rw, rh, stats, ctx->n_cu, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "project: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", why, W, H, n_frames,
+    if (const char *why = plan_project(W, H, n_frames, x0, y0, rw, rh, stats, ctx->n_cu, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", name, why, W, H, n_frames,
                     rw, rh, x0, y0);
-    if (!d_stream || !d_frame_offsets || !d_count) return fail(ctx, DBDE_HIP_ERR_ARG, "project: null pointer");
+    if (!d_stream || !d_frame_offsets || !d_count) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
     if ((reinterpret_cast<uintptr_t>(d_sum) | reinterpret_cast<uintptr_t>(d_sumsq) |
          reinterpret_cast<uintptr_t>(d_count)) & 7u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "project: U64 outputs must be 8-byte aligned");
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U64 outputs must be 8-byte aligned", name);
+    if ((reinterpret_cast<uintptr_t>(d_max) | reinterpret_cast<uintptr_t>(d_min)) & (pix - 1u))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U16 outputs must be 2-byte aligned", name);
     if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n_frames > 0) {
-        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, 1u, pl.roi.split);
+        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
         if (rc) return rc;
     }
     ProjParams p;
     memset(&p, 0, sizeof p);
-    if (pl.workspace) {
+    if (pl.workspace) {   // the partials in project_workspace_bytes' order: max, min, sum, sumsq, each 16-byte aligned
         int rc = grow(ctx, ctx->proj_ws, ctx->proj_ws_bytes, (size_t)pl.workspace, 1);
         if (rc) return rc;
         const uint64_t n = (uint64_t)pl.segments * (uint64_t)rw * (uint64_t)rh;
-        const uint64_t u8 = (n + 15u) & ~(uint64_t)15, u32 = (4u * n + 15u) & ~(uint64_t)15;
+        const uint64_t mm = (pix * n + 15u) & ~(uint64_t)15, u32 = (4u * n + 15u) & ~(uint64_t)15;
+        const uint64_t sq = pix == 1u ? u32 : (8u * n + 15u) & ~(uint64_t)15;
         uint8_t *w = ctx->proj_ws;
-        if (d_max) { p.ws_max = w; w += u8; }
-        if (d_min) { p.ws_min = w; w += u8; }
+        if (d_max) { p.ws_max = w; w += mm; }
+        if (d_min) { p.ws_min = w; w += mm; }
         if (d_sum) { p.ws_sum = reinterpret_cast<uint32_t *>(w); w += u32; }
-        if (d_sumsq) { p.ws_sumsq = reinterpret_cast<uint32_t *>(w); w += u32; }
+        if (d_sumsq) { p.ws_sumsq = reinterpret_cast<uint32_t *>(w); w += sq; }
     }
     p.stream = d_stream;
     p.frame_offsets = d_frame_offsets;
@@ -1047,15 +1066,31 @@ int dbde_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_b
     p.segments = pl.segments;
     p.fps = pl.fps;
     p.accumulate = accumulate ? 1 : 0;
-    p.out_max = d_max;
-    p.out_min = d_min;
+    p.out_max = static_cast<uint8_t *>(d_max);
+    p.out_min = static_cast<uint8_t *>(d_min);
     p.out_sum = d_sum;
     p.out_sumsq = d_sumsq;
     p.out_count = d_count;
     span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_project(p, stats, ctx->stream));
+    HIP_TRY(ctx, pix == 2u ? launch_project16(p, stats, ctx->stream) : launch_project(p, stats, ctx->stream));
     span_end(ctx);
     return DBDE_HIP_OK;
+}
+
+int dbde_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+                     int W, int H, int n_frames, int x0, int y0, int rw, int rh, int accumulate, uint8_t *d_max,
+                     uint8_t *d_min, uint64_t *d_sum, uint64_t *d_sumsq, uint64_t *d_count,
+                     dbde_hip_frame_result *d_results) {
+    return project_common(ctx, "project", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh,
+                          accumulate, d_max, d_min, d_sum, d_sumsq, d_count, d_results);
+}
+
+int dbde16_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                       const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                       int accumulate, uint16_t *d_max, uint16_t *d_min, uint64_t *d_sum, uint64_t *d_sumsq,
+                       uint64_t *d_count, dbde_hip_frame_result *d_results) {
+    return project_common(ctx, "project16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
+                          rh, accumulate, d_max, d_min, d_sum, d_sumsq, d_count, d_results);
 }
 
 int dbde_hip_index_stream_async(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, int W, int H,

@@ -33,6 +33,21 @@ __device__ __forceinline__ uint32_t lds_u32_at(const uint32_t *s32, uint32_t a) 
     return __builtin_amdgcn_alignbyte(s32[(a >> 2) + 1u], s32[a >> 2], a & 3u);
 }
 
+// cut_row16's step: four pixels of d bits at bit 0 of the 64-bit window x1:x0 -> two dwords of two U16 pixels each,
+// the minimum added.  c2 / c3: 2d >= 32 / 3d >= 32, the caller's per-tile flags.  The 16-bit projection kernel (one
+// lane per half row) calls it on its own.
+__device__ __forceinline__ void cut_four16(uint32_t x0, uint32_t x1, const uint32_t &d, const uint32_t &m32,
+                                           const uint32_t &mn2, const bool &c2, const bool &c3, uint32_t &e0,
+                                           uint32_t &e1) {
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    const uint32_t p0 = x0 & m32;
+    const uint32_t p1 = __builtin_amdgcn_alignbit(x1, x0, d) & m32;
+    const uint32_t p2 = __builtin_amdgcn_alignbit(c2 ? 0u : x1, c2 ? x1 : x0, 2u * d) & m32;
+    const uint32_t p3 = __builtin_amdgcn_alignbit(c3 ? 0u : x1, c3 ? x1 : x0, 3u * d) & m32;
+    e0 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, p0 | (p1 << 16)) + __builtin_bit_cast(u16x2, mn2));
+    e1 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, p2 | (p3 << 16)) + __builtin_bit_cast(u16x2, mn2));
+}
+
 // One DBDE16 tile row (8 pixels of d <= 16 bits, the 8d-bit integer at byte a of the tile payload) -> four dwords of two
 // U16 pixels each; shared by dec16_kernel and decode_roi_kernel<T, 2>.  The row's two 4-pixel halves start at bytes a
 // and ah = a + d/2 (plus 4 bits when d is odd); q / qh point at the three aligned dwords holding each.  A half comes out
@@ -44,23 +59,13 @@ __device__ __forceinline__ uint32_t lds_u32_at(const uint32_t *s32, uint32_t a) 
 __device__ __forceinline__ void cut_row16(const uint32_t *q, const uint32_t *qh, uint32_t a, uint32_t ah, const uint32_t &d,
                                           const uint32_t &m32, const uint32_t &mn2, uint32_t &o0, uint32_t &o1,
                                           uint32_t &o2, uint32_t &o3) {
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
     const uint32_t sh_odd = (d & 1u) * 4u;
     const bool c2 = 2u * d >= 32u, c3 = 3u * d >= 32u;
-    // four pixels of d bits at bit 0 of the 64-bit window x1:x0
-    auto four = [&](uint32_t x0, uint32_t x1, uint32_t &e0, uint32_t &e1) __attribute__((always_inline)) {
-        const uint32_t p0 = x0 & m32;
-        const uint32_t p1 = __builtin_amdgcn_alignbit(x1, x0, d) & m32;
-        const uint32_t p2 = __builtin_amdgcn_alignbit(c2 ? 0u : x1, c2 ? x1 : x0, 2u * d) & m32;
-        const uint32_t p3 = __builtin_amdgcn_alignbit(c3 ? 0u : x1, c3 ? x1 : x0, 3u * d) & m32;
-        e0 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, p0 | (p1 << 16)) + __builtin_bit_cast(u16x2, mn2));
-        e1 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, p2 | (p3 << 16)) + __builtin_bit_cast(u16x2, mn2));
-    };
     const uint32_t x0 = __builtin_amdgcn_alignbyte(q[1], q[0], a), x1 = __builtin_amdgcn_alignbyte(q[2], q[1], a);
     const uint32_t w0 = __builtin_amdgcn_alignbyte(qh[1], qh[0], ah), w1 = __builtin_amdgcn_alignbyte(qh[2], qh[1], ah);
     const uint32_t h0 = __builtin_amdgcn_alignbit(w1, w0, sh_odd), h1 = w1 >> sh_odd;
-    four(x0, x1, o0, o1);
-    four(h0, h1, o2, o3);
+    cut_four16(x0, x1, d, m32, mn2, c2, c3, o0, o1);
+    cut_four16(h0, h1, d, m32, mn2, c2, c3, o2, o3);
 }
 
 }  // namespace dbde

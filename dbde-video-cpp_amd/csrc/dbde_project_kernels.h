@@ -19,7 +19,10 @@ constexpr uint32_t kProjMax = 1u, kProjMin = 2u, kProjSum = 4u, kProjSumSq = 8u,
 constexpr uint32_t kProjThreads = 256;
 constexpr uint32_t kProjTiles = kProjThreads / 8u;
 // Frames one workgroup reduces into its U32 per-lane sums: 65,536 * 255^2 < 2^32, so the sums of squares are exact.
+// DBDE16 keeps the same bound through its U32 sums (65,536 * 65,535 < 2^32); its sums of squares are U64.
 constexpr uint32_t kProjMaxFramesPerSegment = 65536;
+// DBDE16: one lane per half tile row, 16 lanes per tile.
+constexpr uint32_t kProj16Tiles = kProjThreads / 16u;
 // Threads per workgroup of the combine kernel (one window pixel per thread).
 constexpr uint32_t kProjCombineThreads = 256;
 
@@ -38,10 +41,12 @@ struct ProjParams {
     uint32_t rows, pieces;          // window tile rows; workgroups (of kProjTiles tiles) across one
     uint32_t segments, fps;         // frame segments; frames per segment (the last may hold fewer)
     int accumulate;                 // 1: combine into what the outputs hold
-    // outputs (segments == 1: written by the projection kernel; otherwise by the combine kernel); NULL = not computed
+    // outputs (segments == 1: written by the projection kernel; otherwise by the combine kernel); NULL = not computed.
+    // The 16-bit kernels read out_max / out_min as U16 arrays.
     uint8_t *out_max, *out_min;
     uint64_t *out_sum, *out_sumsq, *out_count;
-    // per-segment partials [segments][rh * rw] (segments > 1 only), present for the requested statistics
+    // per-segment partials [segments][rh * rw] (segments > 1 only), present for the requested statistics.  The 16-bit
+    // kernels read ws_max / ws_min as U16 arrays and ws_sumsq as a U64 array.
     uint8_t *ws_max, *ws_min;
     uint32_t *ws_sum, *ws_sumsq;
 };
@@ -49,7 +54,11 @@ struct ProjParams {
 // The projection kernel (one instance per statistics set, `stats` = kProj* mask, 1..15): grid = pieces * rows *
 // segments workgroups of kProjThreads; with segments > 1 the combine kernel follows on the same stream.
 hipError_t launch_project(const ProjParams &p, uint32_t stats, hipStream_t s);
-// Bytes of the per-segment partials of a window of `pixels` pixels (0 for one segment).
-uint64_t project_workspace_bytes(uint32_t stats, uint32_t segments, uint64_t pixels);
+// The same for DBDE16 frames (project16_kernel, kProj16Tiles tiles per workgroup, and its combine kernel).
+hipError_t launch_project16(const ProjParams &p, uint32_t stats, hipStream_t s);
+// Bytes of the per-segment partials of a window of `pixels` pixels (0 for one segment), laid out in the order max, min,
+// sum, sumsq, each 16-byte aligned.  pix: 1 = DBDE (U8 max / min, U32 sums), 2 = DBDE16 (U16 max / min, U32 sums, U64
+// sums of squares).
+uint64_t project_workspace_bytes(uint32_t stats, uint32_t segments, uint64_t pixels, uint32_t pix);
 
 }  // namespace dbde

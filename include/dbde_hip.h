@@ -312,6 +312,20 @@ int dbde16_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t str
                           const uint64_t *d_frame_offsets, int W, int H, int n_frames,
                           int x0, int y0, int rw, int rh, const int32_t *d_origins,
                           uint16_t *d_out, dbde_hip_frame_result *d_results);
+/* Temporal projection of DBDE16 frames: dbde_hip_project's contract with U16 pixels.
+ * Validation is dbde16_hip_decode_frames' own: a rejected frame reports the same d_results entry and adds nothing; the
+ * pixels reduced are exactly the U16 values dbde16_hip_decode_frames writes (minima that wrap modulo 2^16 included).
+ * d_max / d_min are U16 at any 2-byte aligned address; d_sum, d_sumsq and d_count U64, 8-byte aligned.  The empty
+ * projection is max 0, min 65535, sums 0, count 0.  accumulate, n_frames == 0, NULL statistics, stream_bytes and the
+ * timing slots are as in dbde_hip_project.
+ * Overflow: a workgroup sums at most 65,536 frames per pixel in U32 (65,536 * 65,535 < 2^32) -- the bound the plan
+ *   enforces -- and its sums of squares in U64 (one square alone, up to 65,535^2, fills a U32).
+ * Errors: DBDE_HIP_ERR_ARG as dbde_hip_project, and for a U16 output that is not 2-byte aligned. */
+int dbde16_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                       const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                       int x0, int y0, int rw, int rh, int accumulate,
+                       uint16_t *d_max, uint16_t *d_min, uint64_t *d_sum, uint64_t *d_sumsq,
+                       uint64_t *d_count, dbde_hip_frame_result *d_results);
 
 /* ---- multi-GPU: variable-length gather of the compressed stream to a root (RCCL over xGMI) ------------------- */
 /* Frames are independent, so the path shards by contiguous frame blocks (rank g of G owns frames
@@ -519,6 +533,11 @@ typedef struct dbde_hip_project_plan_t {
 } dbde_hip_project_plan_t;
 int dbde_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats,
                           int n_cu, dbde_hip_project_plan_t *plan);
+/* The same for dbde16_hip_project: the same window, index geometry and segment rule; the 16-bit kernel takes 16 lanes
+ * per tile (threads / 16 tiles per workgroup, pieces_x accordingly), max_frames_per_segment is its U32 bound on the
+ * sums (65,536 * 65,535 < 2^32), and workspace_bytes counts U16 max / min, U32 sum and U64 sumsq partials. */
+int dbde16_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats,
+                            int n_cu, dbde_hip_project_plan_t *plan);
 
 /* ---- kernel timing hook for bench.py ---------------------------------------------------- */
 /* When enabled, every encode / decode call brackets its kernels with HIP events on the
