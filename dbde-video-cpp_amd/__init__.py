@@ -338,24 +338,25 @@ class RoiPlan(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+def _roi_plan(fn, W, H, n_frames, x, y, rw, rh):
+    """roi_plan / roi16_plan through the C function named fn."""
+    pl = RoiPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, x, y, rw, rh, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}) -> {rc}")
+    return pl.as_dict()
+
+
 def roi_plan(W, H, n_frames, x, y, rw, rh):
     """dbde_hip_roi_plan: the tile window, index geometry and launch of a window decode (host arithmetic only).
     Raises ValueError where dbde_hip_decode_roi would return DBDE_HIP_ERR_ARG."""
-    pl = RoiPlan()
-    rc = lib().dbde_hip_roi_plan(W, H, n_frames, x, y, rw, rh, C.byref(pl))
-    if rc != OK:
-        raise ValueError(f"dbde_hip_roi_plan({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}) -> {rc}")
-    return pl.as_dict()
+    return _roi_plan("dbde_hip_roi_plan", W, H, n_frames, x, y, rw, rh)
 
 
 def roi16_plan(W, H, n_frames, x, y, rw, rh):
     """dbde16_hip_roi_plan: roi_plan for DBDE16 windows (dbde16_hip_decode_roi).
     Raises ValueError where dbde16_hip_decode_roi would return DBDE_HIP_ERR_ARG."""
-    pl = RoiPlan()
-    rc = lib().dbde16_hip_roi_plan(W, H, n_frames, x, y, rw, rh, C.byref(pl))
-    if rc != OK:
-        raise ValueError(f"dbde16_hip_roi_plan({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}) -> {rc}")
-    return pl.as_dict()
+    return _roi_plan("dbde16_hip_roi_plan", W, H, n_frames, x, y, rw, rh)
 
 
 def gather_check(nranks, root, sizes, caps):
@@ -470,28 +471,27 @@ class ProjectPlan(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved_"}
 
 
+def _project_plan(fn, W, H, n_frames, x, y, rw, rh, stats, n_cu):
+    """project_plan / project16_plan through the C function named fn."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    pl = ProjectPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, x, y, rw, rh, stats_mask(stats), n_cu, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, {stats}) -> {rc}")
+    return pl.as_dict()
+
+
 def project_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, stats=("max", "min", "sum", "sumsq"), n_cu=256):
     """dbde_hip_project_plan: the tile window, index geometry, launch and workspace of a projection (host arithmetic
     only).  rw / rh default to the rest of the frame.  Raises ValueError where dbde_hip_project would return
     DBDE_HIP_ERR_ARG."""
-    rw = W - x if rw is None else rw
-    rh = H - y if rh is None else rh
-    pl = ProjectPlan()
-    rc = lib().dbde_hip_project_plan(W, H, n_frames, x, y, rw, rh, stats_mask(stats), n_cu, C.byref(pl))
-    if rc != OK:
-        raise ValueError(f"dbde_hip_project_plan({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, {stats}) -> {rc}")
-    return pl.as_dict()
+    return _project_plan("dbde_hip_project_plan", W, H, n_frames, x, y, rw, rh, stats, n_cu)
 
 
 def project16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, stats=("max", "min", "sum", "sumsq"), n_cu=256):
     """dbde16_hip_project_plan: project_plan for DBDE16 projections (Codec.project16)."""
-    rw = W - x if rw is None else rw
-    rh = H - y if rh is None else rh
-    pl = ProjectPlan()
-    rc = lib().dbde16_hip_project_plan(W, H, n_frames, x, y, rw, rh, stats_mask(stats), n_cu, C.byref(pl))
-    if rc != OK:
-        raise ValueError(f"dbde16_hip_project_plan({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, {stats}) -> {rc}")
-    return pl.as_dict()
+    return _project_plan("dbde16_hip_project_plan", W, H, n_frames, x, y, rw, rh, stats, n_cu)
 
 
 class Projection:
@@ -611,20 +611,44 @@ class Codec:
         self._check(rc, "dbde_hip_decode_frames")
         return images, results
 
+    def _decode_roi(self, fn, dtype, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, origins, out,
+                    results):
+        """decode_roi / decode_roi16 through the C function named fn; dtype: the windows' tensor type."""
+        if out is None:
+            out = torch.empty((n, rh, rw), dtype=dtype, device=self.device)
+        if results is None:
+            results = torch.empty((n, 4), dtype=torch.int64, device=self.device)
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                 W, H, n, x, y, rw, rh, origins.data_ptr() if origins is not None else None,
+                                 out.data_ptr(), results.data_ptr())
+        self._check(rc, fn)
+        return out, results
+
+    def _project(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, stats, out,
+                 accumulate, results):
+        """project / project16 through the C function named fn; pix: bytes per pixel of max / min."""
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out= (the projection to continue)")
+            out = Projection.empty(rh, rw, stats, self.device, pix=pix)
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                 W, H, n, x, y, rw, rh, 1 if accumulate else 0, ptr(out.max), ptr(out.min),
+                                 ptr(out.sum), ptr(out.sumsq), ptr(out.count), ptr(results) if n > 0 else None)
+        self._check(rc, fn)
+        return out, results
+
     def decode_roi(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, origins=None, out=None,
                    results=None):
         """Decodes the rw x rh window at (x, y) of n frames (frame f at stream.data_ptr()+stream_offset+offsets[f]).
         origins: optional int32 device tensor (n, 2) of per-frame (x, y), clamped into the frame.
         Returns (windows uint8 (n, rh, rw), results (n, 4) int64) like decode_frames."""
-        if out is None:
-            out = torch.empty((n, rh, rw), dtype=torch.uint8, device=self.device)
-        if results is None:
-            results = torch.empty((n, 4), dtype=torch.int64, device=self.device)
-        rc = self.L.dbde_hip_decode_roi(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
-                                        W, H, n, x, y, rw, rh, origins.data_ptr() if origins is not None else None,
-                                        out.data_ptr(), results.data_ptr())
-        self._check(rc, "dbde_hip_decode_roi")
-        return out, results
+        return self._decode_roi("dbde_hip_decode_roi", torch.uint8, stream, stream_offset, stream_bytes, offsets, W, H,
+                                n, x, y, rw, rh, origins, out, results)
 
     def project(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x=0, y=0, rw=None, rh=None,
                 stats=("max", "min", "sum", "sumsq"), out=None, accumulate=False, results=None):
@@ -632,20 +656,8 @@ class Codec:
         stream.data_ptr()+stream_offset+offsets[f]): per-pixel max, min, sum and sum of squares of the accepted frames.
         rw / rh default to the rest of the frame.  out: a Projection to write into (accumulate=True continues it);
         its statistics are the ones computed.  Returns (Projection, results (n, 4) int64) like decode_frames."""
-        rw = W - x if rw is None else rw
-        rh = H - y if rh is None else rh
-        if out is None:
-            if accumulate:
-                raise ValueError("accumulate=True needs out= (the projection to continue)")
-            out = Projection.empty(rh, rw, stats, self.device)
-        if results is None:
-            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-        rc = self.L.dbde_hip_project(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
-                                     W, H, n, x, y, rw, rh, 1 if accumulate else 0, ptr(out.max), ptr(out.min),
-                                     ptr(out.sum), ptr(out.sumsq), ptr(out.count), ptr(results) if n > 0 else None)
-        self._check(rc, "dbde_hip_project")
-        return out, results
+        return self._project("dbde_hip_project", 1, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh,
+                             stats, out, accumulate, results)
 
     def index_stream(self, stream, stream_offset, stream_bytes, W, H, max_frames):
         offsets = torch.empty(max(max_frames, 1), dtype=torch.int64, device=self.device)
@@ -705,34 +717,15 @@ class Codec:
         """DBDE16 window decode: the rw x rh window at (x, y) of n frames (frame f at
         stream.data_ptr()+stream_offset+offsets[f]); origins as in decode_roi.  Returns (windows int16 (n, rh, rw)
         holding the U16 bits, as decode_frames16 does; results (n, 4) int64)."""
-        if out is None:
-            out = torch.empty((n, rh, rw), dtype=torch.int16, device=self.device)
-        if results is None:
-            results = torch.empty((n, 4), dtype=torch.int64, device=self.device)
-        rc = self.L.dbde16_hip_decode_roi(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
-                                          W, H, n, x, y, rw, rh, origins.data_ptr() if origins is not None else None,
-                                          out.data_ptr(), results.data_ptr())
-        self._check(rc, "dbde16_hip_decode_roi")
-        return out, results
+        return self._decode_roi("dbde16_hip_decode_roi", torch.int16, stream, stream_offset, stream_bytes, offsets, W,
+                                H, n, x, y, rw, rh, origins, out, results)
 
     def project16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x=0, y=0, rw=None, rh=None,
                   stats=("max", "min", "sum", "sumsq"), out=None, accumulate=False, results=None):
         """DBDE16 temporal projection: project's arguments and results, with max / min as int16 tensors holding the
         U16 bits (Projection.empty(..., pix=2)).  .to(torch.int32) & 0xFFFF gives their values."""
-        rw = W - x if rw is None else rw
-        rh = H - y if rh is None else rh
-        if out is None:
-            if accumulate:
-                raise ValueError("accumulate=True needs out= (the projection to continue)")
-            out = Projection.empty(rh, rw, stats, self.device, pix=2)
-        if results is None:
-            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-        rc = self.L.dbde16_hip_project(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
-                                       W, H, n, x, y, rw, rh, 1 if accumulate else 0, ptr(out.max), ptr(out.min),
-                                       ptr(out.sum), ptr(out.sumsq), ptr(out.count), ptr(results) if n > 0 else None)
-        self._check(rc, "dbde16_hip_project")
-        return out, results
+        return self._project("dbde16_hip_project", 2, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw,
+                             rh, stats, out, accumulate, results)
 
     # ---- host-pointer API: the reference's functions -------------------------------------
     def pack_frame(self, index, image, W, H):

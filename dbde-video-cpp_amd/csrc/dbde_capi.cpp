@@ -939,7 +939,7 @@ struct ProjectPlan {
 };
 // Frames per segment: a segment is cut only to fill the device (about 4 workgroups per CU) and never below
 // kProjMinFramesPerSegment frames, whose partials would cost more traffic than they save; never above the U32 bound.
-// pix: 1 = DBDE (dbde_hip_project), 2 = DBDE16 (dbde16_hip_project: kProj16Tiles tiles per workgroup, U16 / U64
+// pix: 1 = DBDE (dbde_hip_project), 2 = DBDE16 (dbde16_hip_project: kProjTilesOf(2) tiles per workgroup, U16 / U64
 // partials); the segment rule is the same for both.
 static constexpr uint32_t kProjMinFramesPerSegment = 32;
 static const char *plan_project(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
@@ -948,7 +948,7 @@ static const char *plan_project(int W, int H, int n_frames, int x0, int y0, int 
         return why;
     if (stats < 1u || stats > kProjAll) return "no statistic (or an unknown one) requested";
     pl.stats = stats;
-    const uint32_t tiles = pix == 2u ? kProj16Tiles : kProjTiles;
+    const uint32_t tiles = kProjTilesOf(pix);
     pl.pieces = (pl.roi.ntx + tiles - 1u) / tiles;
     pl.rows = pl.roi.nty;
     const uint64_t base = (uint64_t)pl.pieces * pl.rows, n = (uint64_t)n_frames;
@@ -1072,7 +1072,7 @@ static int project_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, con
     p.out_sumsq = d_sumsq;
     p.out_count = d_count;
     span_begin(ctx, 2);
-    HIP_TRY(ctx, pix == 2u ? launch_project16(p, stats, ctx->stream) : launch_project(p, stats, ctx->stream));
+    HIP_TRY(ctx, launch_project(p, stats, pix, ctx->stream));
     span_end(ctx);
     return DBDE_HIP_OK;
 }

@@ -15,14 +15,13 @@ namespace dbde {
 // Statistics bitmask (dbde_hip_project_plan's `stats`).
 constexpr uint32_t kProjMax = 1u, kProjMin = 2u, kProjSum = 4u, kProjSumSq = 8u, kProjAll = 15u;
 
-// One lane per tile row: a workgroup takes kProjTiles consecutive tiles of one window tile row, 8 lanes per tile.
+// A workgroup takes kProjTilesOf(pix) consecutive tiles of one window tile row: one lane per tile row (pix 1: 8 lanes
+// per tile) or per half tile row (pix 2, DBDE16: 16 lanes per tile).
 constexpr uint32_t kProjThreads = 256;
-constexpr uint32_t kProjTiles = kProjThreads / 8u;
+constexpr uint32_t kProjTilesOf(uint32_t pix) { return kProjThreads / (8u * pix); }
 // Frames one workgroup reduces into its U32 per-lane sums: 65,536 * 255^2 < 2^32, so the sums of squares are exact.
 // DBDE16 keeps the same bound through its U32 sums (65,536 * 65,535 < 2^32); its sums of squares are U64.
 constexpr uint32_t kProjMaxFramesPerSegment = 65536;
-// DBDE16: one lane per half tile row, 16 lanes per tile.
-constexpr uint32_t kProj16Tiles = kProjThreads / 16u;
 // Threads per workgroup of the combine kernel (one window pixel per thread).
 constexpr uint32_t kProjCombineThreads = 256;
 
@@ -38,24 +37,23 @@ struct ProjParams {
     uint32_t w;                     // tiles across the frame
     DecGeom geom;                   // the index's chunk geometry (roi_index_geometry)
     uint32_t tx0, ty0;              // the window's first tile column / row
-    uint32_t rows, pieces;          // window tile rows; workgroups (of kProjTiles tiles) across one
+    uint32_t rows, pieces;          // window tile rows; workgroups (of kProjTilesOf(pix) tiles) across one
     uint32_t segments, fps;         // frame segments; frames per segment (the last may hold fewer)
     int accumulate;                 // 1: combine into what the outputs hold
     // outputs (segments == 1: written by the projection kernel; otherwise by the combine kernel); NULL = not computed.
-    // The 16-bit kernels read out_max / out_min as U16 arrays.
+    // The DBDE16 kernels (pix 2) read out_max / out_min as U16 arrays.
     uint8_t *out_max, *out_min;
     uint64_t *out_sum, *out_sumsq, *out_count;
-    // per-segment partials [segments][rh * rw] (segments > 1 only), present for the requested statistics.  The 16-bit
+    // per-segment partials [segments][rh * rw] (segments > 1 only), present for the requested statistics.  The DBDE16
     // kernels read ws_max / ws_min as U16 arrays and ws_sumsq as a U64 array.
     uint8_t *ws_max, *ws_min;
     uint32_t *ws_sum, *ws_sumsq;
 };
 
-// The projection kernel (one instance per statistics set, `stats` = kProj* mask, 1..15): grid = pieces * rows *
-// segments workgroups of kProjThreads; with segments > 1 the combine kernel follows on the same stream.
-hipError_t launch_project(const ProjParams &p, uint32_t stats, hipStream_t s);
-// The same for DBDE16 frames (project16_kernel, kProj16Tiles tiles per workgroup, and its combine kernel).
-hipError_t launch_project16(const ProjParams &p, uint32_t stats, hipStream_t s);
+// The projection kernel (one instance per statistics set, `stats` = kProj* mask, 1..15, and pixel size, pix: 1 = DBDE,
+// 2 = DBDE16): grid = pieces * rows * segments workgroups of kProjThreads; with segments > 1 the combine kernel follows
+// on the same stream.
+hipError_t launch_project(const ProjParams &p, uint32_t stats, uint32_t pix, hipStream_t s);
 // Bytes of the per-segment partials of a window of `pixels` pixels (0 for one segment), laid out in the order max, min,
 // sum, sumsq, each 16-byte aligned.  pix: 1 = DBDE (U8 max / min, U32 sums), 2 = DBDE16 (U16 max / min, U32 sums, U64
 // sums of squares).

@@ -5,32 +5,34 @@
 // the window's tiles, the depth bytes in front of each window tile row's first tile within its chunk (fewer than 512:
 // roi_index_geometry), the chunk's payload offset from the decode index kernel, and the window tiles' payload.
 //
-// project_kernel<STATS>: one workgroup per (frame segment, window tile row, piece of kProjTiles = 32 tiles); one lane
-// per tile row (8 lanes per tile, 256 lanes).  Row r of a depth-d tile is bytes [r*d, r*d + d) of the tile's payload,
-// at most 8 bytes; the lane loads the three aligned dwords around it straight from global memory, cuts its 8 pixels
-// with dbde_bits.h's expand_row / add_bytes, and folds them into register accumulators:
-//   max / min  packed u16 pairs: even bytes masked into 16-bit lanes, odd bytes compared through the high byte of each
-//              16-bit lane (v_pk_max_u16 / v_pk_min_u16: 3 operations per statistic per 4 pixels, as tile_minmax);
-//   sum        one U32 per pixel;
-//   sumsq      one U32 per pixel: exact for kProjMaxFramesPerSegment = 65,536 frames (65,536 * 255^2 < 2^32).
+// project_kernel<STATS, PIX>: PIX = 1 for DBDE frames (U8 pixels and minima, depth 0..8, payload at 32 + 2T), PIX = 2
+// for DBDE16 frames (U16 pixels and minima, depth 0..16, payload at 32 + 3T).  One workgroup per (frame segment, window
+// tile row, piece of kProjTilesOf(PIX) tiles); 256 lanes, 8 * PIX lanes per tile:
+//   PIX = 1  one lane per tile row.  Row r of a depth-d tile is bytes [r*d, r*d + d) of the tile's payload, at most 8
+//            bytes; the lane loads the three aligned dwords around it straight from global memory and cuts its 8 pixels
+//            with dbde_bits.h's expand_row / add_bytes.
+//   PIX = 2  one lane per HALF tile row (lanes 2r and 2r + 1 of a tile).  Half h of row r is the 32d-bit integer at bit
+//            (8r + 4h) * d of the tile's payload: at most 8 bytes plus a nibble, so the lane loads the same three dwords
+//            and cuts its 4 pixels with dbde_device.h's cut_four16 (cut_row16's step).
+// The pixels fold into register accumulators:
+//   max / min  packed U16 pairs (v_pk_max_u16 / v_pk_min_u16).  PIX = 1: even bytes masked into 16-bit lanes, odd bytes
+//              compared through the high byte of each 16-bit lane (3 operations per statistic per 4 pixels, as
+//              tile_minmax);
+//   sum        one U32 per pixel: exact for kProjMaxFramesPerSegment = 65,536 frames (65,536 * 65,535 < 2^32);
+//   sumsq      PIX = 1: one U32 per pixel, exact for the same bound (65,536 * 255^2 < 2^32); PIX = 2: one U64 per pixel
+//              (one square alone can fill a U32), a 32-bit add with carry per frame.
 // STATS is a template parameter: an unrequested statistic has no accumulator and no instruction.
 // The workgroup walks its segment's frames in groups of kProjGroup.  While group k is accumulated, the payload loads of
 // group k + 1, the depth / minimum loads of group k + 2 and the per-frame words (frame_ok, offset, chunk offset) of
 // group k + 3 are in flight (one barrier per group, for the offsets scan).
 // At the end each lane writes its window pixels: into the outputs when the launch has one segment, else into the
-// per-segment partials, which project_combine_kernel (one thread per window pixel) folds into the outputs.
-//
-// project16_kernel<STATS>: DBDE16 frames (U16 pixels and minima, depth 0..16, payload at 32 + 3T), the same pipeline
-// with one lane per HALF tile row (16 lanes per tile, kProj16Tiles = 16 tiles per workgroup).  Half h of row r is the
-// 32d-bit integer at bit (8r + 4h) * d of the tile's payload: at most 8 bytes plus a nibble, so the lane loads the same
-// three aligned dwords as the 8-bit kernel and cuts its 4 pixels with dbde_device.h's cut_four16 (cut_row16's step):
-//   max / min  packed U16 pairs, v_pk_max_u16 / v_pk_min_u16 (2 VGPRs each);
-//   sum        one U32 per pixel: exact for kProjMaxFramesPerSegment frames (65,536 * 65,535 < 2^32);
-//   sumsq      one U64 per pixel (one square alone can fill a U32): a 32-bit add with carry per frame.
-// project16_combine_kernel folds its partials: U16 max / min, U32 sums, U64 sums of squares.  The 8-bit kernels keep
-// their own bodies: the same code as one inlined body behind two wrappers changes the 8-bit kernels' instruction
-// schedule.
+// per-segment partials, which project_combine_kernel<PIX> (one thread per window pixel) folds into the outputs.
+// The __global__ template is the body itself, with the pixel size's differences behind `if constexpr`: every instance
+// compiles to the instructions the two kernels had as separate bodies.
 #include "dbde_project_kernels.h"
+
+#include <type_traits>
+#include <utility>
 
 #include "dbde_bits.h"
 #include "dbde_device.h"
@@ -41,6 +43,10 @@ namespace {
 
 constexpr uint32_t kProjGroup = 4;                 // frames per pipeline step
 constexpr uint32_t kProjWaves = kProjThreads / 64u;
+
+// What the outputs and partials hold: U8 (PIX 1) or U16 (PIX 2) max / min, U32 or U64 partial sums of squares.
+template <uint32_t PIX> using ProjPix = typename std::conditional<PIX == 1u, uint8_t, uint16_t>::type;
+template <uint32_t PIX> using ProjSq = typename std::conditional<PIX == 1u, uint32_t, uint64_t>::type;
 
 __device__ __forceinline__ uint32_t readlane(uint32_t v, uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j); }
 
@@ -62,22 +68,26 @@ __device__ void write_count(const ProjParams &p) {
 
 }  // namespace
 
-template <uint32_t STATS>
+template <uint32_t STATS, uint32_t PIX>
 __global__ __launch_bounds__(kProjThreads) void project_kernel(ProjParams p) {
+    static_assert(PIX == 1u || PIX == 2u, "U8 or U16 pixels");
+    typedef ProjPix<PIX> Pix;
     constexpr bool kMax = (STATS & kProjMax) != 0u, kMin = (STATS & kProjMin) != 0u;
     constexpr bool kSum = (STATS & kProjSum) != 0u, kSq = (STATS & kProjSumSq) != 0u;
-    constexpr uint32_t G = kProjGroup;
+    constexpr uint32_t G = kProjGroup, kTiles = kProjTilesOf(PIX), kDmax = 8u * PIX, kNpx = 8u / PIX;   // kNpx: pixels per lane
+    constexpr uint32_t kPixMask = PIX == 1u ? 0xFFu : 0xFFFFu;
     __shared__ uint32_t s_wsum[2][G][2][kProjWaves];   // per group of frames (double-buffered): wave depth totals, sums in front
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t t = tid >> 3, r = tid & 7u;       // tile of the piece, row of the tile
+    // tile of the piece, row of the tile, half of the row (PIX 2)
+    const uint32_t t = PIX == 1u ? tid >> 3 : tid >> 4, r = PIX == 1u ? tid & 7u : (tid >> 1) & 7u, hh = PIX == 1u ? 0u : tid & 1u;
     const uint32_t per_seg = p.rows * p.pieces;
     const uint32_t seg = blockIdx.x / per_seg;
     const uint32_t rem = blockIdx.x - seg * per_seg;
     const uint32_t br = rem / p.pieces, pc = rem - br * p.pieces;
-    const uint32_t ty = p.ty0 + br, txp = p.tx0 + pc * kProjTiles;
+    const uint32_t ty = p.ty0 + br, txp = p.tx0 + pc * kTiles;
     const uint32_t tx_b = (uint32_t)(p.x0 + p.rw - 1) >> 3;
-    const uint32_t nt = tx_b + 1u - txp < kProjTiles ? tx_b + 1u - txp : kProjTiles;
+    const uint32_t nt = tx_b + 1u - txp < kTiles ? tx_b + 1u - txp : kTiles;
     const bool has_tile = t < nt;
     const uint32_t pos0 = ty * p.w + txp;              // the piece's first tile (stream order)
     const uint32_t c = dec_chunk_of(p.geom, pos0), cb = dec_chunk_begin(p.geom, c);
@@ -88,11 +98,12 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(ProjParams p) {
     const uint32_t f_end = f_last < p.n_frames ? (uint32_t)f_last : p.n_frames;
     const uint8_t *const end = p.stream + p.stream_bytes;
 
-    // ---- accumulators ----
-    uint32_t mxe[2] = {0u, 0u}, mxo[2] = {0u, 0u};                        // max: even bytes / odd bytes, pixels 0-3, 4-7
-    uint32_t mne[2] = {~0u, ~0u}, mno[2] = {~0u, ~0u};                    // min
-    uint32_t sum[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    uint32_t sq[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    // ---- accumulators: this lane's kNpx pixels ----
+    // max / min: PIX 1 even bytes (mx, mn) and odd bytes (mxo, mno) of pixels 0-3, 4-7; PIX 2 U16 pairs (mx, mn)
+    uint32_t mx[2] = {0u, 0u}, mxo[2] = {0u, 0u};
+    uint32_t mn[2] = {~0u, ~0u}, mno[2] = {~0u, ~0u};
+    uint32_t sum[kNpx] = {};
+    ProjSq<PIX> sq[kNpx] = {};
 
     // ---- the per-frame words of a group, one group ahead of their use: lane k < G holds frame g0 + k ----
     struct Words {
@@ -114,288 +125,23 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(ProjParams p) {
         uint32_t ok[G];            // uniform: frame accepted (and inside the segment)
         uint32_t base[G];          // uniform: payload words of the frame in front of the piece's chunk
         const uint8_t *fb[G];      // uniform: the frame
-        uint32_t d8[G], m8[G];     // depth, minimum of this lane's tile (raw loads: combined only where they are used)
+        uint32_t d8[G], ml[G], mh[G];   // depth, minimum (PIX 2: its low / high byte) of this lane's tile (raw loads)
         uint32_t pre[G];           // this lane's dword of the depth bytes in front of the piece (masked where used)
     };
     struct Pay {
-        uint32_t a0[G], a1[G], a2[G];   // the aligned dwords around this lane's tile row
-        uint32_t dms[G];                // depth | minimum << 8 | byte shift << 16
+        uint32_t a0[G], a1[G], a2[G];   // the aligned dwords around this lane's (half) row
+        uint32_t dms[G];                // PIX 1: depth | minimum << 8 | byte shift << 16; PIX 2: depth | shift << 8 | minimum << 16
     };
 
     // pre: depth bytes [cb, pos0) of the frame, as aligned dwords, lane tid < ndw holding dword tid.  Every load is
     // unconditional inside an accepted frame (lanes without a tile read tile 0, lanes past ndw dword 0) and nothing
     // consumes a loaded value here, so that the loads stay in flight while the group in front is accumulated.
+    // The U16 minima start at 28 + T, possibly at an odd address: read byte by byte.
     auto issue_meta = [&](Meta &m, const Words &wd) __attribute__((always_inline)) {
 #pragma unroll
         for (uint32_t k = 0; k < G; k++) {
-            m.ok[k] = 0u; m.base[k] = 0u; m.fb[k] = p.stream; m.d8[k] = 0u; m.m8[k] = 0u; m.pre[k] = 0u;
-            {
-                m.ok[k] = readlane(wd.ok, k);   // 0 past the segment
-                if (m.ok[k]) {
-                    const uint64_t fo = (uint64_t)readlane((uint32_t)wd.fo, k) | ((uint64_t)readlane((uint32_t)(wd.fo >> 32), k) << 32);
-                    m.fb[k] = p.stream + fo;   // validated: the whole frame lies inside stream_bytes
-                    m.base[k] = readlane(wd.base, k);
-                    const uint8_t *darr = m.fb[k] + 24;
-                    const uint32_t tt = has_tile ? t : 0u;
-                    m.d8[k] = darr[pos0 + tt];
-                    m.m8[k] = darr[4u + p.T + pos0 + tt];
-                    const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(darr + cb) & 3u), ndw = (head + npre + 3u) >> 2;
-                    const uint8_t *a_lo = darr + cb - head;   // (pointer arithmetic: the load stays a global one)
-                    m.pre[k] = *reinterpret_cast<const uint32_t *>(a_lo + 4u * (tid < ndw ? tid : 0u));   // inside the frame
-                }
-            }
-        }
-    };
-    // the mask of the depth bytes [cb, pos0) in this lane's pre dword of frame fb
-    auto pre_keep = [&](const uint8_t *fb) __attribute__((always_inline)) -> uint32_t {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(fb + 24 + cb);
-        const uint32_t head = (uint32_t)(a & 3u), ndw = (head + npre + 3u) >> 2;
-        if (tid >= ndw) return 0u;
-        const uint32_t lo = 4u * tid < head ? head - 4u * tid : 0u;   // bytes in front of cb
-        const uint32_t hi = head + npre - 4u * tid;                   // bytes before pos0
-        return (hi >= 4u ? ~0u : (1u << (8u * hi)) - 1u) & ~((1u << (8u * lo)) - 1u);
-    };
-
-    // the group's tile offsets (one barrier) and its payload loads
-    uint32_t buf = 0;
-    auto issue_payload = [&](const Meta &m, Pay &q) __attribute__((always_inline)) {
-        uint32_t any = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < G; k++) any |= m.ok[k];
-        if (!any) {
-#pragma unroll
-            for (uint32_t k = 0; k < G; k++) { q.a0[k] = q.a1[k] = q.a2[k] = 0u; q.dms[k] = 0u; }
-            return;
-        }
-        uint32_t incl[G];
-#pragma unroll
-        for (uint32_t k = 0; k < G; k++) {
-            const uint32_t d = has_tile ? (m.d8[k] > 8u ? 8u : m.d8[k]) : 0u;   // (a validated frame has none above 8)
-            incl[k] = wave_scan_incl(r == 0u ? d : 0u);
-            const uint32_t pw = wave_sum(__builtin_amdgcn_sad_u8(m.pre[k] & pre_keep(m.fb[k]), 0u, 0u));
-            if (lane == 63u) s_wsum[buf][k][0][wave] = incl[k];
-            if (lane == 0u) s_wsum[buf][k][1][wave] = pw;
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t k = 0; k < G; k++) {
-            uint32_t wbase = 0, PRE = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < kProjWaves; w++) {
-                wbase += w < wave ? s_wsum[buf][k][0][w] : 0u;
-                PRE += s_wsum[buf][k][1][w];
-            }
-            const uint32_t d = has_tile ? (m.d8[k] > 8u ? 8u : m.d8[k]) : 0u;
-            const uint32_t woff = m.base[k] + PRE + wbase + incl[k] - d;   // payload words in front of the tile
-            const uint8_t *src = m.fb[k] + 32 + 2ull * p.T + 8ull * woff + r * d;
-            const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 3u);
-            const uint8_t *q8 = src - sh;   // (pointer arithmetic: the loads stay global ones)
-            const bool need = m.ok[k] && has_tile && d != 0u, tail = q8 + 12 > end;
-            uint32_t w0 = 0u, w1 = 0u, w2 = 0u;
-            if (need && !tail) {
-                const uint32_t *q32 = reinterpret_cast<const uint32_t *>(q8);
-                w0 = q32[0]; w1 = q32[1]; w2 = q32[2];
-            }
-            if (need && tail) {   // the stream's last bytes: only those in front of stream_bytes (rare: its waits cost nothing)
-                for (uint32_t b = sh; b < sh + d; b++) {
-                    if (q8 + b >= end) break;
-                    const uint32_t v = (uint32_t)q8[b] << (8u * (b & 3u));
-                    if (b < 4u) w0 |= v; else if (b < 8u) w1 |= v; else w2 |= v;
-                }
-            }
-            q.a0[k] = w0; q.a1[k] = w1; q.a2[k] = w2;
-            q.dms[k] = d | (m.m8[k] << 8) | (sh << 16);
-        }
-        buf ^= 1u;
-    };
-
-    auto accumulate = [&](const Meta &m, const Pay &q) __attribute__((always_inline)) {
-#pragma unroll
-        for (uint32_t k = 0; k < G; k++) {
-            if (!m.ok[k]) continue;   // rejected (or past the segment): contributes nothing
-            const uint32_t d = q.dms[k] & 0xFFu, sh = q.dms[k] >> 16;
-            const uint32_t mm = ((q.dms[k] >> 8) & 0xFFu) * 0x01010101u;
-            const uint64_t bits = (uint64_t)__builtin_amdgcn_alignbyte(q.a1[k], q.a0[k], sh) |
-                                  ((uint64_t)__builtin_amdgcn_alignbyte(q.a2[k], q.a1[k], sh) << 32);
-            uint32_t px[2];
-            expand_row(bits, d, px[0], px[1]);
-            px[0] = add_bytes(px[0], mm);
-            px[1] = add_bytes(px[1], mm);
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const uint32_t e = px[h] & 0x00FF00FFu;
-                if (kMax) { mxe[h] = pk_max_u16(mxe[h], e); mxo[h] = pk_max_u16(mxo[h], px[h]); }
-                if (kMin) { mne[h] = pk_min_u16(mne[h], e); mno[h] = pk_min_u16(mno[h], px[h]); }
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const uint32_t v = (px[h] >> (8 * i)) & 0xFFu;
-                    if (kSum) sum[4 * h + i] += v;
-                    if (kSq) sq[4 * h + i] += v * v;
-                }
-            }
-        }
-    };
-
-    // ---- the pipeline: accumulate group k while group k + 1's payload and group k + 2's depth bytes load ----
-    Meta m_cur, m_nxt, m_nn;
-    Pay q_cur, q_nxt;
-    Words w_nn;
-    issue_words(w_nn, f_begin);
-    issue_meta(m_cur, w_nn);
-    issue_payload(m_cur, q_cur);
-    issue_words(w_nn, f_begin + G);
-    issue_meta(m_nxt, w_nn);
-    issue_words(w_nn, f_begin + 2u * G);
-    for (uint32_t g0 = f_begin; g0 < f_end; g0 += G) {
-        issue_payload(m_nxt, q_nxt);
-        issue_meta(m_nn, w_nn);
-        issue_words(w_nn, g0 + 3u * G);
-        accumulate(m_cur, q_cur);
-        m_cur = m_nxt;
-        q_cur = q_nxt;
-        m_nxt = m_nn;
-    }
-
-    // ---- the window's pixels of this lane -> the outputs, or this segment's partials ----
-    const int yy = 8 * (int)ty + (int)r;
-    if (has_tile && yy >= p.y0 && yy < p.y0 + p.rh) {
-        const uint64_t P = (uint64_t)p.rw * (uint64_t)p.rh;
-        const uint64_t row0 = (uint64_t)(yy - p.y0) * (uint64_t)p.rw;
-        const bool direct = p.segments == 1u;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const int xx = 8 * (int)(txp + t) + i;
-            if (xx < p.x0 || xx >= p.x0 + p.rw) continue;
-            const uint64_t o = row0 + (uint64_t)(xx - p.x0);
-            const int h = i >> 2, sb = 8 * (i & 3);
-            if (kMax) {
-                uint32_t v = ((i & 1) ? mxo[h] : mxe[h]) >> sb & 0xFFu;
-                if (direct) {
-                    if (p.accumulate) { const uint32_t o8 = p.out_max[o]; v = v > o8 ? v : o8; }
-                    p.out_max[o] = (uint8_t)v;
-                } else {
-                    p.ws_max[(uint64_t)seg * P + o] = (uint8_t)v;
-                }
-            }
-            if (kMin) {
-                uint32_t v = ((i & 1) ? mno[h] : mne[h]) >> sb & 0xFFu;
-                if (direct) {
-                    if (p.accumulate) { const uint32_t o8 = p.out_min[o]; v = v < o8 ? v : o8; }
-                    p.out_min[o] = (uint8_t)v;
-                } else {
-                    p.ws_min[(uint64_t)seg * P + o] = (uint8_t)v;
-                }
-            }
-            if (kSum) {
-                if (direct) p.out_sum[o] = (p.accumulate ? p.out_sum[o] : 0ull) + sum[i];
-                else p.ws_sum[(uint64_t)seg * P + o] = sum[i];
-            }
-            if (kSq) {
-                if (direct) p.out_sumsq[o] = (p.accumulate ? p.out_sumsq[o] : 0ull) + sq[i];
-                else p.ws_sumsq[(uint64_t)seg * P + o] = sq[i];
-            }
-        }
-    }
-    if (p.segments == 1u && blockIdx.x == 0u) write_count(p);
-}
-
-// Segments > 1: the partials of every segment (and the outputs' values when accumulating) -> the outputs.  One thread
-// per window pixel; the partials are [segments][rw * rh], so each segment's read is coalesced.
-__global__ __launch_bounds__(kProjCombineThreads) void project_combine_kernel(ProjParams p) {
-    const uint64_t P = (uint64_t)p.rw * (uint64_t)p.rh;
-    const uint64_t i = (uint64_t)blockIdx.x * kProjCombineThreads + threadIdx.x;
-    if (i < P) {
-        if (p.out_max) {
-            uint32_t v = p.accumulate ? p.out_max[i] : 0u;
-            for (uint32_t s = 0; s < p.segments; s++) { const uint32_t w = p.ws_max[(uint64_t)s * P + i]; v = w > v ? w : v; }
-            p.out_max[i] = (uint8_t)v;
-        }
-        if (p.out_min) {
-            uint32_t v = p.accumulate ? p.out_min[i] : 255u;
-            for (uint32_t s = 0; s < p.segments; s++) { const uint32_t w = p.ws_min[(uint64_t)s * P + i]; v = w < v ? w : v; }
-            p.out_min[i] = (uint8_t)v;
-        }
-        if (p.out_sum) {
-            uint64_t v = p.accumulate ? p.out_sum[i] : 0ull;
-            for (uint32_t s = 0; s < p.segments; s++) v += p.ws_sum[(uint64_t)s * P + i];
-            p.out_sum[i] = v;
-        }
-        if (p.out_sumsq) {
-            uint64_t v = p.accumulate ? p.out_sumsq[i] : 0ull;
-            for (uint32_t s = 0; s < p.segments; s++) v += p.ws_sumsq[(uint64_t)s * P + i];
-            p.out_sumsq[i] = v;
-        }
-    }
-    if (blockIdx.x == 0u) write_count(p);
-}
-
-// ---- DBDE16 --------------------------------------------------------------------------------------------------------
-// project_kernel's pipeline (words -> meta -> payload -> accumulate, one barrier per group) on DBDE16 frames, one lane
-// per half tile row: lanes 2r and 2r + 1 of a tile hold the halves of row r.
-template <uint32_t STATS>
-__global__ __launch_bounds__(kProjThreads) void project16_kernel(ProjParams p) {
-    constexpr bool kMax = (STATS & kProjMax) != 0u, kMin = (STATS & kProjMin) != 0u;
-    constexpr bool kSum = (STATS & kProjSum) != 0u, kSq = (STATS & kProjSumSq) != 0u;
-    constexpr uint32_t G = kProjGroup;
-    __shared__ uint32_t s_wsum[2][G][2][kProjWaves];   // per group of frames (double-buffered): wave depth totals, sums in front
-
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t t = tid >> 4, r = (tid >> 1) & 7u, hh = tid & 1u;   // tile of the piece, row of the tile, half of the row
-    const uint32_t per_seg = p.rows * p.pieces;
-    const uint32_t seg = blockIdx.x / per_seg;
-    const uint32_t rem = blockIdx.x - seg * per_seg;
-    const uint32_t br = rem / p.pieces, pc = rem - br * p.pieces;
-    const uint32_t ty = p.ty0 + br, txp = p.tx0 + pc * kProj16Tiles;
-    const uint32_t tx_b = (uint32_t)(p.x0 + p.rw - 1) >> 3;
-    const uint32_t nt = tx_b + 1u - txp < kProj16Tiles ? tx_b + 1u - txp : kProj16Tiles;
-    const bool has_tile = t < nt;
-    const uint32_t pos0 = ty * p.w + txp;              // the piece's first tile (stream order)
-    const uint32_t c = dec_chunk_of(p.geom, pos0), cb = dec_chunk_begin(p.geom, c);
-    const uint32_t npre = pos0 - cb;                   // < 512 (roi_index_geometry)
-    const uint32_t cstride = p.geom.cpf + 1u;
-    const uint32_t f_begin = seg * p.fps;
-    const uint64_t f_last = (uint64_t)f_begin + p.fps;
-    const uint32_t f_end = f_last < p.n_frames ? (uint32_t)f_last : p.n_frames;
-    const uint8_t *const end = p.stream + p.stream_bytes;
-
-    // ---- accumulators: pixels 0-3 of this lane's half row ----
-    uint32_t mx[2] = {0u, 0u}, mn[2] = {~0u, ~0u};   // packed U16 pairs: pixels 0, 1 and 2, 3
-    uint32_t sum[4] = {0u, 0u, 0u, 0u};
-    uint64_t sq[4] = {0ull, 0ull, 0ull, 0ull};
-
-    // ---- the per-frame words of a group, one group ahead of their use: lane k < G holds frame g0 + k ----
-    struct Words {
-        uint32_t ok, base;
-        uint64_t fo;
-    };
-    auto issue_words = [&](Words &wd, uint32_t g0) __attribute__((always_inline)) {
-        const uint32_t g = g0 + (lane < G ? lane : 0u);
-        wd.ok = 0u; wd.base = 0u; wd.fo = 0u;
-        if (lane < G && g < f_end) {
-            wd.ok = p.frame_ok[g];
-            wd.fo = p.frame_offsets[g];
-            wd.base = p.chunk_off[(size_t)g * cstride + c];
-        }
-    };
-
-    // ---- one group of frames in flight ----
-    struct Meta {
-        uint32_t ok[G];            // uniform: frame accepted (and inside the segment)
-        uint32_t base[G];          // uniform: payload words of the frame in front of the piece's chunk
-        const uint8_t *fb[G];      // uniform: the frame
-        uint32_t d8[G], ml[G], mh[G];   // depth, minimum's low / high byte of this lane's tile (raw loads)
-        uint32_t pre[G];           // this lane's dword of the depth bytes in front of the piece (masked where used)
-    };
-    struct Pay {
-        uint32_t a0[G], a1[G], a2[G];   // the aligned dwords around this lane's half row
-        uint32_t dms[G];                // depth | byte shift << 8 | minimum << 16
-    };
-
-    // as project_kernel's issue_meta; the U16 minima start at 28 + T, possibly at an odd address: read byte by byte
-    auto issue_meta = [&](Meta &m, const Words &wd) __attribute__((always_inline)) {
-#pragma unroll
-        for (uint32_t k = 0; k < G; k++) {
-            m.ok[k] = 0u; m.base[k] = 0u; m.fb[k] = p.stream; m.d8[k] = 0u; m.ml[k] = 0u; m.mh[k] = 0u; m.pre[k] = 0u;
+            m.ok[k] = 0u; m.base[k] = 0u; m.fb[k] = p.stream; m.d8[k] = 0u; m.ml[k] = 0u; m.pre[k] = 0u;
+            if constexpr (PIX == 2u) m.mh[k] = 0u;
             m.ok[k] = readlane(wd.ok, k);   // 0 past the segment
             if (m.ok[k]) {
                 const uint64_t fo = (uint64_t)readlane((uint32_t)wd.fo, k) | ((uint64_t)readlane((uint32_t)(wd.fo >> 32), k) << 32);
@@ -404,8 +150,12 @@ __global__ __launch_bounds__(kProjThreads) void project16_kernel(ProjParams p) {
                 const uint8_t *darr = m.fb[k] + 24;
                 const uint32_t tt = has_tile ? t : 0u;
                 m.d8[k] = darr[pos0 + tt];
-                m.ml[k] = darr[4u + p.T + 2u * (pos0 + tt)];
-                m.mh[k] = darr[5u + p.T + 2u * (pos0 + tt)];
+                if constexpr (PIX == 1u) {
+                    m.ml[k] = darr[4u + p.T + pos0 + tt];
+                } else {
+                    m.ml[k] = darr[4u + p.T + 2u * (pos0 + tt)];
+                    m.mh[k] = darr[5u + p.T + 2u * (pos0 + tt)];
+                }
                 const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(darr + cb) & 3u), ndw = (head + npre + 3u) >> 2;
                 const uint8_t *a_lo = darr + cb - head;   // (pointer arithmetic: the load stays a global one)
                 m.pre[k] = *reinterpret_cast<const uint32_t *>(a_lo + 4u * (tid < ndw ? tid : 0u));   // inside the frame
@@ -436,8 +186,8 @@ __global__ __launch_bounds__(kProjThreads) void project16_kernel(ProjParams p) {
         uint32_t incl[G];
 #pragma unroll
         for (uint32_t k = 0; k < G; k++) {
-            const uint32_t d = has_tile ? (m.d8[k] > 16u ? 16u : m.d8[k]) : 0u;   // (a validated frame has none above 16)
-            incl[k] = wave_scan_incl((tid & 15u) == 0u ? d : 0u);
+            const uint32_t d = has_tile ? (m.d8[k] > kDmax ? kDmax : m.d8[k]) : 0u;   // (a validated frame has none above)
+            incl[k] = wave_scan_incl((PIX == 1u ? r == 0u : (tid & 15u) == 0u) ? d : 0u);   // the tile's first lane
             const uint32_t pw = wave_sum(__builtin_amdgcn_sad_u8(m.pre[k] & pre_keep(m.fb[k]), 0u, 0u));
             if (lane == 63u) s_wsum[buf][k][0][wave] = incl[k];
             if (lane == 0u) s_wsum[buf][k][1][wave] = pw;
@@ -451,10 +201,10 @@ __global__ __launch_bounds__(kProjThreads) void project16_kernel(ProjParams p) {
                 wbase += w < wave ? s_wsum[buf][k][0][w] : 0u;
                 PRE += s_wsum[buf][k][1][w];
             }
-            const uint32_t d = has_tile ? (m.d8[k] > 16u ? 16u : m.d8[k]) : 0u;
+            const uint32_t d = has_tile ? (m.d8[k] > kDmax ? kDmax : m.d8[k]) : 0u;
             const uint32_t woff = m.base[k] + PRE + wbase + incl[k] - d;   // payload words in front of the tile
-            // the half row: byte r * d + h * (d / 2), a nibble further when d is odd; 4d bits (+ 4) <= 8 bytes
-            const uint8_t *src = m.fb[k] + 32 + 3ull * p.T + 8ull * woff + r * d + hh * (d >> 1);
+            // PIX 2, the half row: byte r * d + h * (d / 2), a nibble further when d is odd; 4d bits (+ 4) <= 8 bytes
+            const uint8_t *src = m.fb[k] + 32 + (PIX + 1ull) * p.T + 8ull * woff + r * d + hh * (d >> 1);
             const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(src) & 3u);
             const uint8_t *q8 = src - sh;   // (pointer arithmetic: the loads stay global ones)
             const bool need = m.ok[k] && has_tile && d != 0u, tail = q8 + 12 > end;
@@ -464,7 +214,7 @@ __global__ __launch_bounds__(kProjThreads) void project16_kernel(ProjParams p) {
                 w0 = q32[0]; w1 = q32[1]; w2 = q32[2];
             }
             if (need && tail) {   // the stream's last bytes: only those in front of stream_bytes (rare: its waits cost nothing)
-                const uint32_t nb = (4u * d + 4u * hh * (d & 1u) + 7u) >> 3;
+                const uint32_t nb = PIX == 1u ? d : (4u * d + 4u * hh * (d & 1u) + 7u) >> 3;
                 for (uint32_t b = sh; b < sh + nb; b++) {
                     if (q8 + b >= end) break;
                     const uint32_t v = (uint32_t)q8[b] << (8u * (b & 3u));
@@ -472,7 +222,8 @@ __global__ __launch_bounds__(kProjThreads) void project16_kernel(ProjParams p) {
                 }
             }
             q.a0[k] = w0; q.a1[k] = w1; q.a2[k] = w2;
-            q.dms[k] = d | (sh << 8) | (m.ml[k] << 16) | (m.mh[k] << 24);
+            if constexpr (PIX == 1u) q.dms[k] = d | (m.ml[k] << 8) | (sh << 16);
+            else q.dms[k] = d | (sh << 8) | (m.ml[k] << 16) | (m.mh[k] << 24);
         }
         buf ^= 1u;
     };
@@ -481,22 +232,45 @@ __global__ __launch_bounds__(kProjThreads) void project16_kernel(ProjParams p) {
 #pragma unroll
         for (uint32_t k = 0; k < G; k++) {
             if (!m.ok[k]) continue;   // rejected (or past the segment): contributes nothing
-            const uint32_t d = q.dms[k] & 0xFFu, sh = (q.dms[k] >> 8) & 0xFFu, so = 4u * hh * (d & 1u);
-            const uint32_t m32 = d >= 16u ? 0xFFFFu : (1u << d) - 1u, mn2 = (q.dms[k] >> 16) * 0x00010001u;
-            const bool c2 = 2u * d >= 32u, c3 = 3u * d >= 32u;
-            const uint32_t x0 = __builtin_amdgcn_alignbyte(q.a1[k], q.a0[k], sh);
-            const uint32_t x1 = __builtin_amdgcn_alignbyte(q.a2[k], q.a1[k], sh);
-            uint32_t e[2];
-            cut_four16(__builtin_amdgcn_alignbit(x1, x0, so), x1 >> so, d, m32, mn2, c2, c3, e[0], e[1]);
+            if constexpr (PIX == 1u) {
+                const uint32_t d = q.dms[k] & 0xFFu, sh = q.dms[k] >> 16;
+                const uint32_t mm = ((q.dms[k] >> 8) & 0xFFu) * 0x01010101u;
+                const uint64_t bits = (uint64_t)__builtin_amdgcn_alignbyte(q.a1[k], q.a0[k], sh) |
+                                      ((uint64_t)__builtin_amdgcn_alignbyte(q.a2[k], q.a1[k], sh) << 32);
+                uint32_t px[2];
+                expand_row(bits, d, px[0], px[1]);
+                px[0] = add_bytes(px[0], mm);
+                px[1] = add_bytes(px[1], mm);
 #pragma unroll
-            for (int j = 0; j < 2; j++) {
-                if (kMax) mx[j] = pk_max_u16(mx[j], e[j]);
-                if (kMin) mn[j] = pk_min_u16(mn[j], e[j]);
+                for (int h = 0; h < 2; h++) {
+                    const uint32_t e = px[h] & 0x00FF00FFu;
+                    if (kMax) { mx[h] = pk_max_u16(mx[h], e); mxo[h] = pk_max_u16(mxo[h], px[h]); }
+                    if (kMin) { mn[h] = pk_min_u16(mn[h], e); mno[h] = pk_min_u16(mno[h], px[h]); }
 #pragma unroll
-                for (int i = 0; i < 2; i++) {
-                    const uint32_t v = (e[j] >> (16 * i)) & 0xFFFFu;
-                    if (kSum) sum[2 * j + i] += v;
-                    if (kSq) sq[2 * j + i] += (uint64_t)(v * v);   // v * v < 2^32; the add carries into the high dword
+                    for (int i = 0; i < 4; i++) {
+                        const uint32_t v = (px[h] >> (8 * i)) & 0xFFu;
+                        if (kSum) sum[4 * h + i] += v;
+                        if (kSq) sq[4 * h + i] += v * v;
+                    }
+                }
+            } else {
+                const uint32_t d = q.dms[k] & 0xFFu, sh = (q.dms[k] >> 8) & 0xFFu, so = 4u * hh * (d & 1u);
+                const uint32_t m32 = d >= 16u ? 0xFFFFu : (1u << d) - 1u, mn2 = (q.dms[k] >> 16) * 0x00010001u;
+                const bool c2 = 2u * d >= 32u, c3 = 3u * d >= 32u;
+                const uint32_t x0 = __builtin_amdgcn_alignbyte(q.a1[k], q.a0[k], sh);
+                const uint32_t x1 = __builtin_amdgcn_alignbyte(q.a2[k], q.a1[k], sh);
+                uint32_t e[2];
+                cut_four16(__builtin_amdgcn_alignbit(x1, x0, so), x1 >> so, d, m32, mn2, c2, c3, e[0], e[1]);
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    if (kMax) mx[j] = pk_max_u16(mx[j], e[j]);
+                    if (kMin) mn[j] = pk_min_u16(mn[j], e[j]);
+#pragma unroll
+                    for (int i = 0; i < 2; i++) {
+                        const uint32_t v = (e[j] >> (16 * i)) & 0xFFFFu;
+                        if (kSum) sum[2 * j + i] += v;
+                        if (kSq) sq[2 * j + i] += (uint64_t)(v * v);   // v * v < 2^32; the add carries into the high dword
+                    }
                 }
             }
         }
@@ -523,68 +297,73 @@ __global__ __launch_bounds__(kProjThreads) void project16_kernel(ProjParams p) {
     }
 
     // ---- the window's pixels of this lane -> the outputs, or this segment's partials ----
-    uint16_t *const out_max = reinterpret_cast<uint16_t *>(p.out_max), *const out_min = reinterpret_cast<uint16_t *>(p.out_min);
+    Pix *const out_max = reinterpret_cast<Pix *>(p.out_max), *const out_min = reinterpret_cast<Pix *>(p.out_min);
     const int yy = 8 * (int)ty + (int)r;
     if (has_tile && yy >= p.y0 && yy < p.y0 + p.rh) {
         const uint64_t P = (uint64_t)p.rw * (uint64_t)p.rh;
         const uint64_t row0 = (uint64_t)(yy - p.y0) * (uint64_t)p.rw;
         const bool direct = p.segments == 1u;
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
+        for (int i = 0; i < (int)kNpx; i++) {
             const int xx = 8 * (int)(txp + t) + 4 * (int)hh + i;
             if (xx < p.x0 || xx >= p.x0 + p.rw) continue;
             const uint64_t o = row0 + (uint64_t)(xx - p.x0);
+            // the partials' index: PIX 2 forms it once, PIX 1 at each store (listing of the separate bodies)
             const uint64_t ow = (uint64_t)seg * P + o;
-            const int sb = 16 * (i & 1);
+            // pixel i of a packed max / min: PIX 1 byte i & 3 of the even / odd accumulator, PIX 2 U16 i & 1 of a pair
+            const int h = PIX == 1u ? i >> 2 : i >> 1, sb = PIX == 1u ? 8 * (i & 3) : 16 * (i & 1);
             if (kMax) {
-                uint32_t v = mx[i >> 1] >> sb & 0xFFFFu;
+                uint32_t v = ((PIX == 1u && (i & 1)) ? mxo[h] : mx[h]) >> sb & kPixMask;
                 if (direct) {
-                    if (p.accumulate) { const uint32_t o16 = out_max[o]; v = v > o16 ? v : o16; }
-                    out_max[o] = (uint16_t)v;
+                    if (p.accumulate) { const uint32_t ov = out_max[o]; v = v > ov ? v : ov; }
+                    out_max[o] = (Pix)v;
                 } else {
-                    reinterpret_cast<uint16_t *>(p.ws_max)[ow] = (uint16_t)v;
+                    reinterpret_cast<Pix *>(p.ws_max)[PIX == 1u ? (uint64_t)seg * P + o : ow] = (Pix)v;
                 }
             }
             if (kMin) {
-                uint32_t v = mn[i >> 1] >> sb & 0xFFFFu;
+                uint32_t v = ((PIX == 1u && (i & 1)) ? mno[h] : mn[h]) >> sb & kPixMask;
                 if (direct) {
-                    if (p.accumulate) { const uint32_t o16 = out_min[o]; v = v < o16 ? v : o16; }
-                    out_min[o] = (uint16_t)v;
+                    if (p.accumulate) { const uint32_t ov = out_min[o]; v = v < ov ? v : ov; }
+                    out_min[o] = (Pix)v;
                 } else {
-                    reinterpret_cast<uint16_t *>(p.ws_min)[ow] = (uint16_t)v;
+                    reinterpret_cast<Pix *>(p.ws_min)[PIX == 1u ? (uint64_t)seg * P + o : ow] = (Pix)v;
                 }
             }
             if (kSum) {
                 if (direct) p.out_sum[o] = (p.accumulate ? p.out_sum[o] : 0ull) + sum[i];
-                else p.ws_sum[ow] = sum[i];
+                else p.ws_sum[PIX == 1u ? (uint64_t)seg * P + o : ow] = sum[i];
             }
             if (kSq) {
                 if (direct) p.out_sumsq[o] = (p.accumulate ? p.out_sumsq[o] : 0ull) + sq[i];
-                else reinterpret_cast<uint64_t *>(p.ws_sumsq)[ow] = sq[i];
+                else reinterpret_cast<ProjSq<PIX> *>(p.ws_sumsq)[PIX == 1u ? (uint64_t)seg * P + o : ow] = sq[i];
             }
         }
     }
     if (p.segments == 1u && blockIdx.x == 0u) write_count(p);
 }
 
-// project_combine_kernel for project16_kernel's partials (U16 max / min, U32 sums, U64 sums of squares).
-__global__ __launch_bounds__(kProjCombineThreads) void project16_combine_kernel(ProjParams p) {
+// Segments > 1: the partials of every segment (and the outputs' values when accumulating) -> the outputs.  One thread
+// per window pixel; the partials are [segments][rw * rh], so each segment's read is coalesced.
+template <uint32_t PIX>
+__global__ __launch_bounds__(kProjCombineThreads) void project_combine_kernel(ProjParams p) {
+    typedef ProjPix<PIX> Pix;
     const uint64_t P = (uint64_t)p.rw * (uint64_t)p.rh;
     const uint64_t i = (uint64_t)blockIdx.x * kProjCombineThreads + threadIdx.x;
     if (i < P) {
         if (p.out_max) {
-            uint16_t *const out = reinterpret_cast<uint16_t *>(p.out_max);
-            const uint16_t *const ws = reinterpret_cast<const uint16_t *>(p.ws_max);
+            Pix *const out = reinterpret_cast<Pix *>(p.out_max);
+            const Pix *const ws = reinterpret_cast<const Pix *>(p.ws_max);
             uint32_t v = p.accumulate ? out[i] : 0u;
             for (uint32_t s = 0; s < p.segments; s++) { const uint32_t w = ws[(uint64_t)s * P + i]; v = w > v ? w : v; }
-            out[i] = (uint16_t)v;
+            out[i] = (Pix)v;
         }
         if (p.out_min) {
-            uint16_t *const out = reinterpret_cast<uint16_t *>(p.out_min);
-            const uint16_t *const ws = reinterpret_cast<const uint16_t *>(p.ws_min);
-            uint32_t v = p.accumulate ? out[i] : 65535u;
+            Pix *const out = reinterpret_cast<Pix *>(p.out_min);
+            const Pix *const ws = reinterpret_cast<const Pix *>(p.ws_min);
+            uint32_t v = p.accumulate ? out[i] : (PIX == 1u ? 255u : 65535u);
             for (uint32_t s = 0; s < p.segments; s++) { const uint32_t w = ws[(uint64_t)s * P + i]; v = w < v ? w : v; }
-            out[i] = (uint16_t)v;
+            out[i] = (Pix)v;
         }
         if (p.out_sum) {
             uint64_t v = p.accumulate ? p.out_sum[i] : 0ull;
@@ -592,7 +371,7 @@ __global__ __launch_bounds__(kProjCombineThreads) void project16_combine_kernel(
             p.out_sum[i] = v;
         }
         if (p.out_sumsq) {
-            const uint64_t *const ws = reinterpret_cast<const uint64_t *>(p.ws_sumsq);
+            const ProjSq<PIX> *const ws = reinterpret_cast<const ProjSq<PIX> *>(p.ws_sumsq);
             uint64_t v = p.accumulate ? p.out_sumsq[i] : 0ull;
             for (uint32_t s = 0; s < p.segments; s++) v += ws[(uint64_t)s * P + i];
             p.out_sumsq[i] = v;
@@ -611,37 +390,28 @@ uint64_t project_workspace_bytes(uint32_t stats, uint32_t segments, uint64_t pix
 }
 
 typedef void (*ProjKernel)(ProjParams);
+struct ProjTable {
+    ProjKernel k[16];   // [stats]: project_kernel<stats, PIX>, 1..15
+};
 
-// The projection kernel of `stats` from its table, then (segments > 1) the combine kernel, on stream s.
-static hipError_t launch_project_with(const ProjParams &p, const ProjKernel (&table)[16], ProjKernel combine,
-                                      uint32_t stats, hipStream_t s) {
-    if (stats < 1u || stats > kProjAll) return hipErrorInvalidValue;
+template <uint32_t PIX, uint32_t... S>
+static constexpr ProjTable proj_table(std::integer_sequence<uint32_t, S...>) {
+    return {{nullptr, project_kernel<S + 1u, PIX>...}};
+}
+
+hipError_t launch_project(const ProjParams &p, uint32_t stats, uint32_t pix, hipStream_t s) {
+    static const ProjTable tables[2] = {proj_table<1>(std::make_integer_sequence<uint32_t, 15>()),
+                                        proj_table<2>(std::make_integer_sequence<uint32_t, 15>())};
+    if (stats < 1u || stats > kProjAll || (pix != 1u && pix != 2u)) return hipErrorInvalidValue;
     const uint32_t grid = p.pieces * p.rows * p.segments;   // (the host keeps it below 2^31)
-    hipLaunchKernelGGL(table[stats], dim3(grid), dim3(kProjThreads), 0, s, p);
+    hipLaunchKernelGGL(tables[pix - 1u].k[stats], dim3(grid), dim3(kProjThreads), 0, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || p.segments == 1u) return e;
     const uint64_t P = (uint64_t)p.rw * (uint64_t)p.rh;
     const uint32_t cgrid = (uint32_t)((P + kProjCombineThreads - 1u) / kProjCombineThreads);
+    const ProjKernel combine = pix == 1u ? project_combine_kernel<1> : project_combine_kernel<2>;
     hipLaunchKernelGGL(combine, dim3(cgrid), dim3(kProjCombineThreads), 0, s, p);
     return hipGetLastError();
-}
-
-hipError_t launch_project(const ProjParams &p, uint32_t stats, hipStream_t s) {
-    static const ProjKernel table[16] = {nullptr,           project_kernel<1>,  project_kernel<2>,  project_kernel<3>,
-                                             project_kernel<4>,  project_kernel<5>,  project_kernel<6>,  project_kernel<7>,
-                                             project_kernel<8>,  project_kernel<9>,  project_kernel<10>, project_kernel<11>,
-                                             project_kernel<12>, project_kernel<13>, project_kernel<14>, project_kernel<15>};
-    return launch_project_with(p, table, project_combine_kernel, stats, s);
-}
-
-hipError_t launch_project16(const ProjParams &p, uint32_t stats, hipStream_t s) {
-    static const ProjKernel table[16] = {nullptr,              project16_kernel<1>,  project16_kernel<2>,
-                                         project16_kernel<3>,  project16_kernel<4>,  project16_kernel<5>,
-                                         project16_kernel<6>,  project16_kernel<7>,  project16_kernel<8>,
-                                         project16_kernel<9>,  project16_kernel<10>, project16_kernel<11>,
-                                         project16_kernel<12>, project16_kernel<13>, project16_kernel<14>,
-                                         project16_kernel<15>};
-    return launch_project_with(p, table, project16_combine_kernel, stats, s);
 }
 
 }  // namespace dbde

@@ -18,9 +18,13 @@ with tempfile.TemporaryDirectory() as tmp:
     subprocess.run(["make", "-s", "-C", f"{ROOT}/dbde-video-cpp_amd/csrc", "asm"], check=True, capture_output=True)
     bad = 0
 
-    def renamed(k):   # an old instance's name today: the 8- and 16-bit window kernels are one template on the pixel size
+    def renamed(k):   # an old instance's name today: the 8- and 16-bit window and projection kernels are templates on the pixel size
         k = re.sub(r"19decode_roi16_kernelILj(\d+)EEEvNS_9RoiParamsE", r"17decode_roi_kernelILj\1ELj2EEEvNS_9RoiParamsE", k)
-        return re.sub(r"17decode_roi_kernelILj(\d+)EEEvNS_9RoiParamsE", r"17decode_roi_kernelILj\1ELj1EEEvNS_9RoiParamsE", k)
+        k = re.sub(r"17decode_roi_kernelILj(\d+)EEEvNS_9RoiParamsE", r"17decode_roi_kernelILj\1ELj1EEEvNS_9RoiParamsE", k)
+        k = re.sub(r"16project16_kernelILj(\d+)EEEvNS_10ProjParamsE", r"14project_kernelILj\1ELj2EEEvNS_10ProjParamsE", k)
+        k = re.sub(r"14project_kernelILj(\d+)EEEvNS_10ProjParamsE", r"14project_kernelILj\1ELj1EEEvNS_10ProjParamsE", k)
+        k = k.replace("24project16_combine_kernelENS_10ProjParamsE", "22project_combine_kernelILj2EEEvNS_10ProjParamsE")
+        return k.replace("22project_combine_kernelENS_10ProjParamsE", "22project_combine_kernelILj1EEEvNS_10ProjParamsE")
 
     for f in ("dbde_kernels.s", "dbde16_kernels.s", "dbde_roi_kernels.s", "dbde_project_kernels.s"):
         old, new = bodies(f"{tmp}/dbde-video-cpp_amd/csrc/{f}"), bodies(f"{ROOT}/dbde-video-cpp_amd/csrc/{f}")

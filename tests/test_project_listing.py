@@ -1,9 +1,10 @@
 """CPU, compile only: the gfx950 listing of the projection kernels (`make asm`, dbde_project_kernels.s; no GPU).
 
-dbde_hip_project launches one project_kernel instance per statistics set (every non-empty subset of max, min, sum and
-sumsq: 15) and the combine kernel.  Their resources are part of the design: no instance may use scratch
-or a dynamic stack, each keeps its LDS within 512 bytes (the offsets exchange and the frame count), and each keeps its
-VGPRs within 128, so that at least 4 waves per SIMD -- 4 workgroups of 256 threads per CU -- stay resident.
+dbde_hip_project (PIX = 1) and dbde16_hip_project (PIX = 2) launch one project_kernel<STATS, PIX> instance per
+statistics set (every non-empty subset of max, min, sum and sumsq: 15) and project_combine_kernel<PIX>.  Their resources
+are part of the design: no instance may use scratch or a dynamic stack, each keeps its LDS within
+512 bytes (the offsets exchange and the frame count), and each keeps its VGPRs within 128, so that at least 4 waves per
+SIMD -- 4 workgroups of 256 threads per CU -- stay resident.
 """
 import os
 import re
@@ -16,6 +17,7 @@ CSRC = os.path.join(ROOT, "dbde-video-cpp_amd", "csrc")
 
 LDS_BUDGET = 512      # bytes per workgroup
 VGPR_BUDGET = 128     # per lane: 4 waves per SIMD
+PIXES = (1, 2)        # DBDE, DBDE16
 
 
 @pytest.fixture(scope="module")
@@ -30,29 +32,47 @@ def kernels():
     return out
 
 
-def instances(kernels):
+def combine(pix):
+    return f"_ZN4dbde22project_combine_kernelILj{pix}EEEvNS_10ProjParamsE"
+
+
+def expected(pix):
+    """The kernels of one pixel size: project_kernel<1..15, pix> and project_combine_kernel<pix>."""
+    return {combine(pix)} | {f"_ZN4dbde14project_kernelILj{s}ELj{pix}EEEvNS_10ProjParamsE" for s in range(1, 16)}
+
+
+def instances(kernels, pix):
     got = {}
     for name, f in kernels.items():
-        m = re.match(r"_ZN4dbde14project_kernelILj(\d+)EEEvNS_10ProjParamsE$", name)
-        if m:
+        m = re.match(r"_ZN4dbde14project_kernelILj(\d+)ELj(\d+)EEEvNS_10ProjParamsE$", name)
+        if m and int(m.group(2)) == pix:
             got[int(m.group(1))] = f
     return got
 
 
-def test_one_instance_per_statistics_set(kernels):
-    assert sorted(instances(kernels)) == list(range(1, 16))
-    assert "_ZN4dbde22project_combine_kernelENS_10ProjParamsE" in kernels
+@pytest.mark.parametrize("pix", PIXES)
+def test_one_instance_per_statistics_set(kernels, pix):
+    assert sorted(instances(kernels, pix)) == list(range(1, 16))
+    assert combine(pix) in kernels
 
 
-def test_no_scratch_and_within_budget(kernels):
-    for name, f in kernels.items():
+def test_no_other_projection_kernels(kernels):
+    assert set(kernels) == expected(1) | expected(2)
+
+
+@pytest.mark.parametrize("pix", PIXES)
+def test_no_scratch_and_within_budget(kernels, pix):
+    for name in sorted(expected(pix)):
+        f = kernels[name]
         assert f["private_segment_fixed_size"] == 0, (name, "scratch")
         assert not f.get("uses_dynamic_stack", 0), name
         assert f["group_segment_fixed_size"] <= LDS_BUDGET, (name, f["group_segment_fixed_size"])
         assert f["next_free_vgpr"] <= VGPR_BUDGET, (name, f["next_free_vgpr"])
 
 
-def test_fewer_statistics_cost_fewer_registers(kernels):
-    """An unrequested statistic has no accumulators: max + min alone needs fewer VGPRs than all four."""
-    inst = instances(kernels)
+@pytest.mark.parametrize("pix", PIXES)
+def test_fewer_statistics_cost_fewer_registers(kernels, pix):
+    """An unrequested statistic has no accumulators: max + min alone needs fewer VGPRs than all four (whose DBDE16 U64
+    sums of squares take 8)."""
+    inst = instances(kernels, pix)
     assert inst[3]["next_free_vgpr"] < inst[15]["next_free_vgpr"]
