@@ -14,6 +14,7 @@ repository root carries a one-file loader of that name).
 import ctypes as C
 import os
 import subprocess
+import weakref
 
 import numpy as np
 
@@ -57,6 +58,8 @@ C_ABI_SYMBOLS = [
     "dbde_hip_decode_roi", "dbde_hip_unpack_image_roi", "dbde_hip_roi_plan",
     "dbde16_hip_decode_roi", "dbde16_hip_roi_plan",
     "dbde_hip_project", "dbde_hip_project_plan", "dbde16_hip_project", "dbde16_hip_project_plan",
+    "dbde_hip_trace_map_summary", "dbde_hip_trace_map_create", "dbde_hip_trace_map_destroy", "dbde_hip_trace_map_info",
+    "dbde_hip_trace_map_pixels", "dbde_hip_traces", "dbde16_hip_traces", "dbde_hip_trace_plan", "dbde16_hip_trace_plan",
 ]
 
 
@@ -179,6 +182,22 @@ def lib():
     L.dbde16_hip_project.restype = i
     L.dbde16_hip_project_plan.argtypes = [i, i, i, i, i, i, i, C.c_uint, i, C.POINTER(ProjectPlan)]
     L.dbde16_hip_project_plan.restype = i
+    L.dbde_hip_trace_map_summary.argtypes = [vp, i, i, i, C.POINTER(TraceMapInfo), vp]
+    L.dbde_hip_trace_map_summary.restype = i
+    L.dbde_hip_trace_map_create.argtypes = [vp, vp, i, i, i, C.POINTER(vp)]
+    L.dbde_hip_trace_map_create.restype = i
+    L.dbde_hip_trace_map_destroy.argtypes = [vp]
+    L.dbde_hip_trace_map_destroy.restype = None
+    L.dbde_hip_trace_map_info.argtypes = [vp, C.POINTER(TraceMapInfo)]
+    L.dbde_hip_trace_map_info.restype = i
+    L.dbde_hip_trace_map_pixels.argtypes = [vp]
+    L.dbde_hip_trace_map_pixels.restype = vp
+    for fn in ("dbde_hip_traces", "dbde16_hip_traces"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, vp, vp, vp, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_trace_plan", "dbde16_hip_trace_plan"):
+        getattr(L, fn).argtypes = [i, i, i, C.POINTER(TraceMapInfo), C.c_uint, i, C.POINTER(TracePlan)]
+        getattr(L, fn).restype = i
     L.dbde_hip_unpack_frame.argtypes = [vp, C.POINTER(vp), i, i, vp]
     L.dbde_hip_pack_frame_header.restype = sz
     L.dbde_hip_pack_frame_header.argtypes = [C.POINTER(FrameHeader), vp]
@@ -525,6 +544,154 @@ class Projection:
         return (self.sumsq.to(torch.float64) / n - m * m).clamp_(min=0.0).sqrt_()
 
 
+class TraceMapInfo(C.Structure):
+    """dbde_hip_trace_map_info_t (include/dbde_hip.h)."""
+    _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("n_labels", C.c_uint32), ("tiles", C.c_uint32),
+                ("tiles_active", C.c_uint32), ("tiles_whole", C.c_uint32), ("tiles_mixed", C.c_uint32),
+                ("reserved_", C.c_uint32), ("device_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved_"}
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(**{k: int(d[k]) for k, _ in cls._fields_ if k != "reserved_"})
+
+
+class TracePlan(C.Structure):
+    """dbde_hip_trace_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32),
+                ("index_split", C.c_uint32), ("threads", C.c_uint32), ("tiles_per_workgroup", C.c_uint32),
+                ("spans_x", C.c_uint32), ("spans", C.c_uint32), ("segments", C.c_uint32),
+                ("frames_per_segment", C.c_uint32), ("grid", C.c_uint64), ("row_grid", C.c_uint64),
+                ("workspace_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def _labels_host(labels, n_labels):
+    """A label image (numpy, or a torch tensor on any device) -> (contiguous int32 numpy (H, W), n_labels)."""
+    if torch is not None and isinstance(labels, torch.Tensor):
+        labels = labels.detach().cpu().numpy()
+    a = np.asarray(labels)
+    if a.ndim != 2:
+        raise ValueError(f"labels must be a 2-D (H, W) array, not shape {a.shape}")
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"labels must be integers, not {a.dtype}")
+    lo, hi = (int(a.min()), int(a.max())) if a.size else (0, 0)
+    if n_labels is None:
+        n_labels = hi
+    if lo < 0 or hi > int(n_labels):
+        raise ValueError(f"labels must lie in [0, n_labels = {n_labels}], found [{lo}, {hi}]")
+    if not 1 <= int(n_labels) <= 65535:
+        raise ValueError(f"n_labels must lie in [1, 65535], not {n_labels}")
+    return np.ascontiguousarray(a, dtype=np.int32), int(n_labels)
+
+
+def trace_map_summary(labels, n_labels=None):
+    """dbde_hip_trace_map_summary (host only): the trace map's tile classes and per-label pixel counts of a label image
+    (H, W) with 0 = no region and 1..n_labels = region ids.  n_labels defaults to labels.max().  Returns the fields of
+    dbde_hip_trace_map_info_t plus "pixels", an int64 numpy array (n_labels,).  Raises ValueError for labels outside
+    [0, n_labels] or n_labels outside [1, 65535]."""
+    a, L = _labels_host(labels, n_labels)
+    info = TraceMapInfo()
+    pixels = np.zeros(L, np.uint64)
+    rc = lib().dbde_hip_trace_map_summary(a.ctypes.data, a.shape[1], a.shape[0], L, C.byref(info), pixels.ctypes.data)
+    if rc != OK:
+        raise ValueError(f"dbde_hip_trace_map_summary({a.shape[1]}, {a.shape[0]}, {L}) -> {rc}")
+    d = info.as_dict()
+    d["pixels"] = pixels.astype(np.int64)
+    return d
+
+
+def _trace_plan(fn, W, H, n_frames, info, stats, n_cu):
+    if isinstance(info, TraceMap):
+        info = info.info
+    ti = TraceMapInfo.from_dict(info)
+    pl = TracePlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, C.byref(ti), stats_mask(stats), n_cu, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {stats}, n_cu={n_cu}) -> {rc}")
+    return pl.as_dict()
+
+
+def trace_plan(W, H, n_frames, info, stats=("max", "min", "sum", "sumsq"), n_cu=256):
+    """dbde_hip_trace_plan: the index geometry, trace launch and workspace of Codec.traces (host arithmetic only).
+    info: a TraceMap, or the dict trace_map_summary / TraceMap.info returns.  Raises ValueError where dbde_hip_traces
+    would return DBDE_HIP_ERR_ARG for these sizes."""
+    return _trace_plan("dbde_hip_trace_plan", W, H, n_frames, info, stats, n_cu)
+
+
+def trace16_plan(W, H, n_frames, info, stats=("max", "min", "sum", "sumsq"), n_cu=256):
+    """dbde16_hip_trace_plan: trace_plan for DBDE16 traces (Codec.traces16)."""
+    return _trace_plan("dbde16_hip_trace_plan", W, H, n_frames, info, stats, n_cu)
+
+
+class TraceMap:
+    """A label image classified into the device form dbde_hip_traces reads (Codec.trace_map).  .n_labels, .info (dict),
+    .pixels (int64 device tensor (n_labels,): pixels per label), .close().  Holds its codec, and is closed before it."""
+
+    def __init__(self, codec, labels, n_labels=None):
+        a, L = _labels_host(labels, n_labels)
+        self.codec = codec
+        h = C.c_void_p()
+        codec._check(codec.L.dbde_hip_trace_map_create(codec.h, a.ctypes.data, a.shape[1], a.shape[0], L, C.byref(h)),
+                     "dbde_hip_trace_map_create")
+        self.h = h
+        self.n_labels = L
+        info = TraceMapInfo()
+        codec.L.dbde_hip_trace_map_info(h, C.byref(info))
+        self.info = info.as_dict()
+        self.W, self.H = a.shape[1], a.shape[0]
+        # the counts the map holds (dbde_hip_trace_map_pixels), counted here from the same labels
+        counts = np.bincount(a.reshape(-1), minlength=L + 1)[1:]
+        pixels = torch.from_numpy(counts.astype(np.int64)).to(codec.device)
+        self.pixels = pixels
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h.value:
+            self.codec.L.dbde_hip_trace_map_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Traces:
+    """Device tensors of region traces (Codec.traces): max / min (n, L) uint8, sum / sumsq (n, L) int64, and pixels
+    (L,) int64, the map's pixels per label.  Column j is label j + 1.  A statistic that was not asked for is None.
+    Codec.traces16's max / min are int16 tensors holding the U16 bits."""
+
+    def __init__(self, max=None, min=None, sum=None, sumsq=None, pixels=None):
+        self.max, self.min, self.sum, self.sumsq, self.pixels = max, min, sum, sumsq, pixels
+
+    @classmethod
+    def empty(cls, n, L, stats, device, pix=1, pixels=None):
+        """Uninitialised outputs for `stats`; pix: bytes per value of max / min (1: uint8, 2: int16 for DBDE16)."""
+        mask = stats_mask(stats)
+        if pix not in (1, 2):
+            raise ValueError(f"pix must be 1 or 2, not {pix!r}")
+        mm_dtype = torch.uint8 if pix == 1 else torch.int16
+        mm = lambda: torch.empty((n, L), dtype=mm_dtype, device=device)      # noqa: E731
+        i64 = lambda: torch.empty((n, L), dtype=torch.int64, device=device)   # noqa: E731
+        return cls(mm() if mask & 1 else None, mm() if mask & 2 else None, i64() if mask & 4 else None,
+                   i64() if mask & 8 else None, pixels)
+
+    def mean(self):
+        """Per-frame, per-label mean (float64, on the device); NaN for labels without pixels."""
+        return self.sum.to(torch.float64) / self.pixels.to(torch.float64)
+
+    def std(self):
+        """Per-frame, per-label population standard deviation (float64, on the device); NaN for labels without pixels."""
+        n = self.pixels.to(torch.float64)
+        m = self.sum.to(torch.float64) / n
+        return (self.sumsq.to(torch.float64) / n - m * m).clamp_(min=0.0).sqrt_()
+
+
 class DbdeError(RuntimeError):
     pass
 
@@ -548,6 +715,8 @@ class Codec:
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:
+            for m in list(getattr(self, "_trace_maps", ())):   # a map is destroyed before its context
+                m.close()
             self.L.dbde_hip_destroy(self.h)
             self.h = C.c_void_p()
 
@@ -659,6 +828,37 @@ class Codec:
         return self._project("dbde_hip_project", 1, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh,
                              stats, out, accumulate, results)
 
+    def trace_map(self, labels, n_labels=None):
+        """A TraceMap of this codec from a label image (H, W): numpy, or a torch tensor on any device; 0 = no region,
+        1..n_labels = region ids, n_labels defaulting to labels.max()."""
+        m = TraceMap(self, labels, n_labels)
+        if not hasattr(self, "_trace_maps"):
+            self._trace_maps = weakref.WeakSet()
+        self._trace_maps.add(m)
+        return m
+
+    def _traces(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, tmap, stats, out, results):
+        """traces / traces16 through the C function named fn; pix: bytes per value of max / min."""
+        if out is None:
+            out = Traces.empty(n, tmap.n_labels, stats, self.device, pix=pix, pixels=tmap.pixels)
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(), W, H, n,
+                                 tmap.h, ptr(out.max), ptr(out.min), ptr(out.sum), ptr(out.sumsq),
+                                 ptr(results) if n > 0 else None)
+        self._check(rc, fn)
+        return out, results
+
+    def traces(self, stream, stream_offset, stream_bytes, offsets, W, H, n, tmap, stats=("max", "min", "sum", "sumsq"),
+               out=None, results=None):
+        """Region traces of n frames (frame f at stream.data_ptr()+stream_offset+offsets[f]) over the TraceMap tmap:
+        per frame and label, the max, min, sum and sum of squares of the label's pixels.  out: a Traces to write into
+        (its statistics are the ones computed); a rejected frame's rows are left as they were.  Returns
+        (Traces (n, n_labels), results (n, 4) int64) like decode_frames."""
+        return self._traces("dbde_hip_traces", 1, stream, stream_offset, stream_bytes, offsets, W, H, n, tmap, stats,
+                            out, results)
+
     def index_stream(self, stream, stream_offset, stream_bytes, W, H, max_frames):
         offsets = torch.empty(max(max_frames, 1), dtype=torch.int64, device=self.device)
         n = C.c_int(0)
@@ -726,6 +926,13 @@ class Codec:
         U16 bits (Projection.empty(..., pix=2)).  .to(torch.int32) & 0xFFFF gives their values."""
         return self._project("dbde16_hip_project", 2, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw,
                              rh, stats, out, accumulate, results)
+
+    def traces16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, tmap,
+                 stats=("max", "min", "sum", "sumsq"), out=None, results=None):
+        """DBDE16 region traces: traces' arguments and results, with max / min as int16 tensors holding the U16 bits
+        (Traces.empty(..., pix=2)).  .to(torch.int32) & 0xFFFF gives their values."""
+        return self._traces("dbde16_hip_traces", 2, stream, stream_offset, stream_bytes, offsets, W, H, n, tmap, stats,
+                            out, results)
 
     # ---- host-pointer API: the reference's functions -------------------------------------
     def pack_frame(self, index, image, W, H):

@@ -18,6 +18,7 @@
 #include "dbde_kernels.h"
 #include "dbde_project_kernels.h"
 #include "dbde_roi_kernels.h"
+#include "dbde_trace_kernels.h"
 
 using namespace dbde;
 
@@ -69,6 +70,8 @@ struct dbde_hip_ctx {
     unsigned long long *fuse_rec = nullptr;   // records of the fused index + decode launch (epoch-tagged, never cleared)
     uint8_t *proj_ws = nullptr;      // per-segment partials of dbde_hip_project
     size_t proj_ws_bytes = 0;
+    uint8_t *trace_ws = nullptr;     // U32 max / min per (frame, label) of dbde_hip_traces
+    size_t trace_ws_bytes = 0;
     size_t fuse_rec_n = 0;
     uint32_t fuse_epoch = 0;
     // sticky failure word (device) + scratch
@@ -290,6 +293,7 @@ void dbde_hip_destroy(dbde_hip_ctx *ctx) {
     if (ctx->idx_ctr) (void)hipFree(ctx->idx_ctr);
     if (ctx->fuse_rec) (void)hipFree(ctx->fuse_rec);
     if (ctx->proj_ws) (void)hipFree(ctx->proj_ws);
+    if (ctx->trace_ws) (void)hipFree(ctx->trace_ws);
     if (ctx->sticky) (void)hipFree(ctx->sticky);
     if (ctx->st_img) (void)hipFree(ctx->st_img);
     if (ctx->st_pack) (void)hipFree(ctx->st_pack);
@@ -1091,6 +1095,345 @@ int dbde16_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream
                        uint64_t *d_count, dbde_hip_frame_result *d_results) {
     return project_common(ctx, "project16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
                           rh, accumulate, d_max, d_min, d_sum, d_sumsq, d_count, d_results);
+}
+
+// ---- region traces ----------------------------------------------------------------------------------------
+struct dbde_hip_trace_map {
+    dbde_hip_ctx *ctx;
+    dbde_hip_trace_map_info_t info;
+    uint8_t *dev;                     // one allocation: the layout of trace_map_layout
+    const uint32_t *span_first[2];    // [pix - 1]: first active tile of each span, [spans + 1]
+    uint32_t spans_x[2], spans[2];
+    const uint32_t *tile_pos, *tile_kind;
+    const uint16_t *blocks;
+    const uint64_t *pixels;
+};
+
+namespace {
+
+// The host side of a trace map: the active tiles in tile order, their words (the label of a whole tile, kTraceMixed |
+// block of a mixed one), the mixed tiles' label blocks, the per-label pixel counts and each pixel size's spans.
+struct HostTraceMap {
+    dbde_hip_trace_map_info_t info;
+    std::vector<uint32_t> pos, kind, span_first[2];
+    std::vector<uint16_t> blocks;
+    std::vector<uint64_t> pixels;
+    uint32_t spans_x[2];
+};
+
+// nullptr when the labels are good, else what is wrong.  full: also the tile lists, blocks and spans.
+const char *trace_classify(const int32_t *labels, int W, int H, int n_labels, HostTraceMap &m, bool full) {
+    Geometry g;
+    if (!labels) return "null labels";
+    if (!geometry(W, H, g)) return "bad frame size";
+    if (n_labels < 1 || n_labels > 65535) return "n_labels outside [1, 65535]";
+    memset(&m.info, 0, sizeof m.info);
+    m.info.W = W;
+    m.info.H = H;
+    m.info.n_labels = (uint32_t)n_labels;
+    m.info.tiles = g.T;
+    m.pixels.assign((size_t)n_labels, 0);
+    for (size_t i = 0; i < g.pixels; i++)
+        if (labels[i] < 0 || labels[i] > n_labels) return "a label outside [0, n_labels]";
+    uint16_t blk[64];
+    for (uint32_t ty = 0; ty < g.h; ty++) {
+        for (uint32_t tx = 0; tx < g.w; tx++) {
+            const uint32_t x0 = 8u * tx, y0 = 8u * ty;
+            const uint32_t vw = (uint32_t)W - x0 < 8u ? (uint32_t)W - x0 : 8u, vh = (uint32_t)H - y0 < 8u ? (uint32_t)H - y0 : 8u;
+            bool any = false, same = true;
+            const int32_t first = labels[(size_t)y0 * W + x0];
+            for (uint32_t y = 0; y < 8; y++) {
+                for (uint32_t x = 0; x < 8; x++) {
+                    int32_t l = 0;
+                    if (y < vh && x < vw) {
+                        l = labels[(size_t)(y0 + y) * W + x0 + x];
+                        if (l) m.pixels[l - 1]++;
+                        same = same && l == first;
+                    }
+                    any = any || l != 0;
+                    blk[8 * y + x] = (uint16_t)l;
+                }
+            }
+            if (!any) continue;
+            const bool whole = same && vw == 8u && vh == 8u;
+            m.info.tiles_active++;
+            if (whole) m.info.tiles_whole++;
+            else m.info.tiles_mixed++;
+            if (!full) continue;
+            m.pos.push_back(ty * g.w + tx);
+            if (whole) {
+                m.kind.push_back((uint32_t)first);
+            } else {
+                m.kind.push_back(kTraceMixed | (uint32_t)(m.blocks.size() / 64u));
+                m.blocks.insert(m.blocks.end(), blk, blk + 64);
+            }
+        }
+    }
+    if (!full) return nullptr;
+    for (uint32_t pix = 1; pix <= 2u; pix++) {
+        const uint32_t K = kTraceTilesOf(pix), sx = (g.w + K - 1u) / K;
+        std::vector<uint32_t> &sf = m.span_first[pix - 1u];
+        m.spans_x[pix - 1u] = sx;
+        sf.resize((size_t)sx * g.h + 1u);
+        size_t a = 0;
+        for (uint32_t s = 0; s < sx * g.h; s++) {   // spans in stream order: tiles [ty * w + (s % sx) * K, + K) of row ty
+            const uint32_t ty = s / sx, p0 = ty * g.w + (s - ty * sx) * K;
+            while (a < m.pos.size() && m.pos[a] < p0) a++;
+            sf[s] = (uint32_t)a;
+        }
+        sf[(size_t)sx * g.h] = (uint32_t)m.pos.size();
+    }
+    return nullptr;
+}
+
+// Byte offsets of the device map: [span_first pix 1][span_first pix 2][tile_pos][tile_kind][blocks][pixels], each
+// 16-byte aligned.
+struct TraceMapLayout {
+    size_t sf1, sf2, pos, kind, blocks, pixels, total;
+};
+TraceMapLayout trace_map_layout(const HostTraceMap &m) {
+    auto up = [](size_t v) { return (v + 15u) & ~(size_t)15; };
+    TraceMapLayout l;
+    l.sf1 = 0;
+    l.sf2 = l.sf1 + up(4u * m.span_first[0].size());
+    l.pos = l.sf2 + up(4u * m.span_first[1].size());
+    l.kind = l.pos + up(4u * m.pos.size());
+    l.blocks = l.kind + up(4u * m.kind.size());
+    l.pixels = l.blocks + up(2u * m.blocks.size());
+    l.total = l.pixels + up(8u * m.pixels.size());
+    return l;
+}
+
+}  // namespace
+
+int dbde_hip_trace_map_summary(const int32_t *labels, int W, int H, int n_labels, dbde_hip_trace_map_info_t *info,
+                               uint64_t *pixels) {
+    HostTraceMap m;
+    if (trace_classify(labels, W, H, n_labels, m, true)) return DBDE_HIP_ERR_ARG;
+    m.info.device_bytes = trace_map_layout(m).total;
+    if (info) *info = m.info;
+    if (pixels) memcpy(pixels, m.pixels.data(), 8u * m.pixels.size());
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_trace_map_create(dbde_hip_ctx *ctx, const int32_t *labels, int W, int H, int n_labels,
+                              dbde_hip_trace_map **out) {
+    if (!ctx || !out) return fail(ctx, DBDE_HIP_ERR_ARG, "trace_map_create: null pointer");
+    *out = nullptr;
+    HostTraceMap m;
+    if (const char *why = trace_classify(labels, W, H, n_labels, m, true))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "trace_map_create: %s (W=%d H=%d n_labels=%d)", why, W, H, n_labels);
+    const TraceMapLayout l = trace_map_layout(m);
+    m.info.device_bytes = l.total;
+    std::vector<uint8_t> host(l.total, 0);
+    auto put = [&](size_t at, const void *src, size_t n) { if (n) memcpy(host.data() + at, src, n); };
+    put(l.sf1, m.span_first[0].data(), 4u * m.span_first[0].size());
+    put(l.sf2, m.span_first[1].data(), 4u * m.span_first[1].size());
+    put(l.pos, m.pos.data(), 4u * m.pos.size());
+    put(l.kind, m.kind.data(), 4u * m.kind.size());
+    put(l.blocks, m.blocks.data(), 2u * m.blocks.size());
+    put(l.pixels, m.pixels.data(), 8u * m.pixels.size());
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void *dev = nullptr;
+    HIP_TRY(ctx, hipMalloc(&dev, l.total));
+    hipError_t e = hipMemcpyAsync(dev, host.data(), l.total, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(dev);
+        return fail(ctx, DBDE_HIP_ERR_HIP, "trace_map_create: copy failed: %s", hipGetErrorString(e));
+    }
+    dbde_hip_trace_map *tm = new dbde_hip_trace_map;
+    uint8_t *d = static_cast<uint8_t *>(dev);
+    tm->ctx = ctx;
+    tm->info = m.info;
+    tm->dev = d;
+    tm->span_first[0] = reinterpret_cast<const uint32_t *>(d + l.sf1);
+    tm->span_first[1] = reinterpret_cast<const uint32_t *>(d + l.sf2);
+    for (int k = 0; k < 2; k++) {
+        tm->spans_x[k] = m.spans_x[k];
+        tm->spans[k] = (uint32_t)(m.span_first[k].size() - 1u);
+    }
+    tm->tile_pos = reinterpret_cast<const uint32_t *>(d + l.pos);
+    tm->tile_kind = reinterpret_cast<const uint32_t *>(d + l.kind);
+    tm->blocks = reinterpret_cast<const uint16_t *>(d + l.blocks);
+    tm->pixels = reinterpret_cast<const uint64_t *>(d + l.pixels);
+    *out = tm;
+    return DBDE_HIP_OK;
+}
+
+void dbde_hip_trace_map_destroy(dbde_hip_trace_map *m) {
+    if (!m) return;
+    (void)hipSetDevice(m->ctx->device);
+    (void)hipStreamSynchronize(m->ctx->stream);   // queued traces may still read it
+    (void)hipFree(m->dev);
+    delete m;
+}
+
+int dbde_hip_trace_map_info(const dbde_hip_trace_map *m, dbde_hip_trace_map_info_t *info) {
+    if (!m || !info) return DBDE_HIP_ERR_ARG;
+    *info = m->info;
+    return DBDE_HIP_OK;
+}
+
+const uint64_t *dbde_hip_trace_map_pixels(const dbde_hip_trace_map *m) { return m ? m->pixels : nullptr; }
+
+namespace {
+
+struct TracePlan {
+    Geometry g;
+    DecGeom dg;                       // the index's chunks (roi_index_geometry)
+    uint32_t split, tiles, spans_x, spans, segments, fps;
+    uint64_t grid, row_grid, workspace;
+};
+// Frames per segment: segments only fill the device (about 4 busy workgroups per CU, the busy spans counted as the
+// fewest that can hold the active tiles) and never hold fewer than kTraceMinFramesPerSegment frames.  Segments cost no
+// extra traffic: each (frame, span) is traced by one workgroup.
+constexpr uint32_t kTraceMinFramesPerSegment = 16;
+const char *plan_trace(int W, int H, int n_frames, const dbde_hip_trace_map_info_t *info, unsigned stats, int n_cu,
+                       uint32_t pix, TracePlan &pl) {
+    if (!info) return "null map info";
+    if (n_frames < 0) return "n_frames < 0";
+    if (!geometry(W, H, pl.g)) return "bad frame size";
+    if (info->W != W || info->H != H) return "W / H differ from the map's";
+    if (info->n_labels < 1u || info->n_labels > 65535u || info->tiles != pl.g.T || info->tiles_active > pl.g.T)
+        return "map info does not describe a map of this frame size";
+    if (stats < 1u || stats > kProjAll) return "no statistic (or an unknown one) requested";
+    if (n_cu < 1) return "n_cu < 1";
+    pl.dg = roi_index_geometry(pl.g.w, pl.g.h);
+    if (pl.dg.cpf > kMaxChunksPerFrame) return "frame too large";
+    if ((uint64_t)n_frames * (pl.dg.cpf + 1u) >= (1ull << 31)) return "too many chunks in one call";
+    pl.split = index_split_for(n_frames, pl.dg.cpf);
+    pl.tiles = kTraceTilesOf(pix);
+    pl.spans_x = (pl.g.w + pl.tiles - 1u) / pl.tiles;
+    pl.spans = pl.spans_x * pl.g.h;
+    const uint64_t n = (uint64_t)n_frames;
+    const uint64_t busy = info->tiles_active ? (info->tiles_active + pl.tiles - 1u) / pl.tiles : 1u;
+    const uint64_t target = 4ull * (uint64_t)n_cu;
+    uint64_t seg = busy >= target ? 1u : (target + busy - 1u) / busy;
+    const uint64_t by_len = (n + kTraceMinFramesPerSegment - 1u) / kTraceMinFramesPerSegment;
+    if (seg > by_len) seg = by_len;
+    if (seg < 1u) seg = 1u;
+    uint64_t fps = (n + seg - 1u) / seg;
+    if (fps > 0u) seg = (n + fps - 1u) / fps;   // no empty segment
+    pl.segments = (uint32_t)seg;
+    pl.fps = (uint32_t)fps;
+    pl.grid = (uint64_t)pl.spans * seg;
+    if (pl.grid >= (1ull << 31)) return "too many workgroups in one call";
+    const uint64_t rows = n * info->n_labels;
+    pl.row_grid = (rows + kTraceRowThreads - 1u) / kTraceRowThreads;
+    if (pl.row_grid >= (1ull << 31)) return "too many outputs in one call";
+    const uint64_t ws = (4u * rows + 15u) & ~(uint64_t)15;
+    pl.workspace = ((stats & kProjMax) ? ws : 0u) + ((stats & kProjMin) ? ws : 0u);
+    return nullptr;
+}
+
+int trace_plan_common(int W, int H, int n_frames, const dbde_hip_trace_map_info_t *info, unsigned stats, int n_cu,
+                      uint32_t pix, dbde_hip_trace_plan_t *plan) {
+    TracePlan pl;
+    if (!plan || plan_trace(W, H, n_frames, info, stats, n_cu, pix, pl)) return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->chunks_per_frame = pl.dg.cpf;
+    plan->chunk_tiles = pl.dg.ct;
+    plan->chunk_pieces = pl.dg.ct == pl.g.w || pl.dg.pieces > 1u ? pl.dg.pieces : 0u;
+    plan->index_split = pl.split;
+    plan->threads = kTraceThreads;
+    plan->tiles_per_workgroup = pl.tiles;
+    plan->spans_x = pl.spans_x;
+    plan->spans = pl.spans;
+    plan->segments = pl.segments;
+    plan->frames_per_segment = pl.fps;
+    plan->grid = pl.grid;
+    plan->row_grid = pl.row_grid;
+    plan->workspace_bytes = pl.workspace;
+    return DBDE_HIP_OK;
+}
+
+// Both trace entry points: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the trace
+// kernels in slot 2.  d_max / d_min hold U8 (pix 1) or U16 (pix 2) values.
+int traces_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream, size_t stream_bytes,
+                  const uint64_t *d_frame_offsets, int W, int H, int n_frames, const dbde_hip_trace_map *map,
+                  void *d_max, void *d_min, uint64_t *d_sum, uint64_t *d_sumsq, dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    if (!map) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null map", name);
+    if (map->ctx != ctx) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the map belongs to another context", name);
+    const unsigned stats = (d_max ? kProjMax : 0u) | (d_min ? kProjMin : 0u) | (d_sum ? kProjSum : 0u) |
+                           (d_sumsq ? kProjSumSq : 0u);
+    TracePlan pl;
+    if (const char *why = plan_trace(W, H, n_frames, &map->info, stats, ctx->n_cu, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d, map %dx%d)", name, why, W, H, n_frames,
+                    map->info.W, map->info.H);
+    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if ((reinterpret_cast<uintptr_t>(d_sum) | reinterpret_cast<uintptr_t>(d_sumsq)) & 7u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U64 outputs must be 8-byte aligned", name);
+    if ((reinterpret_cast<uintptr_t>(d_max) | reinterpret_cast<uintptr_t>(d_min)) & (pix - 1u))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U16 outputs must be 2-byte aligned", name);
+    if (n_frames == 0) return DBDE_HIP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.dg, pix, pl.split);
+    if (rc) return rc;
+    TraceParams p;
+    memset(&p, 0, sizeof p);
+    if (pl.workspace) {   // U32 max, then U32 min, [n_frames][n_labels] each, 16-byte aligned
+        rc = grow(ctx, ctx->trace_ws, ctx->trace_ws_bytes, (size_t)pl.workspace, 1);
+        if (rc) return rc;
+        const uint64_t ws = (4u * (uint64_t)n_frames * map->info.n_labels + 15u) & ~(uint64_t)15;
+        uint8_t *w = ctx->trace_ws;
+        if (d_max) { p.ws_max = reinterpret_cast<uint32_t *>(w); w += ws; }
+        if (d_min) p.ws_min = reinterpret_cast<uint32_t *>(w);
+    }
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.n_frames = (uint32_t)n_frames;
+    p.T = pl.g.T;
+    p.w = pl.g.w;
+    p.geom = pl.dg;
+    p.spans_x = pl.spans_x;
+    p.spans = pl.spans;
+    p.segments = pl.segments;
+    p.fps = pl.fps;
+    p.n_labels = map->info.n_labels;
+    p.pix_max = pix == 1u ? 0xFFu : 0xFFFFu;
+    p.span_first = map->span_first[pix - 1u];
+    p.tile_pos = map->tile_pos;
+    p.tile_kind = map->tile_kind;
+    p.blocks = map->blocks;
+    p.out_max = static_cast<uint8_t *>(d_max);
+    p.out_min = static_cast<uint8_t *>(d_min);
+    p.out_sum = d_sum;
+    p.out_sumsq = d_sumsq;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_traces(p, stats, pix, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+}  // namespace
+
+int dbde_hip_trace_plan(int W, int H, int n_frames, const dbde_hip_trace_map_info_t *info, unsigned stats, int n_cu,
+                        dbde_hip_trace_plan_t *plan) {
+    return trace_plan_common(W, H, n_frames, info, stats, n_cu, 1u, plan);
+}
+
+int dbde16_hip_trace_plan(int W, int H, int n_frames, const dbde_hip_trace_map_info_t *info, unsigned stats, int n_cu,
+                          dbde_hip_trace_plan_t *plan) {
+    return trace_plan_common(W, H, n_frames, info, stats, n_cu, 2u, plan);
+}
+
+int dbde_hip_traces(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+                    int W, int H, int n_frames, const dbde_hip_trace_map *map, uint8_t *d_max, uint8_t *d_min,
+                    uint64_t *d_sum, uint64_t *d_sumsq, dbde_hip_frame_result *d_results) {
+    return traces_common(ctx, "traces", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, map, d_max, d_min,
+                         d_sum, d_sumsq, d_results);
+}
+
+int dbde16_hip_traces(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+                      int W, int H, int n_frames, const dbde_hip_trace_map *map, uint16_t *d_max, uint16_t *d_min,
+                      uint64_t *d_sum, uint64_t *d_sumsq, dbde_hip_frame_result *d_results) {
+    return traces_common(ctx, "traces16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, map, d_max,
+                         d_min, d_sum, d_sumsq, d_results);
 }
 
 int dbde_hip_index_stream_async(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, int W, int H,

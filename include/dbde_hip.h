@@ -539,6 +539,91 @@ int dbde_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, in
 int dbde16_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats,
                             int n_cu, dbde_hip_project_plan_t *plan);
 
+/* ---- region traces: per frame and per labelled region, max / min / sum / sum of squares ---------- */
+/* A trace map is a label image (H x W int32, row-major, pitch W: 0 = no region, 1..n_labels = region id) classified
+ * once per 8x8 tile, counting only the tile's valid pixels (an edge tile's padding beyond W / H belongs to no region):
+ *   empty  no pixel has a label > 0: the traces read none of its minimum or payload bytes;
+ *   whole  every valid pixel has the same label l > 0 and the tile has no padding: its 64 pixels go to l;
+ *   mixed  everything else (edge tiles with padding included): the map keeps its 64 labels as U16, padding 0.
+ * Rules: 1 <= n_labels <= 65535 and every label in [0, n_labels], else DBDE_HIP_ERR_ARG.  W and H as the codec's. */
+typedef struct dbde_hip_trace_map dbde_hip_trace_map;
+typedef struct dbde_hip_trace_map_info_t {
+    int32_t W, H;
+    uint32_t n_labels;
+    uint32_t tiles, tiles_active, tiles_whole, tiles_mixed, reserved_;  /* active = whole + mixed */
+    uint64_t device_bytes;                                              /* the map's device memory */
+} dbde_hip_trace_map_info_t;
+/* Pure host: validates and classifies labels (host memory) without a context.  info (optional) gets the counts;
+ * pixels (optional, host, n_labels U64) gets the number of pixels of each label 1..n_labels. */
+int dbde_hip_trace_map_summary(const int32_t *labels, int W, int H, int n_labels, dbde_hip_trace_map_info_t *info,
+                               uint64_t *pixels);
+/* Builds the map in the context's device memory from labels (host memory).  Synchronous.  The map belongs to ctx: it
+ * may be used only with ctx, and it must be destroyed before ctx is. */
+int dbde_hip_trace_map_create(dbde_hip_ctx *ctx, const int32_t *labels, int W, int H, int n_labels,
+                              dbde_hip_trace_map **out);
+/* Waits for the map's context's stream, then frees the map.  NULL is allowed. */
+void dbde_hip_trace_map_destroy(dbde_hip_trace_map *m);
+int dbde_hip_trace_map_info(const dbde_hip_trace_map *m, dbde_hip_trace_map_info_t *info);
+/* Device, n_labels U64: the pixels of each label 1..n_labels. */
+const uint64_t *dbde_hip_trace_map_pixels(const dbde_hip_trace_map *m);
+
+/* Region traces: for each frame f of n_frames and each label l = j + 1 of the map, the maximum, minimum, sum and sum of
+ * squares of frame f's pixels that carry label l, reduced straight from the compressed bytes (no image is written).
+ * Inputs and outputs:
+ *   Frame f starts at d_stream + d_frame_offsets[f] (any byte alignment; concatenated and slot layouts alike).  No byte
+ *   at or beyond stream_bytes is read.  W / H must be the map's, and the map must be ctx's.
+ *   Each output is n_frames x n_labels, row-major (column j = label j + 1; label 0 is never reported): d_max and d_min
+ *   U8 at any address, d_sum and d_sumsq U64, 8-byte aligned.  A NULL output is neither computed nor touched; at least
+ *   one of the four must be non-NULL.  Nothing outside the n_frames x n_labels outputs is written.  d_results
+ *   (optional) is filled exactly as dbde_hip_decode_frames fills it.
+ * What is reduced: exactly the bytes dbde_hip_decode_frames would write (minima that wrap modulo 256 included), for
+ *   the frames it accepts.  A rejected frame reports its usual result entry and its output rows are left untouched.
+ *   For an accepted frame, a label without pixels gets the empty reduction: max 0, min 255, sums 0.
+ * Every result is an exact integer, independent of the launch shape and of workgroup order (integer atomics).  The U64
+ *   sums are exact for any frame the index accepts (at most 2^30 pixels * 65535^2 < 2^64); inside the kernel a
+ *   workgroup's run holds at most 2,048 pixels in U32 (2,048 * 255^2 < 2^32).
+ * n_frames == 0 does nothing.  Errors: DBDE_HIP_ERR_ARG for a NULL context, map, stream or offsets, a map of another
+ *   context or of another W / H, no statistic, or an unaligned U64 output.
+ * Asynchronous on the context's stream; workspace (the decode index, and U32 max / min per (frame, label) when max or
+ * min is requested) is the context's, grown on demand.  Timing hook: the index kernel in slot 1, the trace kernels in
+ * slot 2. */
+int dbde_hip_traces(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+                    int W, int H, int n_frames, const dbde_hip_trace_map *map, uint8_t *d_max, uint8_t *d_min,
+                    uint64_t *d_sum, uint64_t *d_sumsq, dbde_hip_frame_result *d_results);
+/* Region traces of DBDE16 frames: dbde_hip_traces' contract with U16 pixels.  Validation is dbde16_hip_decode_frames'
+ * own; the values reduced are exactly the U16 values it writes (minima that wrap modulo 2^16 included).  d_max / d_min
+ * are U16, 2-byte aligned; the empty minimum is 65535.  Inside the kernel a run holds at most 1,024 pixels, its sum in
+ * U32 (1,024 * 65535 < 2^32) and its sum of squares in U64.  Errors: as dbde_hip_traces, and for an unaligned U16
+ * output. */
+int dbde16_hip_traces(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+                      int W, int H, int n_frames, const dbde_hip_trace_map *map, uint16_t *d_max, uint16_t *d_min,
+                      uint64_t *d_sum, uint64_t *d_sumsq, dbde_hip_frame_result *d_results);
+
+/* What dbde_hip_traces runs (pure host arithmetic, like dbde_hip_project_plan): validates exactly what dbde_hip_traces
+ * validates of its sizes (DBDE_HIP_ERR_ARG otherwise: W / H other than info's, bad n_frames, no statistic, n_cu < 1)
+ * and reports the index geometry, the trace kernel's launch and the workspace.  info: the map's
+ * (dbde_hip_trace_map_info or dbde_hip_trace_map_summary).  stats: DBDE_HIP_PROJECT_* bitmask. */
+typedef struct dbde_hip_trace_plan_t {
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t threads;                 /* trace kernel: workgroup size */
+    uint32_t tiles_per_workgroup;     /* trace kernel: tile columns of one span (8 lanes per tile; DBDE16: 16) */
+    uint32_t spans_x;                 /* spans across a tile row */
+    uint32_t spans;                   /* spans of the frame (a workgroup of a span without active tiles returns) */
+    uint32_t segments;                /* frame segments, each traced by its own workgroups */
+    uint32_t frames_per_segment;      /* frames of every segment but the last (which may hold fewer) */
+    uint64_t grid;                    /* trace kernel: spans * segments workgroups */
+    uint64_t row_grid;                /* init / finish kernels: workgroups over n_frames * n_labels */
+    uint64_t workspace_bytes;         /* U32 max / min per (frame, label) */
+} dbde_hip_trace_plan_t;
+int dbde_hip_trace_plan(int W, int H, int n_frames, const dbde_hip_trace_map_info_t *info, unsigned stats, int n_cu,
+                        dbde_hip_trace_plan_t *plan);
+/* The same for dbde16_hip_traces: 16 lanes per tile, so half the tiles per workgroup and twice the spans. */
+int dbde16_hip_trace_plan(int W, int H, int n_frames, const dbde_hip_trace_map_info_t *info, unsigned stats, int n_cu,
+                          dbde_hip_trace_plan_t *plan);
+
 /* ---- kernel timing hook for bench.py ---------------------------------------------------- */
 /* When enabled, every encode / decode call brackets its kernels with HIP events on the
  * context's stream; dbde_hip_timing_read returns accumulated milliseconds and launch counts
