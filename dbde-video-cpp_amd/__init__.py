@@ -60,6 +60,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_project", "dbde_hip_project_plan", "dbde16_hip_project", "dbde16_hip_project_plan",
     "dbde_hip_trace_map_summary", "dbde_hip_trace_map_create", "dbde_hip_trace_map_destroy", "dbde_hip_trace_map_info",
     "dbde_hip_trace_map_pixels", "dbde_hip_traces", "dbde16_hip_traces", "dbde_hip_trace_plan", "dbde16_hip_trace_plan",
+    "dbde_hip_histogram", "dbde16_hip_histogram", "dbde_hip_histogram_plan", "dbde16_hip_histogram_plan",
 ]
 
 
@@ -197,6 +198,12 @@ def lib():
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_trace_plan", "dbde16_hip_trace_plan"):
         getattr(L, fn).argtypes = [i, i, i, C.POINTER(TraceMapInfo), C.c_uint, i, C.POINTER(TracePlan)]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_histogram", "dbde16_hip_histogram"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, i, i, i, vp, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_histogram_plan", "dbde16_hip_histogram_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, i, C.c_uint, i, C.POINTER(HistogramPlan)]
         getattr(L, fn).restype = i
     L.dbde_hip_unpack_frame.argtypes = [vp, C.POINTER(vp), i, i, vp]
     L.dbde_hip_pack_frame_header.restype = sz
@@ -692,6 +699,98 @@ class Traces:
         return (self.sumsq.to(torch.float64) / n - m * m).clamp_(min=0.0).sqrt_()
 
 
+HIST_OUTPUTS = {"rows": 1, "total": 2}
+
+
+def max_bins(pix, shift=0):
+    """The most bins a histogram may have: 256 >> shift (DBDE, pix 1), min(4096, 65536 >> shift) (DBDE16, pix 2)."""
+    return (256 >> shift) if pix == 1 else min(4096, 65536 >> shift)
+
+
+class HistogramPlan(C.Structure):
+    """dbde_hip_histogram_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32),
+                ("index_split", C.c_uint32), ("threads", C.c_uint32), ("tiles_per_piece", C.c_uint32),
+                ("pieces_x", C.c_uint32), ("pieces", C.c_uint32), ("segments", C.c_uint32),
+                ("pieces_per_segment", C.c_uint32), ("lds_bins", C.c_uint32), ("lds_copies", C.c_uint32),
+                ("lds_bytes", C.c_uint32), ("reserved_", C.c_uint32), ("grid", C.c_uint64), ("init_grid", C.c_uint64),
+                ("global_atomics_per_frame", C.c_uint64), ("workspace_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved_"}
+
+
+def _histogram_plan(fn, pix, W, H, n_frames, x, y, rw, rh, shift, bins, per_frame, total, n_cu):
+    """histogram_plan / histogram16_plan through the C function named fn."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    if bins is None:   # the most allowed (0, rejected, for a shift outside the rules)
+        bins = max_bins(pix, shift) if 0 <= shift < 8 * pix else 0
+    outputs = (1 if per_frame else 0) | (2 if total else 0)
+    pl = HistogramPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, x, y, rw, rh, shift, bins, outputs, n_cu, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, shift={shift}, bins={bins}, "
+                         f"outputs={outputs}) -> {rc}")
+    return pl.as_dict()
+
+
+def histogram_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, shift=0, bins=None, per_frame=True, total=False,
+                   n_cu=256):
+    """dbde_hip_histogram_plan: the tile window, index geometry, launch, LDS and workspace of Codec.histogram (host
+    arithmetic only).  rw / rh default to the rest of the frame, bins to the most allowed.  Raises ValueError where
+    dbde_hip_histogram would return DBDE_HIP_ERR_ARG."""
+    return _histogram_plan("dbde_hip_histogram_plan", 1, W, H, n_frames, x, y, rw, rh, shift, bins, per_frame, total,
+                           n_cu)
+
+
+def histogram16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, shift=0, bins=None, per_frame=True, total=False,
+                     n_cu=256):
+    """dbde16_hip_histogram_plan: histogram_plan for DBDE16 histograms (Codec.histogram16)."""
+    return _histogram_plan("dbde16_hip_histogram_plan", 2, W, H, n_frames, x, y, rw, rh, shift, bins, per_frame, total,
+                           n_cu)
+
+
+class Histograms:
+    """Device tensors of per-frame histograms (Codec.histogram): counts int32 (n, bins) (the U32 counts, at most
+    2^30), total int64 (bins,), count int64 (1,).  An output that was not asked for is None.  shift, bins and pixels
+    (= rw * rh, the pixels of one frame's window) describe the binning: value v is in bin min(v >> shift, bins - 1)."""
+
+    def __init__(self, counts=None, total=None, count=None, shift=0, bins=None, pixels=None):
+        self.counts, self.total, self.count = counts, total, count
+        self.shift, self.bins, self.pixels = shift, bins, pixels
+
+    @classmethod
+    def empty(cls, n, bins, device, shift=0, pixels=None, per_frame=True, total=False):
+        """Zeroed outputs (a rejected frame's row then reads 0)."""
+        return cls(torch.zeros((n, bins), dtype=torch.int32, device=device) if per_frame else None,
+                   torch.zeros(bins, dtype=torch.int64, device=device) if total else None,
+                   torch.zeros(1, dtype=torch.int64, device=device) if total else None,
+                   shift=shift, bins=bins, pixels=pixels)
+
+    @staticmethod
+    def _quantile(h, q, shift):
+        """Per row of h (int64, (..., bins)): the lower edge b << shift of the bin holding the k-th smallest value,
+        k = floor(q * (N - 1)) with N the row's sum; -1 for an all-zero row."""
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f"q must lie in [0, 1], not {q!r}")
+        c = torch.cumsum(h, dim=-1)
+        n = c[..., -1:]
+        k = torch.floor(q * (n - 1).clamp(min=0).to(torch.float64)).to(torch.int64)
+        b = torch.searchsorted(c, k, right=True).squeeze(-1)
+        return torch.where(n.squeeze(-1) > 0, b << shift, torch.full_like(b, -1))
+
+    def quantile(self, q):
+        """Per frame (int64, (n,)): the value of the k-th smallest pixel, k = floor(q * (pixels - 1)) (0-based), as its
+        bin's lower edge b << shift; -1 for an all-zero row (a rejected frame)."""
+        return self._quantile(self.counts.to(torch.int64), q, self.shift)
+
+    def total_quantile(self, q):
+        """quantile(q) of the total over the accepted frames (an int64 scalar tensor; -1 when it is empty)."""
+        return self._quantile(self.total.to(torch.int64), q, self.shift)
+
+
 class DbdeError(RuntimeError):
     pass
 
@@ -827,6 +926,46 @@ class Codec:
         its statistics are the ones computed.  Returns (Projection, results (n, 4) int64) like decode_frames."""
         return self._project("dbde_hip_project", 1, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh,
                              stats, out, accumulate, results)
+
+    def _histogram(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, shift, bins,
+                   per_frame, total, out, accumulate, results):
+        """histogram / histogram16 through the C function named fn."""
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        if bins is None:
+            bins = out.bins if out is not None and out.bins is not None else max_bins(pix, shift)
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out= (the histograms to continue)")
+            out = Histograms.empty(max(n, 0), bins, self.device, shift=shift, pixels=rw * rh, per_frame=per_frame,
+                                   total=total)
+        else:
+            out.shift, out.bins, out.pixels = shift, bins, rw * rh
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                 W, H, n, x, y, rw, rh, shift, bins, 1 if accumulate else 0, ptr(out.counts),
+                                 ptr(out.total), ptr(out.count), ptr(results) if n > 0 else None)
+        self._check(rc, fn)
+        return out, results
+
+    def histogram(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x=0, y=0, rw=None, rh=None, shift=0,
+                  bins=None, per_frame=True, total=False, out=None, accumulate=False, results=None):
+        """Per-frame histograms of the rw x rh window at (x, y) of n frames (frame f at
+        stream.data_ptr()+stream_offset+offsets[f]): value v counts in bin min(v >> shift, bins - 1).  rw / rh default
+        to the rest of the frame, bins to 256 >> shift.  per_frame: the (n, bins) rows; total: the sum over the accepted
+        frames and their number (accumulate=True adds to out's).  out: a Histograms to write into.
+        Returns (Histograms, results (n, 4) int64) like decode_frames."""
+        return self._histogram("dbde_hip_histogram", 1, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw,
+                               rh, shift, bins, per_frame, total, out, accumulate, results)
+
+    def histogram16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x=0, y=0, rw=None, rh=None, shift=0,
+                    bins=None, per_frame=True, total=False, out=None, accumulate=False, results=None):
+        """DBDE16 per-frame histograms: histogram's arguments and results over U16 values; bins default to
+        min(4096, 65536 >> shift)."""
+        return self._histogram("dbde16_hip_histogram", 2, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y,
+                               rw, rh, shift, bins, per_frame, total, out, accumulate, results)
 
     def trace_map(self, labels, n_labels=None):
         """A TraceMap of this codec from a label image (H, W): numpy, or a torch tensor on any device; 0 = no region,

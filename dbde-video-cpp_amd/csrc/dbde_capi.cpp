@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "dbde16_kernels.h"
+#include "dbde_hist_kernels.h"
 #include "dbde_kernels.h"
 #include "dbde_project_kernels.h"
 #include "dbde_roi_kernels.h"
@@ -1434,6 +1435,164 @@ int dbde16_hip_traces(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_
                       uint64_t *d_sum, uint64_t *d_sumsq, dbde_hip_frame_result *d_results) {
     return traces_common(ctx, "traces16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, map, d_max,
                          d_min, d_sum, d_sumsq, d_results);
+}
+
+// ---- per-frame histograms ---------------------------------------------------------------------------------
+struct HistPlan {
+    RoiPlan roi;                      // arguments, tile window and index geometry: the window decoder's (plan_roi)
+    uint32_t pieces_x, pieces, segments, pps, lds_bins;
+    uint64_t grid, init_grid, atomics, workspace;
+};
+// A segment is cut only to fill the device (about 16 workgroups per CU) and never below the pieces whose pixels
+// outnumber its flush 64 times (64 * bins pixels, and at least kHistMinPieces pieces).
+static constexpr uint32_t kHistMinPieces = 16;
+static const char *plan_histogram(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins,
+                                  unsigned outputs, int n_cu, uint32_t pix, HistPlan &pl) {
+    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, pix == 2u ? kRoi16WideThreads : kRoiWideThreads))
+        return why;
+    const int max_shift = pix == 1u ? 7 : 15;
+    if (shift < 0 || shift > max_shift) return "shift outside [0, 7] (DBDE) / [0, 15] (DBDE16)";
+    const uint32_t range = (pix == 1u ? 256u : 65536u) >> shift;
+    const uint32_t most = pix == 1u ? range : (range < kHistLargeBins ? range : kHistLargeBins);
+    if (bins < 1 || (uint32_t)bins > most) return "bins outside [1, 256 >> shift] (DBDE) / [1, min(4096, 65536 >> shift)] (DBDE16)";
+    if (outputs < 1u || outputs > 3u) return "no output (or an unknown one) requested";
+    const uint32_t tiles = kHistTilesOf(pix);
+    pl.pieces_x = (pl.roi.ntx + tiles - 1u) / tiles;
+    pl.pieces = pl.pieces_x * pl.roi.nty;
+    pl.lds_bins = kHistLdsBinsOf((uint32_t)bins);
+    const uint64_t n = (uint64_t)n_frames;
+    const uint64_t px_piece = 64ull * tiles;
+    uint64_t min_pieces = (64ull * (uint64_t)bins + px_piece - 1u) / px_piece;
+    if (min_pieces < kHistMinPieces) min_pieces = kHistMinPieces;
+    const uint64_t target = 16ull * (uint64_t)(n_cu > 0 ? n_cu : 1);
+    uint64_t seg = (target + (n > 0 ? n : 1) - 1u) / (n > 0 ? n : 1);
+    const uint64_t by_len = (pl.pieces + min_pieces - 1u) / min_pieces;
+    if (seg > by_len) seg = by_len;
+    if (seg < 1u) seg = 1u;
+    const uint64_t pps = (pl.pieces + seg - 1u) / seg;
+    seg = (pl.pieces + pps - 1u) / pps;   // no empty segment
+    pl.segments = (uint32_t)seg;
+    pl.pps = (uint32_t)pps;
+    pl.grid = n * seg;
+    if (pl.grid >= (1ull << 31)) return "too many workgroups in one call";
+    const uint64_t rows = (n > 0 ? n : 1) * (uint64_t)bins;
+    pl.init_grid = (rows + kHistRowThreads - 1u) / kHistRowThreads;
+    if (pl.init_grid >= (1ull << 31)) return "too many workgroups in one call";
+    pl.atomics = seg * (uint64_t)bins * (uint64_t)(((outputs & 1u) ? 1u : 0u) + ((outputs & 2u) ? 1u : 0u));
+    pl.workspace = n * (pl.roi.dg.cpf + 1u) * 4u + n * 4u;
+    return nullptr;
+}
+
+static int histogram_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins,
+                                 unsigned outputs, int n_cu, uint32_t pix, dbde_hip_histogram_plan_t *plan) {
+    HistPlan pl;
+    if (!plan || n_cu < 1 || plan_histogram(W, H, n_frames, x0, y0, rw, rh, shift, bins, outputs, n_cu, pix, pl))
+        return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->tile_x = (int32_t)pl.roi.tx0;
+    plan->tile_y = (int32_t)pl.roi.ty0;
+    plan->tiles_x = (int32_t)pl.roi.ntx;
+    plan->tiles_y = (int32_t)pl.roi.nty;
+    plan->chunks_per_frame = pl.roi.dg.cpf;
+    plan->chunk_tiles = pl.roi.dg.ct;
+    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
+    plan->index_split = pl.roi.split;
+    plan->threads = kHistThreads;
+    plan->tiles_per_piece = kHistTilesOf(pix);
+    plan->pieces_x = pl.pieces_x;
+    plan->pieces = pl.pieces;
+    plan->segments = pl.segments;
+    plan->pieces_per_segment = pl.pps;
+    plan->lds_bins = pl.lds_bins;
+    plan->lds_copies = kHistCopiesOf(pl.lds_bins);
+    plan->lds_bytes = kHistLdsBytesOf(pl.lds_bins);
+    plan->grid = pl.grid;
+    plan->init_grid = pl.init_grid;
+    plan->global_atomics_per_frame = pl.atomics;
+    plan->workspace_bytes = pl.workspace;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_histogram_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins,
+                            unsigned outputs, int n_cu, dbde_hip_histogram_plan_t *plan) {
+    return histogram_plan_common(W, H, n_frames, x0, y0, rw, rh, shift, bins, outputs, n_cu, 1u, plan);
+}
+
+int dbde16_hip_histogram_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins,
+                              unsigned outputs, int n_cu, dbde_hip_histogram_plan_t *plan) {
+    return histogram_plan_common(W, H, n_frames, x0, y0, rw, rh, shift, bins, outputs, n_cu, 2u, plan);
+}
+
+// Both histograms: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the histogram kernels
+// in slot 2.
+static int histogram_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
+                            size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
+                            int y0, int rw, int rh, int shift, int bins, int accumulate, uint32_t *d_hist,
+                            uint64_t *d_total, uint64_t *d_count, dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    const unsigned outputs = (d_hist ? 1u : 0u) | (d_total ? 2u : 0u);
+    HistPlan pl;
+    if (const char *why = plan_histogram(W, H, n_frames, x0, y0, rw, rh, shift, bins, outputs, ctx->n_cu, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d shift %d bins %d)", name, why,
+                    W, H, n_frames, rw, rh, x0, y0, shift, bins);
+    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if (d_total && !d_count) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: d_total needs d_count", name);
+    if ((reinterpret_cast<uintptr_t>(d_total) | reinterpret_cast<uintptr_t>(d_count)) & 7u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U64 outputs must be 8-byte aligned", name);
+    if (reinterpret_cast<uintptr_t>(d_hist) & 3u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U32 rows must be 4-byte aligned", name);
+    if (n_frames == 0 && (accumulate || !d_total)) return DBDE_HIP_OK;   // nothing to add or to reset
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n_frames > 0) {
+        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
+        if (rc) return rc;
+    }
+    HistParams p;
+    memset(&p, 0, sizeof p);
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.n_frames = (uint32_t)n_frames;
+    p.x0 = x0;
+    p.y0 = y0;
+    p.rw = rw;
+    p.rh = rh;
+    p.T = pl.roi.g.T;
+    p.w = pl.roi.g.w;
+    p.geom = pl.roi.dg;
+    p.tx0 = pl.roi.tx0;
+    p.ty0 = pl.roi.ty0;
+    p.rows = pl.roi.nty;
+    p.pieces = pl.pieces_x;
+    p.segments = pl.segments;
+    p.pps = pl.pps;
+    p.shift = (uint32_t)shift;
+    p.bins = (uint32_t)bins;
+    p.accumulate = accumulate ? 1 : 0;
+    p.out_hist = d_hist;
+    p.out_total = d_total;
+    p.out_count = d_total ? d_count : nullptr;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_histogram(p, pix, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_histogram(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+                       int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins, int accumulate,
+                       uint32_t *d_hist, uint64_t *d_total, uint64_t *d_count, dbde_hip_frame_result *d_results) {
+    return histogram_common(ctx, "histogram", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
+                            rh, shift, bins, accumulate, d_hist, d_total, d_count, d_results);
+}
+
+int dbde16_hip_histogram(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                         const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                         int shift, int bins, int accumulate, uint32_t *d_hist, uint64_t *d_total, uint64_t *d_count,
+                         dbde_hip_frame_result *d_results) {
+    return histogram_common(ctx, "histogram16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
+                            rh, shift, bins, accumulate, d_hist, d_total, d_count, d_results);
 }
 
 int dbde_hip_index_stream_async(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, int W, int H,

@@ -624,6 +624,79 @@ int dbde_hip_trace_plan(int W, int H, int n_frames, const dbde_hip_trace_map_inf
 int dbde16_hip_trace_plan(int W, int H, int n_frames, const dbde_hip_trace_map_info_t *info, unsigned stats, int n_cu,
                           dbde_hip_trace_plan_t *plan);
 
+/* ---- per-frame intensity histograms ------------------------------------------------------------- */
+/* Histograms: for each frame f of n_frames, the counts of the values of the rw x rh window at (x0, y0), counted
+ * straight from the compressed bytes (no image is written).
+ * Inputs:
+ *   Frame f starts at d_stream + d_frame_offsets[f] (any byte alignment; concatenated and slot layouts alike).  No byte
+ *   at or beyond stream_bytes is read.  The window and its argument rules are dbde_hip_decode_roi's (plan_roi); there
+ *   are no per-frame origins.  The whole frame is 0, 0, W, H.
+ * Binning: a pixel value v goes to bin min(v >> shift, bins - 1); the last bin also collects every value above the
+ *   range (the saturation bin).  DBDE: 0 <= shift <= 7 and 1 <= bins <= 256 >> shift.  The values binned are exactly
+ *   the bytes dbde_hip_decode_frames writes (minima that wrap modulo 256 included), for the frames it accepts.
+ * Outputs (at least one of d_hist / d_total; a NULL output is neither computed nor touched):
+ *   d_hist   U32 [n_frames][bins], 4-byte aligned.  An accepted frame's row is overwritten with its counts, which sum
+ *            to rw * rh (at most 2^30 by the index limit, so U32 is exact).  A rejected frame reports its usual
+ *            d_results entry and its row is left untouched.
+ *   d_total  U64 [bins], 8-byte aligned, with d_count (one U64, 8-byte aligned, required with d_total): the sum of the
+ *            accepted frames' rows and the number of those frames.  accumulate = 0 overwrites them (all zeros for
+ *            n_frames == 0 or an all-rejected batch); accumulate = 1 adds to them (n_frames == 0 changes nothing).
+ *            Frames [0, n) in one call give the same as any split into consecutive calls with accumulate = 1.
+ *   d_results (optional) is filled exactly as dbde_hip_decode_frames fills it.  Nothing outside the outputs is written.
+ * Every count is an exact integer, independent of the launch shape and of workgroup order (integer atomics).
+ * Errors: DBDE_HIP_ERR_ARG as dbde_hip_project (window, sizes, null stream / offsets), and for shift / bins outside
+ *   the rules, no output, a d_total without d_count, or an unaligned output.
+ * Asynchronous on the context's stream; workspace (the decode index) is the context's, grown on demand.  Timing hook:
+ *   the index kernel in slot 1, the histogram kernels in slot 2. */
+int dbde_hip_histogram(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                       const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                       int x0, int y0, int rw, int rh, int shift, int bins, int accumulate,
+                       uint32_t *d_hist, uint64_t *d_total, uint64_t *d_count,
+                       dbde_hip_frame_result *d_results);
+/* Histograms of DBDE16 frames: dbde_hip_histogram's contract with U16 values.  Validation is dbde16_hip_decode_frames'
+ * own; the values binned are exactly the U16 values it writes (minima that wrap modulo 2^16 included).  Binning:
+ * 0 <= shift <= 15 and 1 <= bins <= min(4096, 65536 >> shift): shift 0 with 4096 bins bins 12-bit data exactly,
+ * shift 4 with 4096 bins covers the whole 16-bit range. */
+int dbde16_hip_histogram(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                         const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                         int x0, int y0, int rw, int rh, int shift, int bins, int accumulate,
+                         uint32_t *d_hist, uint64_t *d_total, uint64_t *d_count,
+                         dbde_hip_frame_result *d_results);
+/* What dbde_hip_histogram runs (pure host arithmetic, like dbde_hip_project_plan): validates exactly what
+ * dbde_hip_histogram validates of its arguments (DBDE_HIP_ERR_ARG otherwise) and reports the tile window and index
+ * geometry (dbde_hip_roi_plan's), the histogram launch, its LDS and the workspace.  outputs: bitmask, per-frame rows 1,
+ * total 2 (dbde_hip_histogram: its non-NULL d_hist / d_total).  n_cu: compute units of the device (dbde_hip_histogram
+ * uses its context's). */
+enum { DBDE_HIP_HISTOGRAM_ROWS = 1, DBDE_HIP_HISTOGRAM_TOTAL = 2 };
+typedef struct dbde_hip_histogram_plan_t {
+    int32_t tile_x, tile_y;           /* first tile column / row of the window */
+    int32_t tiles_x, tiles_y;         /* tiles across / down the window covers */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t threads;                 /* histogram kernel: workgroup size */
+    uint32_t tiles_per_piece;         /* histogram kernel: tiles of one piece (8 lanes per tile; DBDE16: 16) */
+    uint32_t pieces_x;                /* pieces across a window tile row */
+    uint32_t pieces;                  /* pieces of one frame's window: pieces_x * tiles_y */
+    uint32_t segments;                /* workgroups per frame, each counting a run of consecutive pieces */
+    uint32_t pieces_per_segment;      /* pieces of every segment but the last (which may hold fewer) */
+    uint32_t lds_bins;                /* bins of the kernel instance's LDS histogram (256, or 4096 for DBDE16) */
+    uint32_t lds_copies;              /* copies of it per workgroup (one per wave, or one shared) */
+    uint32_t lds_bytes;               /* LDS per workgroup (histogram copies and the offsets scan) */
+    uint32_t reserved_;
+    uint64_t grid;                    /* histogram kernel: n_frames * segments workgroups */
+    uint64_t init_grid;               /* init kernel: workgroups over max(n_frames, 1) * bins */
+    uint64_t global_atomics_per_frame;/* at most: segments * bins per requested output */
+    uint64_t workspace_bytes;         /* the decode index: chunk offsets and frame verdicts */
+} dbde_hip_histogram_plan_t;
+int dbde_hip_histogram_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins,
+                            unsigned outputs, int n_cu, dbde_hip_histogram_plan_t *plan);
+/* The same for dbde16_hip_histogram: 16 lanes per tile (half the tiles per piece), its bins / shift rules, and the
+ * 4096-bin LDS instance (one shared copy) for more than 256 bins. */
+int dbde16_hip_histogram_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins,
+                              unsigned outputs, int n_cu, dbde_hip_histogram_plan_t *plan);
+
 /* ---- kernel timing hook for bench.py ---------------------------------------------------- */
 /* When enabled, every encode / decode call brackets its kernels with HIP events on the
  * context's stream; dbde_hip_timing_read returns accumulated milliseconds and launch counts
