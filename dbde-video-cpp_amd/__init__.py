@@ -61,6 +61,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_trace_map_summary", "dbde_hip_trace_map_create", "dbde_hip_trace_map_destroy", "dbde_hip_trace_map_info",
     "dbde_hip_trace_map_pixels", "dbde_hip_traces", "dbde16_hip_traces", "dbde_hip_trace_plan", "dbde16_hip_trace_plan",
     "dbde_hip_histogram", "dbde16_hip_histogram", "dbde_hip_histogram_plan", "dbde16_hip_histogram_plan",
+    "dbde_hip_decode_binned", "dbde16_hip_decode_binned", "dbde_hip_binned_plan", "dbde16_hip_binned_plan",
 ]
 
 
@@ -204,6 +205,12 @@ def lib():
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_histogram_plan", "dbde16_hip_histogram_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, i, C.c_uint, i, C.POINTER(HistogramPlan)]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_decode_binned", "dbde16_hip_decode_binned"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, i, vp, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_binned_plan", "dbde16_hip_binned_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, C.c_uint, C.POINTER(BinnedPlan)]
         getattr(L, fn).restype = i
     L.dbde_hip_unpack_frame.argtypes = [vp, C.POINTER(vp), i, i, vp]
     L.dbde_hip_pack_frame_header.restype = sz
@@ -702,6 +709,95 @@ class Traces:
 HIST_OUTPUTS = {"rows": 1, "total": 2}
 
 
+BINNED_STATS = {"sum": 1, "max": 2, "min": 4}
+
+
+def binned_mask(stats):
+    """("sum", "max", "min") names (or an int bitmask) -> dbde_hip_binned_plan's bitmask."""
+    if isinstance(stats, int):
+        return stats
+    if isinstance(stats, str):
+        stats = (stats,)
+    mask = 0
+    for name in stats:
+        if name not in BINNED_STATS:
+            raise ValueError(f"unknown statistic {name!r} (one of {sorted(BINNED_STATS)})")
+        mask |= BINNED_STATS[name]
+    return mask
+
+
+class BinnedPlan(C.Structure):
+    """dbde_hip_binned_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32),
+                ("index_split", C.c_uint32), ("out_w", C.c_uint32), ("out_h", C.c_uint32), ("threads", C.c_uint32),
+                ("pieces_x", C.c_uint32), ("lds_bytes", C.c_uint32), ("reserved_", C.c_uint32), ("grid", C.c_uint64),
+                ("sum_bytes", C.c_uint64), ("max_bytes", C.c_uint64), ("min_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved_"}
+
+
+def _binned_plan(fn, W, H, n_frames, bin, x, y, rw, rh, stats):
+    """binned_plan / binned16_plan through the C function named fn."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    pl = BinnedPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, x, y, rw, rh, bin, binned_mask(stats), C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, bin={bin}, stats={stats!r}) -> {rc}")
+    return pl.as_dict()
+
+
+def binned_plan(W, H, n_frames, bin, x=0, y=0, rw=None, rh=None, stats=("sum",)):
+    """dbde_hip_binned_plan: the tile window, index geometry, plane shape and bytes, launch and LDS of
+    Codec.decode_binned (host arithmetic only).  rw / rh default to the rest of the frame.  Raises ValueError where
+    dbde_hip_decode_binned would return DBDE_HIP_ERR_ARG."""
+    return _binned_plan("dbde_hip_binned_plan", W, H, n_frames, bin, x, y, rw, rh, stats)
+
+
+def binned16_plan(W, H, n_frames, bin, x=0, y=0, rw=None, rh=None, stats=("sum",)):
+    """dbde16_hip_binned_plan: binned_plan for DBDE16 frames (Codec.decode_binned16)."""
+    return _binned_plan("dbde16_hip_binned_plan", W, H, n_frames, bin, x, y, rw, rh, stats)
+
+
+def bin_pixels(rh, rw, bin, device=None):
+    """int32 (ceil(rh / bin), ceil(rw / bin)): the pixels of each bin of an rw x rh window; bin * bin except in the
+    last row and column, whose bins end at the window's edge."""
+    ny = torch.arange(0, rh, bin, dtype=torch.int32, device=device).neg_().add_(rh).clamp_(max=bin)
+    nx = torch.arange(0, rw, bin, dtype=torch.int32, device=device).neg_().add_(rw).clamp_(max=bin)
+    return ny[:, None] * nx[None, :]
+
+
+class Binned:
+    """Device tensors of a binned decode (Codec.decode_binned): per frame, the sum / max / min of every bin x bin block
+    of the window, each (n, oh, ow).  DBDE: sum int16 (at most 64 * 255), max / min uint8.  DBDE16: sum int32 (at most
+    64 * 65535), max / min int16 tensors holding the U16 bits (as decode_frames16 returns its images).  A statistic that
+    was not asked for is None.  bin is the bin's side; pixels (int32, (oh, ow)) each bin's pixel count: bin * bin
+    except on the window's right and bottom edge."""
+
+    def __init__(self, sum=None, max=None, min=None, bin=None, pixels=None):
+        self.sum, self.max, self.min, self.bin, self.pixels = sum, max, min, bin, pixels
+
+    @classmethod
+    def empty(cls, n, rh, rw, bin, stats, device, pix=1):
+        """Zeroed outputs for `stats` (a rejected frame's planes then read 0); pix: bytes per pixel (1: DBDE, 2: DBDE16)."""
+        mask = binned_mask(stats)
+        if pix not in (1, 2):
+            raise ValueError(f"pix must be 1 or 2, not {pix!r}")
+        if bin not in (2, 4, 8):
+            raise ValueError(f"bin must be 2, 4 or 8, not {bin!r}")
+        oh, ow = -(-rh // bin), -(-rw // bin)
+        sum_dtype, mm_dtype = (torch.int16, torch.uint8) if pix == 1 else (torch.int32, torch.int16)
+        plane = lambda dt: torch.zeros((n, oh, ow), dtype=dt, device=device)   # noqa: E731
+        return cls(plane(sum_dtype) if mask & 1 else None, plane(mm_dtype) if mask & 2 else None,
+                   plane(mm_dtype) if mask & 4 else None, bin=bin, pixels=bin_pixels(rh, rw, bin, device))
+
+    def mean(self):
+        """Per-bin mean (float32, (n, oh, ow)): sum / pixels."""
+        return self.sum.to(torch.float32) / self.pixels.to(torch.float32)
+
+
 def max_bins(pix, shift=0):
     """The most bins a histogram may have: 256 >> shift (DBDE, pix 1), min(4096, 65536 >> shift) (DBDE16, pix 2)."""
     return (256 >> shift) if pix == 1 else min(4096, 65536 >> shift)
@@ -966,6 +1062,45 @@ class Codec:
         min(4096, 65536 >> shift)."""
         return self._histogram("dbde16_hip_histogram", 2, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y,
                                rw, rh, shift, bins, per_frame, total, out, accumulate, results)
+
+    def _decode_binned(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, bin, x, y, rw, rh, stats,
+                       out, results):
+        """decode_binned / decode_binned16 through the C function named fn."""
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        if out is None:
+            out = Binned.empty(max(n, 0), rh, rw, bin, stats, self.device, pix=pix)
+        else:
+            out.bin, out.pixels = bin, bin_pixels(rh, rw, bin, self.device)
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        if n == 0:   # nothing to do (empty planes have no address to pass): the arguments are still checked
+            mask = (1 if out.sum is not None else 0) | (2 if out.max is not None else 0) | (4 if out.min is not None else 0)
+            _binned_plan(fn.replace("decode_binned", "binned_plan"), W, H, 0, bin, x, y, rw, rh, mask)
+            return out, results
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                 W, H, n, x, y, rw, rh, bin, ptr(out.sum), ptr(out.max), ptr(out.min),
+                                 ptr(results) if n > 0 else None)
+        self._check(rc, fn)
+        return out, results
+
+    def decode_binned(self, stream, stream_offset, stream_bytes, offsets, W, H, n, bin, x=0, y=0, rw=None, rh=None,
+                      stats=("sum",), out=None, results=None):
+        """Binned decode of the rw x rh window at (x, y) of n frames (frame f at
+        stream.data_ptr()+stream_offset+offsets[f]): the sum, max and min of every bin x bin block (bin 2, 4 or 8; x and
+        y multiples of bin), bins on the right and bottom edge ending at the window's edge.  rw / rh default to the rest
+        of the frame.  out: a Binned to write into; its planes are the ones computed (stats is then ignored).
+        Returns (Binned, results (n, 4) int64) like decode_frames."""
+        return self._decode_binned("dbde_hip_decode_binned", 1, stream, stream_offset, stream_bytes, offsets, W, H, n,
+                                   bin, x, y, rw, rh, stats, out, results)
+
+    def decode_binned16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, bin, x=0, y=0, rw=None, rh=None,
+                        stats=("sum",), out=None, results=None):
+        """DBDE16 binned decode: decode_binned's arguments and results over U16 pixels (sum int32, max / min int16
+        tensors holding the U16 bits)."""
+        return self._decode_binned("dbde16_hip_decode_binned", 2, stream, stream_offset, stream_bytes, offsets, W, H, n,
+                                   bin, x, y, rw, rh, stats, out, results)
 
     def trace_map(self, labels, n_labels=None):
         """A TraceMap of this codec from a label image (H, W): numpy, or a torch tensor on any device; 0 = no region,

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "dbde16_kernels.h"
+#include "dbde_binned_kernels.h"
 #include "dbde_hist_kernels.h"
 #include "dbde_kernels.h"
 #include "dbde_project_kernels.h"
@@ -1593,6 +1594,129 @@ int dbde16_hip_histogram(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stre
                          dbde_hip_frame_result *d_results) {
     return histogram_common(ctx, "histogram16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
                             rh, shift, bins, accumulate, d_hist, d_total, d_count, d_results);
+}
+
+// ---- binned decode -----------------------------------------------------------------------------------------
+struct BinnedPlan {
+    RoiPlan roi;                      // arguments, tile window and index geometry: the window decoder's (plan_roi)
+    uint32_t threads, pieces, ow, oh;
+    uint64_t grid, sum_bytes, mm_bytes;
+};
+static const char *plan_binned(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int bin, unsigned stats,
+                               uint32_t pix, BinnedPlan &pl) {
+    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, kBinWideThreadsOf(pix))) return why;
+    if (bin != 2 && bin != 4 && bin != 8) return "bin other than 2, 4, 8";
+    if (x0 % bin || y0 % bin) return "window origin not a multiple of the bin";
+    if (stats < 1u || stats > 7u) return "no statistic (or an unknown one) requested";
+    pl.threads = pl.roi.ntx <= kBinNarrowThreads ? kBinNarrowThreads : kBinWideThreadsOf(pix);
+    pl.pieces = (pl.roi.ntx + pl.threads - 1u) / pl.threads;
+    pl.ow = ((uint32_t)rw + (uint32_t)bin - 1u) / (uint32_t)bin;
+    pl.oh = ((uint32_t)rh + (uint32_t)bin - 1u) / (uint32_t)bin;
+    pl.grid = (uint64_t)n_frames * pl.roi.nty * pl.pieces;   // below 2^31: at most plan_roi's grid_origins
+    const uint64_t elems = (uint64_t)n_frames * pl.oh * pl.ow;
+    pl.sum_bytes = elems * 2u * pix;
+    pl.mm_bytes = elems * pix;
+    return nullptr;
+}
+
+static int binned_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int bin, unsigned stats,
+                              uint32_t pix, dbde_hip_binned_plan_t *plan) {
+    BinnedPlan pl;
+    if (!plan || plan_binned(W, H, n_frames, x0, y0, rw, rh, bin, stats, pix, pl)) return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->tile_x = (int32_t)pl.roi.tx0;
+    plan->tile_y = (int32_t)pl.roi.ty0;
+    plan->tiles_x = (int32_t)pl.roi.ntx;
+    plan->tiles_y = (int32_t)pl.roi.nty;
+    plan->chunks_per_frame = pl.roi.dg.cpf;
+    plan->chunk_tiles = pl.roi.dg.ct;
+    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
+    plan->index_split = pl.roi.split;
+    plan->out_w = pl.ow;
+    plan->out_h = pl.oh;
+    plan->threads = pl.threads;
+    plan->pieces_x = pl.pieces;
+    plan->lds_bytes = kBinLdsBytesOf(pl.threads, pix);
+    plan->grid = pl.grid;
+    plan->sum_bytes = (stats & DBDE_HIP_BINNED_SUM) ? pl.sum_bytes : 0u;
+    plan->max_bytes = (stats & DBDE_HIP_BINNED_MAX) ? pl.mm_bytes : 0u;
+    plan->min_bytes = (stats & DBDE_HIP_BINNED_MIN) ? pl.mm_bytes : 0u;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_binned_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int bin, unsigned stats,
+                         dbde_hip_binned_plan_t *plan) {
+    return binned_plan_common(W, H, n_frames, x0, y0, rw, rh, bin, stats, 1u, plan);
+}
+
+int dbde16_hip_binned_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int bin, unsigned stats,
+                           dbde_hip_binned_plan_t *plan) {
+    return binned_plan_common(W, H, n_frames, x0, y0, rw, rh, bin, stats, 2u, plan);
+}
+
+// Both binned decoders: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the binning kernel
+// in slot 2.
+static int decode_binned_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
+                                size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
+                                int y0, int rw, int rh, int bin, void *d_sum, void *d_max, void *d_min,
+                                dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    const unsigned stats = (d_sum ? DBDE_HIP_BINNED_SUM : 0u) | (d_max ? DBDE_HIP_BINNED_MAX : 0u) | (d_min ? DBDE_HIP_BINNED_MIN : 0u);
+    BinnedPlan pl;
+    if (const char *why = plan_binned(W, H, n_frames, x0, y0, rw, rh, bin, stats, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d bin %d)", name, why, W, H,
+                    n_frames, rw, rh, x0, y0, bin);
+    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if (reinterpret_cast<uintptr_t>(d_sum) & (2u * pix - 1u))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the sum plane must be %u-byte aligned", name, 2u * pix);
+    if ((reinterpret_cast<uintptr_t>(d_max) | reinterpret_cast<uintptr_t>(d_min)) & (pix - 1u))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U16 planes must be 2-byte aligned", name);
+    if (n_frames == 0) return DBDE_HIP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
+    if (rc) return rc;
+    BinnedParams p;
+    memset(&p, 0, sizeof p);
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.x0 = x0;
+    p.y0 = y0;
+    p.rw = rw;
+    p.rh = rh;
+    p.w = pl.roi.g.w;
+    p.T = pl.roi.g.T;
+    p.geom = pl.roi.dg;
+    p.tx0 = pl.roi.tx0;
+    p.ty0 = pl.roi.ty0;
+    p.rows = pl.roi.nty;
+    p.pieces = pl.pieces;
+    p.ow = pl.ow;
+    p.oh = pl.oh;
+    p.out_sum = d_sum;
+    p.out_max = d_max;
+    p.out_min = d_min;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_decode_binned(p, (uint32_t)n_frames, pl.threads, pix, (uint32_t)bin, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_decode_binned(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                           int bin, uint16_t *d_sum, uint8_t *d_max, uint8_t *d_min, dbde_hip_frame_result *d_results) {
+    return decode_binned_common(ctx, "decode_binned", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0,
+                                y0, rw, rh, bin, d_sum, d_max, d_min, d_results);
+}
+
+int dbde16_hip_decode_binned(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                             const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                             int bin, uint32_t *d_sum, uint16_t *d_max, uint16_t *d_min,
+                             dbde_hip_frame_result *d_results) {
+    return decode_binned_common(ctx, "decode_binned16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0,
+                                y0, rw, rh, bin, d_sum, d_max, d_min, d_results);
 }
 
 int dbde_hip_index_stream_async(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, int W, int H,

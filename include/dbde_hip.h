@@ -697,6 +697,71 @@ int dbde_hip_histogram_plan(int W, int H, int n_frames, int x0, int y0, int rw, 
 int dbde16_hip_histogram_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins,
                               unsigned outputs, int n_cu, dbde_hip_histogram_plan_t *plan);
 
+/* ---- binned decode: b x b block sum, max and min per frame ------------------------------------- */
+/* Binned decode: for each frame f of n_frames, the rw x rh window at (x0, y0) reduced in bins of bin x bin pixels,
+ * straight from the compressed bytes (no image is written).
+ * Inputs:
+ *   Frame f starts at d_stream + d_frame_offsets[f] (any byte alignment; concatenated and slot layouts alike).  No byte
+ *   at or beyond stream_bytes is read.  bin is 2, 4 or 8.  The window and its argument rules are dbde_hip_decode_roi's
+ *   (plan_roi), and x0 and y0 must be multiples of bin, which keeps every bin inside one 8 x 8 tile; rw and rh are
+ *   free.  There are no per-frame origins.  The whole frame is 0, 0, W, H.
+ * Bins: the planes have oh = ceil(rh / bin) rows and ow = ceil(rw / bin) columns per frame.  Element (i, j) of frame f
+ *   reduces the pixels of rows [y0 + i bin, min(y0 + i bin + bin, y0 + rh)) and columns [x0 + j bin,
+ *   min(x0 + j bin + bin, x0 + rw)) of the image dbde_hip_decode_frames writes for that frame: exactly the bytes it
+ *   writes (minima that wrap modulo 256 included), for the frames it accepts.  Bins on the window's right and bottom
+ *   edge are partial: they reduce only the pixels inside the window, never the padding of an edge tile.
+ * Outputs (at least one; a NULL plane is neither computed nor touched), each [n_frames][oh][ow], row-major, pitch ow:
+ *   d_sum  U16, 2-byte aligned: the bin's sum, at most 64 * 255 = 16,320: exact.
+ *   d_max  U8: the bin's largest pixel.      d_min  U8: its smallest.
+ *   There is no mean plane: the mean is sum / pixels, and a bin's pixel count follows from the geometry alone.
+ *   A rejected frame reports its usual d_results entry and its planes are left untouched.  d_results (optional) is
+ *   filled exactly as dbde_hip_decode_frames fills it.  Nothing outside the planes is written.  n_frames == 0 does
+ *   nothing.
+ * Errors: DBDE_HIP_ERR_ARG as dbde_hip_decode_roi (window, sizes, null stream / offsets), and for a bin other than
+ *   2 / 4 / 8, an origin that is not a multiple of bin, no plane, or an unaligned d_sum.
+ * Asynchronous on the context's stream; workspace (the decode index) is the context's, grown on demand.  Timing hook:
+ *   the index kernel in slot 1, the binning kernel in slot 2. */
+int dbde_hip_decode_binned(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                           int x0, int y0, int rw, int rh, int bin,
+                           uint16_t *d_sum, uint8_t *d_max, uint8_t *d_min,
+                           dbde_hip_frame_result *d_results);
+/* Binned decode of DBDE16 frames: dbde_hip_decode_binned's contract with U16 pixels.  Validation is
+ * dbde16_hip_decode_frames' own; the values reduced are exactly the U16 values it writes (minima that wrap modulo 2^16
+ * included).  d_sum is U32, 4-byte aligned (at most 64 * 65,535 = 4,194,240: exact); d_max / d_min are U16, 2-byte
+ * aligned. */
+int dbde16_hip_decode_binned(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                             const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                             int x0, int y0, int rw, int rh, int bin,
+                             uint32_t *d_sum, uint16_t *d_max, uint16_t *d_min,
+                             dbde_hip_frame_result *d_results);
+/* What dbde_hip_decode_binned runs (pure host arithmetic, like dbde_hip_roi_plan): validates exactly what
+ * dbde_hip_decode_binned validates of its sizes (DBDE_HIP_ERR_ARG otherwise) and reports the tile window and index
+ * geometry (dbde_hip_roi_plan's), the planes' shape and bytes, and the binning kernel's launch.  stats: bitmask of the
+ * planes asked for (dbde_hip_decode_binned: its non-NULL d_sum / d_max / d_min). */
+enum { DBDE_HIP_BINNED_SUM = 1, DBDE_HIP_BINNED_MAX = 2, DBDE_HIP_BINNED_MIN = 4 };
+typedef struct dbde_hip_binned_plan_t {
+    int32_t tile_x, tile_y;           /* first tile column / row of the window */
+    int32_t tiles_x, tiles_y;         /* tiles across / down the window covers */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t out_w, out_h;            /* columns and rows of each plane per frame: ceil(rw / bin), ceil(rh / bin) */
+    uint32_t threads;                 /* binning kernel: workgroup size = tiles per workgroup (64, or 256; DBDE16: 128) */
+    uint32_t pieces_x;                /* binning kernel: workgroups per window tile row */
+    uint32_t lds_bytes;               /* LDS per workgroup (the piece's payload, reused as the output band; the scan) */
+    uint32_t reserved_;
+    uint64_t grid;                    /* binning kernel: n_frames * tiles_y * pieces_x workgroups */
+    uint64_t sum_bytes, max_bytes, min_bytes;   /* bytes of each plane asked for (0: not asked for), n_frames frames */
+} dbde_hip_binned_plan_t;
+int dbde_hip_binned_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int bin, unsigned stats,
+                         dbde_hip_binned_plan_t *plan);
+/* The same for dbde16_hip_decode_binned: its index, 128 tiles per workgroup for windows more than 64 tiles across, U32
+ * sums and U16 maxima / minima. */
+int dbde16_hip_binned_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int bin, unsigned stats,
+                           dbde_hip_binned_plan_t *plan);
+
 /* ---- kernel timing hook for bench.py ---------------------------------------------------- */
 /* When enabled, every encode / decode call brackets its kernels with HIP events on the
  * context's stream; dbde_hip_timing_read returns accumulated milliseconds and launch counts
