@@ -62,6 +62,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_trace_map_pixels", "dbde_hip_traces", "dbde16_hip_traces", "dbde_hip_trace_plan", "dbde16_hip_trace_plan",
     "dbde_hip_histogram", "dbde16_hip_histogram", "dbde_hip_histogram_plan", "dbde16_hip_histogram_plan",
     "dbde_hip_decode_binned", "dbde16_hip_decode_binned", "dbde_hip_binned_plan", "dbde16_hip_binned_plan",
+    "dbde_hip_crop_frames", "dbde16_hip_crop_frames", "dbde_hip_crop_plan", "dbde16_hip_crop_plan",
 ]
 
 
@@ -211,6 +212,12 @@ def lib():
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_binned_plan", "dbde16_hip_binned_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, C.c_uint, C.POINTER(BinnedPlan)]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_crop_frames", "dbde16_hip_crop_frames"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, vp, sz, u64, vp, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_crop_plan", "dbde16_hip_crop_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, u64, C.POINTER(CropPlan)]
         getattr(L, fn).restype = i
     L.dbde_hip_unpack_frame.argtypes = [vp, C.POINTER(vp), i, i, vp]
     L.dbde_hip_pack_frame_header.restype = sz
@@ -761,6 +768,48 @@ def binned16_plan(W, H, n_frames, bin, x=0, y=0, rw=None, rh=None, stats=("sum",
     return _binned_plan("dbde16_hip_binned_plan", W, H, n_frames, bin, x, y, rw, rh, stats)
 
 
+class CropPlan(C.Structure):
+    """dbde_hip_crop_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("out_tiles", C.c_uint32), ("recoded_tiles", C.c_uint32),
+                ("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32),
+                ("index_split", C.c_uint32),
+                ("size_threads", C.c_uint32), ("size_lds_bytes", C.c_uint32),
+                ("repack_threads", C.c_uint32), ("repack_lds_bytes", C.c_uint32),
+                ("rows_threads", C.c_uint32), ("rows_lds_bytes", C.c_uint32),
+                ("place_threads", C.c_uint32), ("place_lds_bytes", C.c_uint32),
+                ("copy_threads", C.c_uint32), ("copy_lds_bytes", C.c_uint32),
+                ("size_grid", C.c_uint64), ("rows_grid", C.c_uint64), ("place_grid", C.c_uint64),
+                ("copy_grid", C.c_uint64), ("repack_grid", C.c_uint64), ("max_out_frame_bytes", C.c_uint64), ("out_capacity", C.c_uint64),
+                ("workspace_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def _crop_plan(fn, W, H, n_frames, x, y, rw, rh, slot_stride):
+    """crop_plan / crop16_plan through the C function named fn."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    pl = CropPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, x, y, rw, rh, slot_stride, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, slot_stride={slot_stride}) -> {rc}")
+    return pl.as_dict()
+
+
+def crop_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, slot_stride=0):
+    """dbde_hip_crop_plan: the tile window, output size and capacity, index geometry, launches, LDS and workspace of
+    Codec.crop_frames (host arithmetic only).  rw / rh default to the rest of the frame.  Raises ValueError where
+    dbde_hip_crop_frames would return DBDE_HIP_ERR_ARG."""
+    return _crop_plan("dbde_hip_crop_plan", W, H, n_frames, x, y, rw, rh, slot_stride)
+
+
+def crop16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, slot_stride=0):
+    """dbde16_hip_crop_plan: crop_plan for DBDE16 frames (Codec.crop_frames16)."""
+    return _crop_plan("dbde16_hip_crop_plan", W, H, n_frames, x, y, rw, rh, slot_stride)
+
+
 def bin_pixels(rh, rw, bin, device=None):
     """int32 (ceil(rh / bin), ceil(rw / bin)): the pixels of each bin of an rw x rh window; bin * bin except in the
     last row and column, whose bins end at the window's edge."""
@@ -1101,6 +1150,44 @@ class Codec:
         tensors holding the U16 bits)."""
         return self._decode_binned("dbde16_hip_decode_binned", 2, stream, stream_offset, stream_bytes, offsets, W, H, n,
                                    bin, x, y, rw, rh, stats, out, results)
+
+    def _crop_frames(self, fn, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, out, out_offset,
+                     capacity, origins, slot_stride, out_offsets, out_bytes, origins_used, results):
+        """crop_frames / crop_frames16 through the C function named fn."""
+        if out_offsets is None:
+            out_offsets = torch.empty(n, dtype=torch.int64, device=self.device)
+        if out_bytes is None:
+            out_bytes = torch.empty(n, dtype=torch.int64, device=self.device)
+        if results is None:
+            results = torch.empty((n, 4), dtype=torch.int64, device=self.device)
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                 W, H, n, x, y, rw, rh, origins.data_ptr() if origins is not None else None,
+                                 out.data_ptr() + out_offset, capacity, slot_stride, out_offsets.data_ptr(),
+                                 out_bytes.data_ptr(),
+                                 origins_used.data_ptr() if origins_used is not None else None, results.data_ptr())
+        self._check(rc, fn)
+        return out_offsets, out_bytes, results
+
+    def crop_frames(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, out, out_offset,
+                    capacity, origins=None, slot_stride=0, out_offsets=None, out_bytes=None, origins_used=None,
+                    results=None):
+        """Crops the rw x rh window at (x, y; multiples of 8) of n frames into n DBDE frames of an rw x rh image,
+        written from out.data_ptr()+out_offset like encode_frames (alloc_stream(rw, rh, n, slot_stride) sizes `out`):
+        tiles are copied in the compressed domain, only those the window's right / bottom edge cuts are re-packed.
+        origins: optional int32 device tensor (n, 2) of per-frame (x, y), clamped into the frame and rounded down to
+        a multiple of 8; origins_used (optional, same shape) receives the origin of each cropped frame.
+        Returns (out_offsets, out_bytes, results): int64 device tensors; a rejected frame has 0 bytes."""
+        return self._crop_frames("dbde_hip_crop_frames", stream, stream_offset, stream_bytes, offsets, W, H, n, x, y,
+                                 rw, rh, out, out_offset, capacity, origins, slot_stride, out_offsets, out_bytes,
+                                 origins_used, results)
+
+    def crop_frames16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, out, out_offset,
+                      capacity, origins=None, slot_stride=0, out_offsets=None, out_bytes=None, origins_used=None,
+                      results=None):
+        """crop_frames for DBDE16 frames in and out (worst case per frame: dbde16_hip_max_frame_bytes(rw, rh))."""
+        return self._crop_frames("dbde16_hip_crop_frames", stream, stream_offset, stream_bytes, offsets, W, H, n, x,
+                                 y, rw, rh, out, out_offset, capacity, origins, slot_stride, out_offsets, out_bytes,
+                                 origins_used, results)
 
     def trace_map(self, labels, n_labels=None):
         """A TraceMap of this codec from a label image (H, W): numpy, or a torch tensor on any device; 0 = no region,

@@ -20,6 +20,7 @@
 namespace dbde16 {
 
 using dbde::cut_row16;
+using dbde::pack_four16;
 using dbde::pk_max_u16;
 using dbde::pk_min_u16;
 using dbde::wave_scan_incl;
@@ -85,13 +86,6 @@ __device__ __forceinline__ Tile16 tile_of(const Params16 &p, uint32_t c, uint32_
 typedef unsigned long long u64a;
 constexpr u64a kReady = 1ull << 63;
 
-// Four pixels (two dwords, 16 bits each, already minus the minimum) -> the 4*d-bit integer p0 | p1<<d | p2<<2d | p3<<3d.
-__device__ __forceinline__ uint64_t pack4x16(uint32_t a, uint32_t b, uint32_t d) {
-    const uint64_t lo = (uint64_t)(a & 0xFFFFu) | ((uint64_t)(a >> 16) << d);
-    const uint64_t hi = (uint64_t)(b & 0xFFFFu) | ((uint64_t)(b >> 16) << d);
-    return lo | (hi << (2u * d));
-}
-
 __device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m, 64);
@@ -137,7 +131,7 @@ __device__ __forceinline__ void pack_tile16(const uint32_t (&v)[32], uint32_t mn
     uint32_t fill = 0;
 #pragma unroll
     for (int h = 0; h < 16; h++) {
-        const uint64_t bits = pack4x16(v[2 * h] - mn2, v[2 * h + 1] - mn2, d);
+        const uint64_t bits = pack_four16(v[2 * h] - mn2, v[2 * h + 1] - mn2, d);
         const uint64_t merged = acc | (bits << fill);
         s_pay[q < kPayWords16 ? q : kPayWords16] = merged;
         const uint32_t nf = fill + nb;

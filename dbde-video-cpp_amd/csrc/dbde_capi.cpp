@@ -16,6 +16,7 @@
 
 #include "dbde16_kernels.h"
 #include "dbde_binned_kernels.h"
+#include "dbde_crop_kernels.h"
 #include "dbde_hist_kernels.h"
 #include "dbde_kernels.h"
 #include "dbde_project_kernels.h"
@@ -74,6 +75,8 @@ struct dbde_hip_ctx {
     size_t proj_ws_bytes = 0;
     uint8_t *trace_ws = nullptr;     // U32 max / min per (frame, label) of dbde_hip_traces
     size_t trace_ws_bytes = 0;
+    uint8_t *crop_ws = nullptr;      // row and frame tables, records of re-packed tiles of dbde_hip_crop_frames
+    size_t crop_ws_bytes = 0;
     size_t fuse_rec_n = 0;
     uint32_t fuse_epoch = 0;
     // sticky failure word (device) + scratch
@@ -296,6 +299,7 @@ void dbde_hip_destroy(dbde_hip_ctx *ctx) {
     if (ctx->fuse_rec) (void)hipFree(ctx->fuse_rec);
     if (ctx->proj_ws) (void)hipFree(ctx->proj_ws);
     if (ctx->trace_ws) (void)hipFree(ctx->trace_ws);
+    if (ctx->crop_ws) (void)hipFree(ctx->crop_ws);
     if (ctx->sticky) (void)hipFree(ctx->sticky);
     if (ctx->st_img) (void)hipFree(ctx->st_img);
     if (ctx->st_pack) (void)hipFree(ctx->st_pack);
@@ -1717,6 +1721,162 @@ int dbde16_hip_decode_binned(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t 
                              dbde_hip_frame_result *d_results) {
     return decode_binned_common(ctx, "decode_binned16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0,
                                 y0, rw, rh, bin, d_sum, d_max, d_min, d_results);
+}
+
+// ---- compressed-domain crop ---------------------------------------------------------------------------------
+struct CropPlan {
+    RoiPlan roi;                      // arguments, tile window and index geometry: the window decoder's (plan_roi)
+    uint32_t Tout, recoded;
+    uint64_t max_frame, capacity, rows;
+    uint64_t tables_bytes, rec_fixed_bytes, rec_origins_bytes;
+};
+static uint64_t crop_max_frame_bytes(uint64_t T, uint32_t pix) { return 20u + 12u + (pix == 2u ? 131u : 66u) * T; }
+static uint64_t round16(uint64_t v) { return (v + 15u) & ~(uint64_t)15; }
+static const char *plan_crop(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint64_t slot_stride,
+                             uint32_t pix, CropPlan &pl) {
+    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi)) return why;
+    if ((x0 | y0) & 7) return "window origin not a multiple of 8";
+    const RoiPlan &r = pl.roi;
+    pl.Tout = r.ntx * r.nty;
+    pl.max_frame = crop_max_frame_bytes(pl.Tout, pix);
+    if (slot_stride && slot_stride < pl.max_frame) return "slot_stride below the cropped frame's worst case";
+    pl.capacity = n_frames == 0 ? 0u : (slot_stride ? (uint64_t)(n_frames - 1) * slot_stride + pl.max_frame : (uint64_t)n_frames * pl.max_frame);
+    pl.rows = (uint64_t)n_frames * r.nty;
+    if (pl.rows >= (1ull << 31)) return "too many workgroups in one call";
+    const uint32_t rm = (uint32_t)rw - 8u * (r.ntx - 1u), dm = (uint32_t)rh - 8u * (r.nty - 1u);
+    const uint32_t srm = (uint32_t)W - 8u * (r.tx0 + r.ntx - 1u), sdm = (uint32_t)H - 8u * (r.ty0 + r.nty - 1u);
+    const bool cut_col = rm != (srm < 8u ? srm : 8u), cut_row = dm != (sdm < 8u ? sdm : 8u);
+    pl.recoded = cut_row ? (cut_col ? r.ntx + r.nty - 1u : r.ntx) : (cut_col ? r.nty : 0u);
+    // three U32 per (frame, window tile row), two U64 per frame; the records behind them
+    pl.tables_bytes = round16(3u * 4u * pl.rows) + 2u * 8u * (uint64_t)n_frames;
+    pl.rec_origins_bytes = (uint64_t)n_frames * (r.ntx + r.nty - 1u) * kCropRecBytes;
+    pl.rec_fixed_bytes = pl.recoded ? pl.rec_origins_bytes : 0u;
+    return nullptr;
+}
+
+static int crop_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint64_t slot_stride, uint32_t pix,
+                            dbde_hip_crop_plan_t *plan) {
+    CropPlan pl;
+    if (!plan || plan_crop(W, H, n_frames, x0, y0, rw, rh, slot_stride, pix, pl)) return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->tile_x = (int32_t)pl.roi.tx0;
+    plan->tile_y = (int32_t)pl.roi.ty0;
+    plan->tiles_x = (int32_t)pl.roi.ntx;
+    plan->tiles_y = (int32_t)pl.roi.nty;
+    plan->out_tiles = pl.Tout;
+    plan->recoded_tiles = pl.recoded;
+    plan->chunks_per_frame = pl.roi.dg.cpf;
+    plan->chunk_tiles = pl.roi.dg.ct;
+    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
+    plan->index_split = pl.roi.split;
+    plan->size_threads = kCropThreads;
+    plan->size_lds_bytes = kCropSizeLds;
+    plan->rows_threads = kCropThreads;
+    plan->rows_lds_bytes = kCropRowsLds;
+    plan->place_threads = kCropPlaceThreads;
+    plan->place_lds_bytes = kCropPlaceLds;
+    plan->copy_threads = kCropThreads;
+    plan->copy_lds_bytes = kCropCopyLds;
+    plan->repack_threads = kCropThreads;
+    plan->repack_lds_bytes = kCropRepackLds;
+    plan->repack_grid = pl.recoded ? (uint64_t)n_frames * ((pl.roi.ntx + pl.roi.nty - 1u + kCropThreads - 1u) / kCropThreads) : 0u;
+    plan->size_grid = pl.rows;
+    plan->rows_grid = (uint64_t)n_frames;
+    plan->place_grid = n_frames ? 1u : 0u;
+    plan->copy_grid = pl.rows;
+    plan->max_out_frame_bytes = pl.max_frame;
+    plan->out_capacity = pl.capacity;
+    plan->workspace_bytes = pl.tables_bytes + pl.rec_origins_bytes;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_crop_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint64_t slot_stride,
+                       dbde_hip_crop_plan_t *plan) {
+    return crop_plan_common(W, H, n_frames, x0, y0, rw, rh, slot_stride, 1u, plan);
+}
+
+int dbde16_hip_crop_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint64_t slot_stride,
+                         dbde_hip_crop_plan_t *plan) {
+    return crop_plan_common(W, H, n_frames, x0, y0, rw, rh, slot_stride, 2u, plan);
+}
+
+// Both crops: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the crop kernels in slot 2.
+static int crop_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream, size_t stream_bytes,
+                       const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                       const int32_t *d_origins, uint8_t *d_out, size_t out_capacity, uint64_t slot_stride,
+                       uint64_t *d_out_offsets, uint64_t *d_out_bytes, int32_t *d_origins_used,
+                       dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    CropPlan pl;
+    if (const char *why = plan_crop(W, H, n_frames, x0, y0, rw, rh, slot_stride, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", name, why, W, H, n_frames, rw,
+                    rh, x0, y0);
+    if (!d_stream || !d_frame_offsets || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if (n_frames == 0) return DBDE_HIP_OK;
+    if ((uint64_t)out_capacity < pl.capacity)
+        return fail(ctx, DBDE_HIP_ERR_CAPACITY, "%s: out_capacity %zu below the worst case %llu", name, out_capacity,
+                    (unsigned long long)pl.capacity);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t rec_bytes = d_origins ? pl.rec_origins_bytes : pl.rec_fixed_bytes;
+    int rc = grow(ctx, ctx->crop_ws, ctx->crop_ws_bytes, (size_t)(pl.tables_bytes + rec_bytes), 1);
+    if (rc) return rc;
+    rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
+    if (rc) return rc;
+
+    CropParams p;
+    memset(&p, 0, sizeof p);
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.origins = d_origins;
+    p.origins_used = d_origins_used;
+    p.out = d_out;
+    p.slot_stride = slot_stride;
+    p.out_offsets = d_out_offsets;
+    p.out_bytes = d_out_bytes;
+    uint8_t *ws = ctx->crop_ws;
+    p.frame_bytes = reinterpret_cast<uint64_t *>(ws);
+    p.frame_off = p.frame_bytes + n_frames;
+    p.row_src = reinterpret_cast<uint32_t *>(ws + 16u * (size_t)n_frames);
+    p.row_copy = p.row_src + pl.rows;
+    p.row_words = p.row_copy + pl.rows;
+    p.rec = ws + pl.tables_bytes;
+    p.W = W;
+    p.H = H;
+    p.x0 = x0;
+    p.y0 = y0;
+    p.rw = rw;
+    p.rh = rh;
+    p.w = pl.roi.g.w;
+    p.T = pl.roi.g.T;
+    p.geom = pl.roi.dg;
+    p.ntx = pl.roi.ntx;
+    p.nty = pl.roi.nty;
+    p.Tout = pl.Tout;
+    p.n_frames = (uint32_t)n_frames;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_crop(p, pix, d_origins != nullptr || pl.recoded != 0u, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_crop_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+                         int W, int H, int n_frames, int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                         uint8_t *d_out, size_t out_capacity, uint64_t slot_stride, uint64_t *d_out_offsets,
+                         uint64_t *d_out_bytes, int32_t *d_origins_used, dbde_hip_frame_result *d_results) {
+    return crop_common(ctx, "crop_frames", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh,
+                       d_origins, d_out, out_capacity, slot_stride, d_out_offsets, d_out_bytes, d_origins_used, d_results);
+}
+
+int dbde16_hip_crop_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                           const int32_t *d_origins, uint8_t *d_out, size_t out_capacity, uint64_t slot_stride,
+                           uint64_t *d_out_offsets, uint64_t *d_out_bytes, int32_t *d_origins_used,
+                           dbde_hip_frame_result *d_results) {
+    return crop_common(ctx, "crop_frames16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh,
+                       d_origins, d_out, out_capacity, slot_stride, d_out_offsets, d_out_bytes, d_origins_used, d_results);
 }
 
 int dbde_hip_index_stream_async(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, int W, int H,

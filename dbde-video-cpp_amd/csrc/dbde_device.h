@@ -68,4 +68,12 @@ __device__ __forceinline__ void cut_row16(const uint32_t *q, const uint32_t *qh,
     cut_four16(h0, h1, d, m32, mn2, c2, c3, o2, o3);
 }
 
+// The packing half of a DBDE16 tile row, shared by enc16_kernel and the crop's re-pack: four pixels (two dwords, 16 bits
+// each, already minus the minimum) -> the 4*d-bit integer p0 | p1<<d | p2<<2d | p3<<3d.
+__device__ __forceinline__ uint64_t pack_four16(uint32_t a, uint32_t b, uint32_t d) {
+    const uint64_t lo = (uint64_t)(a & 0xFFFFu) | ((uint64_t)(a >> 16) << d);
+    const uint64_t hi = (uint64_t)(b & 0xFFFFu) | ((uint64_t)(b >> 16) << d);
+    return lo | (hi << (2u * d));
+}
+
 }  // namespace dbde

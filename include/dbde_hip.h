@@ -762,6 +762,83 @@ int dbde_hip_binned_plan(int W, int H, int n_frames, int x0, int y0, int rw, int
 int dbde16_hip_binned_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int bin, unsigned stats,
                            dbde_hip_binned_plan_t *plan);
 
+/* ---- compressed-domain crop: a window of each frame as a new stream ------------------------------ */
+/* Crops the rw x rh window at (x0, y0) out of each of n_frames DBDE frames and writes it as a complete DBDE frame of an
+ * rw x rh image, without decoding the window: tiles whose valid pixels are unchanged are COPIED (depth byte, minimum,
+ * payload bytes), only tiles that the window's right or bottom edge cuts are decoded, padded and packed again.
+ * Input: exactly as dbde_hip_decode_roi -- frame f at d_stream + d_frame_offsets[f], any byte alignment, concatenated or
+ *   slot layout; no byte at or beyond stream_bytes is read.  Validation is dbde_hip_decode_frames' own (the same index
+ *   kernel); d_results (optional) is filled exactly as that call fills it, consumed being the SOURCE frame's length.
+ * Window: inside the frame as dbde_hip_decode_roi requires, and x0, y0 multiples of 8 (DBDE_HIP_ERR_ARG otherwise); rw
+ *   and rh are free.  d_origins (optional, device int32 [n_frames][2]): per-frame (x, y), clamped into
+ *   [0, W-rw] x [0, H-rh] as dbde_hip_decode_roi clamps them, then rounded DOWN to a multiple of 8; the origin actually
+ *   used goes to d_origins_used (optional, same shape; written for rejected frames too).
+ * Output: for every accepted frame the source's 20 header bytes unchanged (index and elapsed_ns bits kept), then
+ *   nb = T', depths, nm, minima, n64, payload with T' = ceil(rw/8) * ceil(rh/8).  Layout as dbde_hip_encode_frames:
+ *   slot_stride == 0 concatenates from d_out (a ready .dbde body for a video header of rw x rh), otherwise frame f
+ *   starts at d_out + f*slot_stride, slot_stride >= dbde_hip_max_frame_bytes(rw, rh).  d_out may have any alignment.
+ *   d_out_offsets / d_out_bytes (optional) as the encoder returns them.  out_capacity must cover the worst case
+ *   (n_frames * max_frame_bytes(rw, rh), or (n_frames-1)*slot_stride + max): less is DBDE_HIP_ERR_CAPACITY before
+ *   anything is launched.
+ * Which tiles are copied: window tile (i, j) has valid margins rm = min(8, rw - 8i), dm = min(8, rh - 8j); its source
+ *   tile has srm = min(8, W - 8(tx+i)), sdm = min(8, H - 8(ty+j)).  With rm == srm and dm == sdm the tile is copied
+ *   verbatim; otherwise it is decoded (wrapping add), its rm x dm valid pixels are constant-padded as
+ *   dbde_pack_8x8_partial pads them, and it is packed again.  With per-frame origins the test is per frame.
+ * Guarantees: (a) decoding an output frame as an rw x rh frame gives rows [y, y+rh) x columns [x, x+rw) of what
+ *   dbde_hip_decode_frames gives for the source, byte for byte.  (b) If the source frame is what an encoder writes,
+ *   the output frame is byte-identical to the reference's dbde_pack_frame of the cropped image with the header's 16
+ *   index / elapsed bytes carried over.  (c) x0 = y0 = 0, rw = W, rh = H reproduces every accepted source frame byte
+ *   for byte.  For valid but NON-CANONICAL streams (a stored minimum that makes the add wrap, a depth larger than the
+ *   range needs) copied tiles stay as stored, so only (a) and (c) hold.
+ * Rejected frames write nothing: d_out_bytes[f] = 0; d_out_offsets[f] is the slot start in the slot layout and,
+ *   concatenated, the position the next accepted frame takes (the body holds the accepted frames only, in order).
+ * Nothing outside [offsets[f], offsets[f] + bytes[f]) of the accepted frames is written.  n_frames == 0 does nothing.
+ * Asynchronous on the context's stream; workspace is the context's, grown on demand.  Timing hook: the index kernel
+ * in slot 1, the crop kernels in slot 2. */
+int dbde_hip_crop_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                         const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                         int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                         uint8_t *d_out, size_t out_capacity, uint64_t slot_stride,
+                         uint64_t *d_out_offsets, uint64_t *d_out_bytes,
+                         int32_t *d_origins_used, dbde_hip_frame_result *d_results);
+/* The same for DBDE16 frames in, DBDE16 frames out: U16 minima, depth <= 16, nm = 2T', sizes by
+ * dbde16_hip_max_frame_bytes; validation is dbde16_hip_decode_frames' own.  (That format's parity is unpinned.) */
+int dbde16_hip_crop_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                           int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                           uint8_t *d_out, size_t out_capacity, uint64_t slot_stride,
+                           uint64_t *d_out_offsets, uint64_t *d_out_bytes,
+                           int32_t *d_origins_used, dbde_hip_frame_result *d_results);
+/* What dbde_hip_crop_frames runs (pure host arithmetic, like dbde_hip_roi_plan): validates exactly what it validates
+ * of its sizes (DBDE_HIP_ERR_ARG otherwise) and reports the tile window, the output's size, the index geometry and
+ * the crop kernels' launches.  The workspace is reported for per-frame origins (records for every tile that any
+ * origin could cut); with the fixed origin only recoded_tiles records per frame are kept. */
+typedef struct dbde_hip_crop_plan_t {
+    int32_t tile_x, tile_y;           /* first tile column / row of the window at (x0, y0) */
+    int32_t tiles_x, tiles_y;         /* tiles across / down of the cropped frame */
+    uint32_t out_tiles;               /* T' = tiles_x * tiles_y */
+    uint32_t recoded_tiles;           /* tiles re-packed per frame at (x0, y0): 0 when both extents end on a tile
+                                         boundary or on the frame's own edge */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t size_threads, size_lds_bytes;     /* sizing kernel: one workgroup per (frame, window tile row) */
+    uint32_t repack_threads, repack_lds_bytes; /* re-pack kernel: one thread per record slot (tiles_x + tiles_y - 1 a frame) */
+    uint32_t rows_threads, rows_lds_bytes;     /* row scan: one workgroup per frame */
+    uint32_t place_threads, place_lds_bytes;   /* frame scan: one workgroup */
+    uint32_t copy_threads, copy_lds_bytes;     /* copy: one workgroup per (frame, window tile row) */
+    uint64_t size_grid, rows_grid, place_grid, copy_grid;
+    uint64_t repack_grid;             /* 0 when nothing is cut at (x0, y0); with per-frame origins it always runs */
+    uint64_t max_out_frame_bytes;     /* worst case of one cropped frame: max_frame_bytes(rw, rh) */
+    uint64_t out_capacity;            /* the least out_capacity for n_frames and slot_stride */
+    uint64_t workspace_bytes;         /* row and frame tables, records of re-packed tiles (the index's own aside) */
+} dbde_hip_crop_plan_t;
+int dbde_hip_crop_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint64_t slot_stride,
+                       dbde_hip_crop_plan_t *plan);
+int dbde16_hip_crop_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint64_t slot_stride,
+                         dbde_hip_crop_plan_t *plan);
+
 /* ---- kernel timing hook for bench.py ---------------------------------------------------- */
 /* When enabled, every encode / decode call brackets its kernels with HIP events on the
  * context's stream; dbde_hip_timing_read returns accumulated milliseconds and launch counts
