@@ -17,6 +17,11 @@
 //     window: displacement 0).
 // librccl is opened at run time (dlopen "librccl.so.1": in a PyTorch process that is the copy torch has loaded, so the
 // process holds ONE RCCL), which keeps single-GPU users of libdbde_hip.so free of the dependency.
+// What has run: one rank on the real RCCL (tests/c_client/gather1.cpp, tests/test_gpu_config5.py), and the multi-rank
+// branches -- the non-root SEND, the root's RECV at a displacement, its own segment at a non-zero displacement (root != 0),
+// the shared verdict -- with 2-4 real peer PROCESSES on one GPU through a stand-in transport
+// (tests/test_gpu_exchange_ranks.py; the library override of dbde_rccl.h): bytes and verdicts, explicitly not a measurement
+// and never over xGMI.  What has not: RCCL itself between ranks.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -52,6 +57,7 @@ struct dbde_hip_gather {
     hipStream_t ctx_stream = nullptr, comm_stream = nullptr;
     uint64_t max_piece = 1ull << 30;
     uint64_t window_cap = ~0ull;      // root: bytes its window holds (dbde_hip_gather_set_window); travels with every size exchange
+    bool window_declared = false;     // (with peers an undeclared window travels as "none": see dbde_hip_gather_begin)
     struct Slot {
         uint64_t *d_mine = nullptr, *d_sizes = nullptr;   // device: this rank's {count, window capacity}, every rank's pair
         uint64_t *h_sizes = nullptr;                      // pinned host copy of d_sizes
@@ -216,7 +222,11 @@ void dbde_hip_gather_destroy(dbde_hip_gather *g) {
     delete g;
 }
 
-const char *dbde_hip_gather_error(const dbde_hip_gather *g) { return g ? g->err.c_str() : "null gather"; }
+const char *dbde_hip_gather_error(const dbde_hip_gather *g) {
+    if (g) return g->err.c_str();
+    const char *why = dbde_rccl::rccl_error();   // no handle: a create that failed because RCCL could not be opened says why here
+    return *why ? why : "null gather";
+}
 
 int dbde_hip_gather_set_max_message(dbde_hip_gather *g, uint64_t bytes) {
     if (!g || bytes == 0) return DBDE_HIP_ERR_ARG;
@@ -227,6 +237,7 @@ int dbde_hip_gather_set_max_message(dbde_hip_gather *g, uint64_t bytes) {
 int dbde_hip_gather_set_window(dbde_hip_gather *g, uint64_t window_bytes) {
     if (!g) return DBDE_HIP_ERR_ARG;
     g->window_cap = window_bytes;
+    g->window_declared = true;
     return DBDE_HIP_OK;
 }
 
@@ -237,8 +248,11 @@ int dbde_hip_gather_begin(dbde_hip_gather *g, int slot, const uint64_t *d_last_o
     // behind everything the codec's stream holds so far (the encode that produces the count and the bytes)
     G_HIP(g, hipEventRecord(s.ev_ready, g->ctx_stream));
     G_HIP(g, hipStreamWaitEvent(g->comm_stream, s.ev_ready, 0));
-    hipLaunchKernelGGL(gather_count_kernel, dim3(1), dim3(64), 0, g->comm_stream, d_last_offset, d_last_bytes,
-                       g->rank == g->root ? g->window_cap : 0ull, s.d_mine);
+    // With peers, a root that never declared its window sends "none" (0), not "no limit": otherwise the shared check
+    // passes everywhere and the root's own window_bytes test in gather_post fails on the root ALONE, after its peers
+    // have posted their sends.  Capacity 0 makes every rank reach the same DBDE_HIP_ERR_CAPACITY from the same numbers.
+    const uint64_t cap_word = g->rank != g->root ? 0ull : (g->nranks > 1 && !g->window_declared) ? 0ull : g->window_cap;
+    hipLaunchKernelGGL(gather_count_kernel, dim3(1), dim3(64), 0, g->comm_stream, d_last_offset, d_last_bytes, cap_word, s.d_mine);
     G_HIP(g, hipGetLastError());
     G_NCCL(g, rccl()->AllGather(s.d_mine, s.d_sizes, 2, ncclUint64, g->comm, g->comm_stream));
     G_HIP(g, hipMemcpyAsync(s.h_sizes, s.d_sizes, 16 * (size_t)g->nranks, hipMemcpyDeviceToHost, g->comm_stream));
@@ -262,8 +276,9 @@ int dbde_hip_gather_post(dbde_hip_gather *g, int slot, const uint8_t *d_segment,
     // The data-dependent verdict is the same on every rank (the root's capacity travelled with the counts): all post or none
     uint64_t total = 0;
     if (dbde_hip_gather_check(g->nranks, g->root, s.h_sizes, &total) != DBDE_HIP_OK)
-        return gfail(g, DBDE_HIP_ERR_CAPACITY, "gather_post: %llu bytes do not fit the root window (%llu): nothing posted on any rank",
-                     (unsigned long long)total, (unsigned long long)s.h_sizes[2 * g->root + 1]);
+        return gfail(g, DBDE_HIP_ERR_CAPACITY, "gather_post: %llu bytes do not fit the root window (%llu%s): nothing posted on any rank",
+                     (unsigned long long)total, (unsigned long long)s.h_sizes[2 * g->root + 1],
+                     g->nranks > 1 && s.h_sizes[2 * g->root + 1] == 0 ? "; with more than one rank the root must declare it, dbde_hip_gather_set_window" : "");
     if (g->rank == g->root && total > window_bytes)   // (a caller's error, not the data's: the window is smaller than what was declared)
         return gfail(g, DBDE_HIP_ERR_ARG, "gather_post: window_bytes %zu below the declared capacity (dbde_hip_gather_set_window) and the %llu bytes on their way",
                      window_bytes, (unsigned long long)total);

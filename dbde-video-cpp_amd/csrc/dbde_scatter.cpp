@@ -12,8 +12,12 @@
 //   * the bytes travel as grouped ncclSend / ncclRecv, the frame offsets of a block (8 bytes per frame) behind them; the
 //     receiver rebases them to its segment on the device.  The root's own block is not moved: it decodes from the stream
 //     where it lies.
-// RCCL is opened at run time (dbde_rccl.h).  Rank-to-rank traffic has not run on hardware (one-GPU boxes only); the
-// plan both ends derive is pure arithmetic and is tested for worlds 1-8 without a GPU (tests/test_scatter_plan.py).
+// RCCL is opened at run time (dbde_rccl.h).  What has run: one rank on the real RCCL (tests/test_gpu_scatter.py), and every
+// multi-rank branch below -- SEND_/RECV_BYTES, SEND_/RECV_OFFSETS, the in-place rebase of received offsets, the shared
+// capacity verdict -- with 2-4 real peer PROCESSES on one GPU through a stand-in transport
+// (tests/test_gpu_exchange_ranks.py; the library override of dbde_rccl.h): bytes and verdicts, explicitly not a measurement
+// and never over xGMI.  What has not: RCCL itself between ranks (one-GPU boxes only).  The plan both ends derive is pure
+// arithmetic and is tested for worlds 1-8 without a GPU (tests/test_scatter_plan.py).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -239,7 +243,11 @@ void dbde_hip_scatter_destroy(dbde_hip_scatter *s) {
     delete s;
 }
 
-const char *dbde_hip_scatter_error(const dbde_hip_scatter *s) { return s ? s->err.c_str() : "null scatter"; }
+const char *dbde_hip_scatter_error(const dbde_hip_scatter *s) {
+    if (s) return s->err.c_str();
+    const char *why = dbde_rccl::rccl_error();   // no handle: a create that failed because RCCL could not be opened says why here
+    return *why ? why : "null scatter";
+}
 
 int dbde_hip_scatter_set_max_message(dbde_hip_scatter *s, uint64_t bytes) {
     if (!s || bytes == 0) return DBDE_HIP_ERR_ARG;
@@ -264,9 +272,11 @@ int dbde_hip_scatter_begin(dbde_hip_scatter *s, int slot, const uint8_t *d_strea
     // behind everything the codec's stream holds so far (the scanner that produces the offsets and the count)
     S_HIP(s, hipEventRecord(sl.ev_ready, s->ctx_stream));
     S_HIP(s, hipStreamWaitEvent(s->comm_stream, sl.ev_ready, 0));
-    // the root's own block is decoded in place: no capacity of its own to meet
-    hipLaunchKernelGGL(scatter_caps_kernel, dim3(1), dim3(64), 0, s->comm_stream, is_root ? ~0ull : s->seg_cap,
-                       is_root ? ~0ull : s->max_frames, sl.d_mine);
+    // the root's own block is decoded in place: no SEGMENT capacity of its own to meet -- but the rebased offsets of its
+    // block are written to its d_offsets_out, and their number is the scanner's reading of an untrusted stream, so its
+    // max_frames counts in the shared verdict like everybody's
+    hipLaunchKernelGGL(scatter_caps_kernel, dim3(1), dim3(64), 0, s->comm_stream, is_root ? ~0ull : s->seg_cap, s->max_frames,
+                       sl.d_mine);
     S_HIP(s, hipGetLastError());
     if (is_root) {
         hipLaunchKernelGGL(scatter_table_kernel, dim3(1), dim3(64), 0, s->comm_stream, d_frame_offsets, d_n_frames, stream_bytes,

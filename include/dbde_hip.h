@@ -335,6 +335,15 @@ int dbde16_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream
  * are all-gathered (ncclAllGather, 8 bytes per rank), every rank derives the same displacements, and the bytes
  * travel as grouped ncclSend / ncclRecv into the root's window at their displacement.  One process per GPU; the
  * library opens librccl itself (dlopen; a process that never calls these needs no RCCL).
+ * Which RCCL: when the environment variable DBDE_HIP_RCCL_LIBRARY is set and non-empty, the library it names is opened
+ * first (a path, or a name the dynamic loader can resolve); otherwise "librccl.so.1", "librccl.so" and
+ * "/opt/rocm/lib/librccl.so.1" are tried in turn.  A named library that cannot be opened, or that lacks one of the eleven
+ * entry points used (ncclGetUniqueId, ncclCommInitRank, ncclCommDestroy, ncclAllGather, ncclBroadcast, ncclSend, ncclRecv,
+ * ncclGroupStart, ncclGroupEnd, ncclGetErrorString, ncclGetVersion), is an ERROR -- there is no fall-back to the default
+ * names: dbde_hip_gather_rccl_version returns 0, the create / attach / unique_id calls return DBDE_HIP_ERR_HIP, and
+ * dbde_hip_gather_error(NULL) / dbde_hip_scatter_error(NULL) give the reason.  The choice is made once per process, at
+ * the first call that needs RCCL.  (The tests use it to run real peer ranks on one GPU through a stand-in transport,
+ * tests/fake_rccl/; nothing in the library, the Python package or bench.py sets it.)
  *
  * Per batch, with two slots so that the gather of batch k overlaps the encode of batch k+1:
  *   dbde_hip_gather_join(g, slot)            codec stream waits until the slot's previous transfer has finished
@@ -354,13 +363,19 @@ int dbde_hip_gather_create(dbde_hip_ctx *ctx, const uint8_t id[DBDE_HIP_GATHER_I
 int dbde_hip_gather_attach(dbde_hip_ctx *ctx, void *nccl_comm, int nranks, int rank, int root,
                            dbde_hip_gather **out);
 void dbde_hip_gather_destroy(dbde_hip_gather *g);
+/* The handle's last error; with g == NULL, why RCCL could not be opened (or "null gather"). */
 const char *dbde_hip_gather_error(const dbde_hip_gather *g);
 /* Messages are cut into pieces of at most this many bytes (default 1 GiB), all posted in one group. */
 int dbde_hip_gather_set_max_message(dbde_hip_gather *g, uint64_t bytes);
-/* Root: the bytes its window holds (default: no limit declared).  The value travels with every size exchange, so that
- * "the batch does not fit" is a verdict EVERY rank reaches from the same numbers (dbde_hip_gather_post then returns
- * DBDE_HIP_ERR_CAPACITY on all ranks and nothing has been posted anywhere; a root that found out alone used to leave
- * its peers' sends unmatched).  Call it once, before the first dbde_hip_gather_begin. */
+/* Root: the bytes its window holds.  The value travels with every size exchange, so that "the batch does not fit" is a
+ * verdict EVERY rank reaches from the same numbers (dbde_hip_gather_post then returns DBDE_HIP_ERR_CAPACITY on all ranks
+ * and nothing has been posted anywhere; a root that found out alone used to leave its peers' sends unmatched).  Call it
+ * once, before the first dbde_hip_gather_begin.  With nranks > 1 the declaration is REQUIRED: an undeclared window
+ * travels as "none" (capacity 0), so every batch that carries a byte is DBDE_HIP_ERR_CAPACITY on every rank.  (nranks
+ * == 1 has no peer to strand: an undeclared window there means "no limit declared" and only window_bytes is checked.)
+ * The caller's contract that remains: the window_bytes the root later passes to dbde_hip_gather_post must be at least
+ * what it declared here.  A root that breaks it gets DBDE_HIP_ERR_ARG ALONE, after its peers have posted their sends --
+ * only the root knows window_bytes, so this cannot be a shared verdict without passing it through the exchange. */
 int dbde_hip_gather_set_window(dbde_hip_gather *g, uint64_t window_bytes);
 /* The verdict itself, pure arithmetic: pairs[2 r] = rank r's count, pairs[2 r + 1] = the window capacity rank r declared
  * (only the root's counts).  DBDE_HIP_OK or DBDE_HIP_ERR_CAPACITY; *total_out = sum of the counts. */
@@ -415,7 +430,9 @@ int dbde_hip_gather_plan(int nranks, int rank, int root, const uint64_t *sizes, 
  *   all:    dbde_hip_scatter_join(s, slot)
  *   all:    dbde_hip_decode_frames(ctx, root ? d_stream + mine.byte_start : d_segment, mine.byte_count, d_my_offsets, W, H,
  *                                  (int)mine.n_frames, d_images, d_results)
- * Collective: every rank makes the same begin / post calls in the same order.  UNMEASURED on hardware beyond one rank. */
+ * Collective: every rank makes the same begin / post calls in the same order.  UNMEASURED on hardware beyond one rank:
+ * worlds of 2-4 real processes have run every branch on one GPU through a stand-in transport (tests/fake_rccl/), which
+ * checks bytes and verdicts and says nothing about time; RCCL itself has not carried rank-to-rank traffic. */
 typedef struct dbde_hip_scatter dbde_hip_scatter;
 typedef struct {
     uint64_t first_frame, n_frames;   /* the rank's frame block: global frame numbers [first_frame, first_frame + n_frames) */
@@ -425,10 +442,14 @@ int dbde_hip_scatter_create(dbde_hip_ctx *ctx, const uint8_t id[DBDE_HIP_GATHER_
                             int root, dbde_hip_scatter **out);      /* collective (ncclCommInitRank); id: dbde_hip_gather_unique_id */
 int dbde_hip_scatter_attach(dbde_hip_ctx *ctx, void *nccl_comm, int nranks, int rank, int root, dbde_hip_scatter **out);
 void dbde_hip_scatter_destroy(dbde_hip_scatter *s);
-const char *dbde_hip_scatter_error(const dbde_hip_scatter *s);
+const char *dbde_hip_scatter_error(const dbde_hip_scatter *s);   /* s == NULL: as dbde_hip_gather_error(NULL) */
 int dbde_hip_scatter_set_max_message(dbde_hip_scatter *s, uint64_t bytes);
 /* What this rank's receive buffers hold: segment bytes and frame offsets.  Travels with every table exchange, so that "a
- * block does not fit" is DBDE_HIP_ERR_CAPACITY on EVERY rank with nothing posted (the root needs none: it decodes in place). */
+ * block does not fit" is DBDE_HIP_ERR_CAPACITY on EVERY rank with nothing posted.  d_offsets_out (dbde_hip_scatter_post)
+ * must hold max_frames entries on EVERY rank, the root included: the root's block is decoded in place, so its
+ * segment_bytes is not looked at (unless DBDE_HIP_SCATTER_LOOPBACK), but the rebased offsets of its block ARE written to
+ * its d_offsets_out, and their number comes from the scanner's reading of an untrusted stream.  A rank that never calls
+ * this has declared room for nothing. */
 int dbde_hip_scatter_set_capacity(dbde_hip_scatter *s, uint64_t segment_bytes, uint64_t max_frames);
 /* Enqueues the table exchange of `slot` behind everything on the context's stream (the scanner).  Root: the stream, its
  * readable extent, the scanner's offsets and its count word (all device).  Other ranks: NULL, 0, NULL, NULL. */

@@ -52,6 +52,32 @@ def test_every_send_meets_its_receive_and_the_window_is_tiled():
                 assert all(k != dv.GATHER_SEND for _, k, _, _, _ in root_ops)
 
 
+def test_an_undeclared_window_with_peers_is_one_verdict_for_every_rank():
+    """A root that never declared its window (dbde_hip_gather_set_window) used to send "no limit" (~0): the shared check
+    passed everywhere, and the root's own window_bytes test then failed on the root ALONE, after its peers had posted
+    their sends.  With peers, dbde_hip_gather_begin now sends "none" (capacity 0) for an undeclared window: the verdict
+    is a function of the exchanged pairs alone, so a total that overflows is ERR_CAPACITY on every rank and nobody posts."""
+    import dbde_video_cpp_amd as dv
+    NO_LIMIT = (1 << 64) - 1
+    for world in range(2, 9):
+        for root in sorted({0, world - 1, world // 2}):
+            sizes = [1000 + 7 * r for r in range(world)]
+            undeclared = [0] * world                       # what travels now: the root's word is "none"
+            assert dv.gather_check(world, root, sizes, undeclared) == (dv.ERR_CAPACITY, sum(sizes))
+            one_byte = [0] * world
+            one_byte[(root + 1) % world] = 1               # any byte at all overflows a window nobody declared
+            assert dv.gather_check(world, root, one_byte, undeclared) == (dv.ERR_CAPACITY, 1)
+            assert dv.gather_check(world, root, [0] * world, undeclared) == (dv.OK, 0)      # empty rounds still pass
+            # the verdict has no rank argument: what the root alone knows (its window_bytes) cannot enter it, which is
+            # why "no limit" must never travel -- it passes here whatever the total, and only the root could object
+            old = [0] * world
+            old[root] = NO_LIMIT
+            assert dv.gather_check(world, root, sizes, old) == (dv.OK, sum(sizes))
+            # the source holds the rule: with peers an undeclared window is sent as 0, never as the default ~0
+    src = open(os.path.join(ROOT, "dbde-video-cpp_amd", "csrc", "dbde_gather.cpp")).read()
+    assert "g->nranks > 1 && !g->window_declared) ? 0ull" in src
+
+
 def test_plan_rejects_bad_arguments():
     import ctypes as C
     import dbde_video_cpp_amd as dv

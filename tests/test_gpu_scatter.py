@@ -1,8 +1,10 @@
 """GPU, one rank: the native decode-side shard (dbde_hip_scatter_*, csrc/dbde_scatter.cpp) end to end on an MI355X --
 communicator from a unique id, the block table worked out on the device from the scanner's offsets and count, its
 broadcast and the capacity all-gather, the root's block in place and (DBDE_HIP_SCATTER_LOOPBACK) through ncclSend /
-ncclRecv in pieces, the offsets rebased on the device -- and the scattered block decoded bit-exact.  Rank-to-rank
-traffic needs more than one GPU and has not run (tests/test_scatter_plan.py plays worlds 1-8 on the CPU)."""
+ncclRecv in pieces, the offsets rebased on the device -- and the scattered block decoded bit-exact, on the real RCCL.
+The multi-rank branches run with 2-4 real peer processes on one GPU through a stand-in transport in
+tests/test_gpu_exchange_ranks.py (bytes and verdicts, not a measurement, never over xGMI); RCCL itself between ranks
+needs more than one GPU and has not run (tests/test_scatter_plan.py plays worlds 1-8 on the CPU)."""
 import numpy as np
 import pytest
 

@@ -102,6 +102,31 @@ def test_capacity_verdict_is_the_same_on_every_rank():
             assert dv.gather_check(world, root, sizes, caps)[0] == dv.OK
 
 
+def test_the_roots_frame_capacity_counts_in_the_verdict():
+    """The root decodes its block in place, so its SEGMENT capacity is exempt (it advertises ~0 for it) -- but the rebased
+    offsets of its block are written to its d_offsets_out, so its max_frames travels like everybody's: a root whose
+    offsets array is one entry short is ERR_CAPACITY on every rank (the number of frames is the scanner's reading of an
+    untrusted stream).  It used to advertise ~0 for both, and the rebase kernel wrote past a short array."""
+    import dbde_video_cpp_amd as dv
+    NO_LIMIT = (1 << 64) - 1
+    rng = np.random.default_rng(8)
+    for world in range(1, 9):
+        offs, total = random_index(rng, 5 * world + 3)
+        blocks = dv.scatter_blocks(world, offs, total)
+        for root in sorted({0, world - 1, world // 2}):
+            caps = [(b[3], b[1]) for b in blocks]
+            caps[root] = (NO_LIMIT, blocks[root][1])               # what the root sends now: no segment limit, its frames
+            assert dv.scatter_check(blocks, caps) == dv.OK
+            caps[root] = (NO_LIMIT, blocks[root][1] - 1)
+            assert dv.scatter_check(blocks, caps) == dv.ERR_CAPACITY
+            caps[root] = (NO_LIMIT, 0)                             # a root that never called set_capacity
+            assert dv.scatter_check(blocks, caps) == dv.ERR_CAPACITY
+            caps[root] = (0, blocks[root][1])                      # its segment bytes are NOT exempt in the arithmetic:
+            assert dv.scatter_check(blocks, caps) == dv.ERR_CAPACITY   # the exemption is the ~0 it sends, nothing else
+    src = open(os.path.join(ROOT, "dbde-video-cpp_amd", "csrc", "dbde_scatter.cpp")).read()
+    assert "is_root ? ~0ull : s->seg_cap, s->max_frames," in src and "is_root ? ~0ull : s->max_frames" not in src
+
+
 def test_plan_rejects_bad_arguments():
     import ctypes as C
     import dbde_video_cpp_amd as dv
