@@ -62,6 +62,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_trace_map_pixels", "dbde_hip_traces", "dbde16_hip_traces", "dbde_hip_trace_plan", "dbde16_hip_trace_plan",
     "dbde_hip_histogram", "dbde16_hip_histogram", "dbde_hip_histogram_plan", "dbde16_hip_histogram_plan",
     "dbde_hip_decode_binned", "dbde16_hip_decode_binned", "dbde_hip_binned_plan", "dbde16_hip_binned_plan",
+    "dbde_hip_decode_scaled", "dbde16_hip_decode_scaled", "dbde_hip_scaled_plan", "dbde16_hip_scaled_plan",
     "dbde_hip_crop_frames", "dbde16_hip_crop_frames", "dbde_hip_crop_plan", "dbde16_hip_crop_plan",
 ]
 
@@ -212,6 +213,12 @@ def lib():
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_binned_plan", "dbde16_hip_binned_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, C.c_uint, C.POINTER(BinnedPlan)]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_decode_scaled", "dbde16_hip_decode_scaled"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, i, vp, C.c_float, vp, C.c_float, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_scaled_plan", "dbde16_hip_scaled_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, C.POINTER(ScaledPlan)]
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_crop_frames", "dbde16_hip_crop_frames"):
         getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, vp, sz, u64, vp, vp, vp, vp]
@@ -768,6 +775,53 @@ def binned16_plan(W, H, n_frames, bin, x=0, y=0, rw=None, rh=None, stats=("sum",
     return _binned_plan("dbde16_hip_binned_plan", W, H, n_frames, bin, x, y, rw, rh, stats)
 
 
+OUT_F32, OUT_F16, OUT_BF16 = 0, 1, 2   # DBDE_HIP_OUT_* (include/dbde_hip.h)
+
+
+def _scaled_type(dtype):
+    """torch.float32 / float16 / bfloat16 -> (DBDE_HIP_OUT_*, torch dtype)."""
+    table = {torch.float32: OUT_F32, torch.float16: OUT_F16, torch.bfloat16: OUT_BF16}
+    if dtype in table:
+        return table[dtype], dtype
+    raise ValueError(f"unknown output type {dtype!r} (torch.float32, torch.float16 or torch.bfloat16)")
+
+
+class ScaledPlan(C.Structure):
+    """dbde_hip_scaled_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("max_tiles_x", C.c_int32), ("max_tiles_y", C.c_int32), ("chunks_per_frame", C.c_uint32),
+                ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32), ("index_split", C.c_uint32),
+                ("threads", C.c_uint32), ("pieces_x", C.c_uint32), ("lds_bytes", C.c_uint32), ("elem_bytes", C.c_uint32),
+                ("grid", C.c_uint64), ("grid_origins", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def _scaled_plan(fn, W, H, n_frames, x, y, rw, rh, dtype):
+    """scaled_plan / scaled16_plan through the C function named fn."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    out_type = dtype if isinstance(dtype, int) and not isinstance(dtype, bool) else _scaled_type(dtype)[0]
+    pl = ScaledPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, x, y, rw, rh, out_type, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, type={out_type}) -> {rc}")
+    return pl.as_dict()
+
+
+def scaled_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, dtype=OUT_F32):
+    """dbde_hip_scaled_plan: the tile window, index geometry, launch, LDS and output bytes of Codec.decode_scaled (host
+    arithmetic only).  rw / rh default to the rest of the frame; dtype: a torch dtype or a DBDE_HIP_OUT_* value.
+    Raises ValueError where dbde_hip_decode_scaled would return DBDE_HIP_ERR_ARG."""
+    return _scaled_plan("dbde_hip_scaled_plan", W, H, n_frames, x, y, rw, rh, dtype)
+
+
+def scaled16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, dtype=OUT_F32):
+    """dbde16_hip_scaled_plan: scaled_plan for DBDE16 frames (Codec.decode_scaled16)."""
+    return _scaled_plan("dbde16_hip_scaled_plan", W, H, n_frames, x, y, rw, rh, dtype)
+
+
 class CropPlan(C.Structure):
     """dbde_hip_crop_plan_t (include/dbde_hip.h)."""
     _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
@@ -1150,6 +1204,65 @@ class Codec:
         tensors holding the U16 bits)."""
         return self._decode_binned("dbde16_hip_decode_binned", 2, stream, stream_offset, stream_bytes, offsets, W, H, n,
                                    bin, x, y, rw, rh, stats, out, results)
+
+    def _decode_scaled(self, fn, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, dtype, dark, gain,
+                       origins, out, results):
+        """decode_scaled / decode_scaled16 through the C function named fn."""
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        try:
+            out_type, dtype = _scaled_type(dtype)
+        except ValueError as e:
+            raise DbdeError(f"{fn}: {e}") from None
+
+        def term(v, name, default):
+            """(map pointer or None, scalar) of dark= / gain=."""
+            if v is None:
+                return None, default
+            if isinstance(v, torch.Tensor):
+                if v.dtype != torch.float32 or tuple(v.shape) != (H, W) or not v.is_contiguous() or not v.is_cuda:
+                    raise DbdeError(f"{fn}: {name} must be a contiguous float32 device tensor of shape ({H}, {W}), "
+                                    f"not {v.dtype} {tuple(v.shape)}")
+                return v.data_ptr(), default
+            return None, float(v)
+
+        d_ptr, d0 = term(dark, "dark", 0.0)
+        g_ptr, g0 = term(gain, "gain", 1.0)
+        if out is None:
+            out = torch.empty((max(n, 0), rh, rw), dtype=dtype, device=self.device)
+        elif out.dtype != dtype:
+            raise DbdeError(f"{fn}: out is {out.dtype}, dtype= is {dtype}")
+        elif not out.is_cuda or not out.is_contiguous() or out.numel() < max(n, 0) * rw * rh:
+            raise DbdeError(f"{fn}: out must be a contiguous device tensor of at least {max(n, 0)} x {rh} x {rw} "
+                            f"elements, not {tuple(out.shape)}")
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        if n == 0:   # nothing to do (empty tensors have no address to pass): the arguments are still checked
+            _scaled_plan(fn.replace("decode_scaled", "scaled_plan"), W, H, 0, x, y, rw, rh, out_type)
+            return out, results
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                 W, H, n, x, y, rw, rh, origins.data_ptr() if origins is not None else None,
+                                 out_type, d_ptr, d0, g_ptr, g0, out.data_ptr(), results.data_ptr())
+        self._check(rc, fn)
+        return out, results
+
+    def decode_scaled(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x=0, y=0, rw=None, rh=None,
+                      dtype=torch.float32, dark=None, gain=None, origins=None, out=None, results=None):
+        """Scaled float decode of the rw x rh window at (x, y) of n frames (frame f at
+        stream.data_ptr()+stream_offset+offsets[f]): ((pixel.float() - dark) * gain).to(dtype) in one pass, dtype
+        torch.float32, float16 or bfloat16.  dark / gain: None (0.0 / 1.0), a Python float, or a contiguous float32
+        device tensor (H, W) in FRAME coordinates.  rw / rh default to the rest of the frame.  origins: optional int32
+        device tensor (n, 2) of per-frame (x, y), clamped into the frame as decode_roi clamps them.
+        Returns (windows (n, rh, rw) of dtype, results (n, 4) int64) like decode_frames."""
+        return self._decode_scaled("dbde_hip_decode_scaled", stream, stream_offset, stream_bytes, offsets, W, H, n, x, y,
+                                   rw, rh, dtype, dark, gain, origins, out, results)
+
+    def decode_scaled16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x=0, y=0, rw=None, rh=None,
+                        dtype=torch.float32, dark=None, gain=None, origins=None, out=None, results=None):
+        """DBDE16 scaled float decode: decode_scaled's arguments and results over U16 pixels (16 is the stream format;
+        the output type is dtype=)."""
+        return self._decode_scaled("dbde16_hip_decode_scaled", stream, stream_offset, stream_bytes, offsets, W, H, n, x,
+                                   y, rw, rh, dtype, dark, gain, origins, out, results)
 
     def _crop_frames(self, fn, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, out, out_offset,
                      capacity, origins, slot_stride, out_offsets, out_bytes, origins_used, results):

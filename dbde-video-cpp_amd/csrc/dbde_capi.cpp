@@ -21,6 +21,7 @@
 #include "dbde_kernels.h"
 #include "dbde_project_kernels.h"
 #include "dbde_roi_kernels.h"
+#include "dbde_scaled_kernels.h"
 #include "dbde_trace_kernels.h"
 
 using namespace dbde;
@@ -1721,6 +1722,127 @@ int dbde16_hip_decode_binned(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t 
                              dbde_hip_frame_result *d_results) {
     return decode_binned_common(ctx, "decode_binned16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0,
                                 y0, rw, rh, bin, d_sum, d_max, d_min, d_results);
+}
+
+// ---- scaled float decode -------------------------------------------------------------------------------------
+struct ScaledPlan {
+    RoiPlan roi;                      // arguments, tile window, index geometry and launch: the window decoder's (plan_roi)
+    uint32_t elem;                    // bytes of an output element
+    uint64_t out_bytes;
+};
+static const char *plan_scaled(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int out_type, uint32_t pix,
+                               ScaledPlan &pl) {
+    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, kScaledWideThreadsOf(pix))) return why;
+    if (out_type != DBDE_HIP_OUT_F32 && out_type != DBDE_HIP_OUT_F16 && out_type != DBDE_HIP_OUT_BF16)
+        return "output type other than F32, F16, BF16";
+    pl.elem = kScaledElemBytesOf((uint32_t)out_type);
+    pl.out_bytes = (uint64_t)n_frames * (uint64_t)rw * (uint64_t)rh * pl.elem;
+    return nullptr;
+}
+
+static int scaled_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int out_type, uint32_t pix,
+                              dbde_hip_scaled_plan_t *plan) {
+    ScaledPlan pl;
+    if (!plan || plan_scaled(W, H, n_frames, x0, y0, rw, rh, out_type, pix, pl)) return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->tile_x = (int32_t)pl.roi.tx0;
+    plan->tile_y = (int32_t)pl.roi.ty0;
+    plan->tiles_x = (int32_t)pl.roi.ntx;
+    plan->tiles_y = (int32_t)pl.roi.nty;
+    plan->max_tiles_x = (int32_t)pl.roi.max_tx;
+    plan->max_tiles_y = (int32_t)pl.roi.max_ty;
+    plan->chunks_per_frame = pl.roi.dg.cpf;
+    plan->chunk_tiles = pl.roi.dg.ct;
+    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
+    plan->index_split = pl.roi.split;
+    plan->threads = pl.roi.threads;
+    plan->pieces_x = pl.roi.pieces;
+    plan->lds_bytes = kScaledLdsBytesOf(pl.roi.threads, pix);
+    plan->elem_bytes = pl.elem;
+    plan->grid = pl.roi.grid;
+    plan->grid_origins = pl.roi.grid_origins;
+    plan->out_bytes = pl.out_bytes;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_scaled_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int out_type,
+                         dbde_hip_scaled_plan_t *plan) {
+    return scaled_plan_common(W, H, n_frames, x0, y0, rw, rh, out_type, 1u, plan);
+}
+
+int dbde16_hip_scaled_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int out_type,
+                           dbde_hip_scaled_plan_t *plan) {
+    return scaled_plan_common(W, H, n_frames, x0, y0, rw, rh, out_type, 2u, plan);
+}
+
+// Both scaled decoders: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the scaling kernel
+// in slot 2.
+static int decode_scaled_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
+                                size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
+                                int y0, int rw, int rh, const int32_t *d_origins, int out_type, const float *d_dark,
+                                float dark0, const float *d_gain, float gain0, void *d_out,
+                                dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    ScaledPlan pl;
+    if (const char *why = plan_scaled(W, H, n_frames, x0, y0, rw, rh, out_type, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d type %d)", name, why, W, H,
+                    n_frames, rw, rh, x0, y0, out_type);
+    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if (n_frames > 0 && !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null output", name);
+    if (reinterpret_cast<uintptr_t>(d_out) & (pl.elem - 1u))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the output must be %u-byte aligned", name, pl.elem);
+    if ((reinterpret_cast<uintptr_t>(d_dark) | reinterpret_cast<uintptr_t>(d_gain)) & 3u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the maps must be 4-byte aligned", name);
+    if (n_frames == 0) return DBDE_HIP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
+    if (rc) return rc;
+
+    ScaledParams p;
+    memset(&p, 0, sizeof p);
+    p.roi.stream = d_stream;
+    p.roi.frame_offsets = d_frame_offsets;
+    p.roi.stream_bytes = stream_bytes;
+    p.roi.chunk_off = ctx->chunk_off;
+    p.roi.frame_ok = ctx->frame_ok;
+    p.roi.origins = d_origins;
+    p.roi.out = static_cast<uint8_t *>(d_out);
+    p.roi.W = W;
+    p.roi.H = H;
+    p.roi.x0 = x0;
+    p.roi.y0 = y0;
+    p.roi.rw = rw;
+    p.roi.rh = rh;
+    p.roi.w = pl.roi.g.w;
+    p.roi.h = pl.roi.g.h;
+    p.roi.T = pl.roi.g.T;
+    p.roi.geom = pl.roi.dg;
+    p.roi.rows = d_origins ? pl.roi.max_ty : pl.roi.nty;
+    p.roi.pieces = d_origins ? pl.roi.pieces : pl.roi.pieces_fixed;
+    p.dark = d_dark;
+    p.gain = d_gain;
+    p.dark0 = dark0;
+    p.gain0 = gain0;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_decode_scaled(p, (uint32_t)n_frames, pl.roi.threads, pix, (uint32_t)out_type, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_decode_scaled(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                           const int32_t *d_origins, int out_type, const float *d_dark, float dark0, const float *d_gain,
+                           float gain0, void *d_out, dbde_hip_frame_result *d_results) {
+    return decode_scaled_common(ctx, "decode_scaled", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0,
+                                y0, rw, rh, d_origins, out_type, d_dark, dark0, d_gain, gain0, d_out, d_results);
+}
+
+int dbde16_hip_decode_scaled(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                             const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                             const int32_t *d_origins, int out_type, const float *d_dark, float dark0,
+                             const float *d_gain, float gain0, void *d_out, dbde_hip_frame_result *d_results) {
+    return decode_scaled_common(ctx, "decode_scaled16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames,
+                                x0, y0, rw, rh, d_origins, out_type, d_dark, dark0, d_gain, gain0, d_out, d_results);
 }
 
 // ---- compressed-domain crop ---------------------------------------------------------------------------------

@@ -783,6 +783,69 @@ int dbde_hip_binned_plan(int W, int H, int n_frames, int x0, int y0, int rw, int
 int dbde16_hip_binned_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int bin, unsigned stats,
                            dbde_hip_binned_plan_t *plan);
 
+/* ---- scaled float decode: dark-subtracted, gain-corrected F32 / F16 / BF16 ----------------------- */
+/* Scaled decode: the rw x rh window of each of n_frames frames as floating point, v = ((float)p - D) * G per pixel,
+ * straight from the compressed bytes (no integer image is written).
+ * Input and validation: the stream, the window, d_origins and d_results are exactly dbde_hip_decode_roi's -- the same
+ *   index kernel, the same clamping of per-frame origins into [0, W-rw] x [0, H-rh], the same result entries.  A
+ *   rejected frame leaves its window untouched.  No byte at or beyond stream_bytes is read; nothing outside the
+ *   n_frames*rw*rh output elements is written.  n_frames == 0 does nothing.
+ * Value: for the pixel at FRAME coordinates (X, Y) with decoded value p -- exactly the byte dbde_hip_decode_frames
+ *   writes, wrapping minima included -- the value is v = ((float)p - D) * G with
+ *     D = d_dark ? d_dark[Y*W + X] : dark0        G = d_gain ? d_gain[Y*W + X] : gain0.
+ *   The maps are F32, [H][W], pitch W, 4-byte aligned, in frame coordinates: a moving window (d_origins) keeps each
+ *   sensor pixel's own correction, taken at the clamped origin.
+ * Arithmetic: the subtraction and the multiplication are two IEEE binary32 operations, each rounded to nearest even
+ *   (never p*G - D*G, never fused); v is then rounded once, to nearest even, to the output type.  F16 overflow goes to
+ *   +-inf; F16 and BF16 subnormal results are produced, not flushed; the sign of a zero product is IEEE's.  F32
+ *   subnormal intermediates follow the device's default denormal mode (not pinned here).  NaN / Inf in a map
+ *   propagate; NaN payload bits are unspecified.
+ * Output: out_type is DBDE_HIP_OUT_F32, _F16 or _BF16; d_out is [n_frames][rh][rw] of that type, row-major, pitch rw,
+ *   aligned to its element size only (not assumed 16-byte aligned).
+ * Errors: DBDE_HIP_ERR_ARG as dbde_hip_decode_roi, and for an unknown out_type, a NULL d_out with n_frames > 0, or a
+ *   misaligned d_out or map.
+ * Asynchronous on the context's stream; workspace (the decode index) is the context's, grown on demand.  Timing hook:
+ *   the index kernel in slot 1, the scaling kernel in slot 2. */
+enum { DBDE_HIP_OUT_F32 = 0, DBDE_HIP_OUT_F16 = 1, DBDE_HIP_OUT_BF16 = 2 };
+int dbde_hip_decode_scaled(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                           int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                           int out_type, const float *d_dark, float dark0,
+                           const float *d_gain, float gain0,
+                           void *d_out, dbde_hip_frame_result *d_results);
+/* Scaled decode of DBDE16 frames: dbde_hip_decode_scaled's contract with U16 pixels.  Validation is
+ * dbde16_hip_decode_frames' own; p is exactly the U16 value it writes (minima that wrap modulo 2^16 included). */
+int dbde16_hip_decode_scaled(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                             const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                             int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                             int out_type, const float *d_dark, float dark0,
+                             const float *d_gain, float gain0,
+                             void *d_out, dbde_hip_frame_result *d_results);
+/* What dbde_hip_decode_scaled runs (pure host arithmetic, like dbde_hip_binned_plan): validates exactly what
+ * dbde_hip_decode_scaled validates of its sizes, window and type (DBDE_HIP_ERR_ARG otherwise) and reports
+ * dbde_hip_roi_plan's tile window and index geometry, the scaling kernel's launch and LDS, and the output bytes. */
+typedef struct dbde_hip_scaled_plan_t {
+    int32_t tile_x, tile_y;           /* first tile column / row of the window at (x0, y0) */
+    int32_t tiles_x, tiles_y;         /* tiles across / down the window at (x0, y0) covers */
+    int32_t max_tiles_x, max_tiles_y; /* the most any per-frame origin needs */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t threads;                 /* scaling kernel: workgroup size = tiles per workgroup (64, or 256; DBDE16: 128) */
+    uint32_t pieces_x;                /* scaling kernel: workgroups per window tile row (the most any origin needs) */
+    uint32_t lds_bytes;               /* LDS per workgroup (the piece's payload, reused as the band of pixels; the scan) */
+    uint32_t elem_bytes;              /* bytes of an output element: 4, 2, 2 */
+    uint64_t grid;                    /* workgroups without per-frame origins */
+    uint64_t grid_origins;            /* workgroups with per-frame origins */
+    uint64_t out_bytes;               /* n_frames * rw * rh * elem_bytes */
+} dbde_hip_scaled_plan_t;
+int dbde_hip_scaled_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int out_type,
+                         dbde_hip_scaled_plan_t *plan);
+/* The same for dbde16_hip_decode_scaled: its index and 128 tiles per workgroup for windows more than 64 tiles across. */
+int dbde16_hip_scaled_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int out_type,
+                           dbde_hip_scaled_plan_t *plan);
+
 /* ---- compressed-domain crop: a window of each frame as a new stream ------------------------------ */
 /* Crops the rw x rh window at (x0, y0) out of each of n_frames DBDE frames and writes it as a complete DBDE frame of an
  * rw x rh image, without decoding the window: tiles whose valid pixels are unchanged are COPIED (depth byte, minimum,
