@@ -64,6 +64,8 @@ C_ABI_SYMBOLS = [
     "dbde_hip_decode_binned", "dbde16_hip_decode_binned", "dbde_hip_binned_plan", "dbde16_hip_binned_plan",
     "dbde_hip_decode_scaled", "dbde16_hip_decode_scaled", "dbde_hip_scaled_plan", "dbde16_hip_scaled_plan",
     "dbde_hip_crop_frames", "dbde16_hip_crop_frames", "dbde_hip_crop_plan", "dbde16_hip_crop_plan",
+    "dbde_hip_encode_window", "dbde16_hip_encode_window", "dbde_hip_window_encode_plan", "dbde16_hip_window_encode_plan",
+    "dbde_hip_writer_put_window",
 ]
 
 
@@ -226,6 +228,15 @@ def lib():
     for fn in ("dbde_hip_crop_plan", "dbde16_hip_crop_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, u64, C.POINTER(CropPlan)]
         getattr(L, fn).restype = i
+    L.dbde_hip_encode_window.argtypes = [vp, vp, sz, i, i, u64, u64, i, i, i, i, i, vp, u64, vp, vp, vp, sz, u64, vp, vp]
+    L.dbde_hip_encode_window.restype = i
+    L.dbde16_hip_encode_window.argtypes = [vp, vp, sz, i, i, u64, u64, i, i, i, i, i, vp, u64, vp, sz, u64, vp, vp]
+    L.dbde16_hip_encode_window.restype = i
+    for fn in ("dbde_hip_window_encode_plan", "dbde16_hip_window_encode_plan"):
+        getattr(L, fn).argtypes = [u64, sz, i, i, u64, u64, i, i, i, i, i, i, sz, u64, i, C.POINTER(WindowEncodePlan)]
+        getattr(L, fn).restype = i
+    L.dbde_hip_writer_put_window.argtypes = [vp, vp, sz, i, i, u64, u64, i, i, i, vp, u64, vp, vp]
+    L.dbde_hip_writer_put_window.restype = i
     L.dbde_hip_unpack_frame.argtypes = [vp, C.POINTER(vp), i, i, vp]
     L.dbde_hip_pack_frame_header.restype = sz
     L.dbde_hip_pack_frame_header.argtypes = [C.POINTER(FrameHeader), vp]
@@ -864,6 +875,53 @@ def crop16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, slot_stride=0):
     return _crop_plan("dbde16_hip_crop_plan", W, H, n_frames, x, y, rw, rh, slot_stride)
 
 
+class WindowEncodePlan(C.Structure):
+    """dbde_hip_window_encode_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("forwards", C.c_uint32), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32), ("tiles", C.c_uint32),
+                ("lanes_per_row", C.c_uint32), ("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32),
+                ("record_group", C.c_uint32), ("threads", C.c_uint32), ("lds_bytes", C.c_uint32),
+                ("grid", C.c_uint64), ("pitch", C.c_uint64), ("frame_stride", C.c_uint64),
+                ("min_image_bytes", C.c_uint64), ("max_out_frame_bytes", C.c_uint64), ("out_capacity", C.c_uint64),
+                ("workspace_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def _window_encode_plan(fn, pix, W, H, n_frames, x, y, rw, rh, pitch, frame_stride, image_bytes, image_address,
+                        has_origins, out_capacity, slot_stride, n_cu):
+    """window_encode_plan / window_encode16_plan through the C function named fn."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    if image_bytes is None:   # the least extent of this layout
+        pt = pitch or W * pix
+        image_bytes = max(n_frames - 1, 0) * (frame_stride or H * pt) + (H - 1) * pt + W * pix if n_frames else 0
+    pl = WindowEncodePlan()
+    rc = getattr(lib(), fn)(image_address, image_bytes, W, H, pitch, frame_stride, n_frames, x, y, rw, rh,
+                            1 if has_origins else 0, out_capacity, slot_stride, n_cu, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, pitch={pitch}, frame_stride={frame_stride}, image_bytes={image_bytes}, "
+                         f"n={n_frames}, window {rw}x{rh} at {x},{y}, slot_stride={slot_stride}) -> {rc}")
+    return pl.as_dict()
+
+
+def window_encode_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, pitch=0, frame_stride=0, image_bytes=None,
+                       image_address=0, has_origins=False, out_capacity=0, slot_stride=0, n_cu=256):
+    """dbde_hip_window_encode_plan: whether Codec.encode_window forwards to encode_frames, else the window's tiles,
+    chunks, workgroup, grid, LDS and workspace, and the least image_bytes / out_capacity (host arithmetic only).
+    pitch / frame_stride in bytes, 0 = compact; image_bytes None = the least extent; out_capacity 0 = not checked.
+    Raises ValueError where dbde_hip_encode_window would return an error."""
+    return _window_encode_plan("dbde_hip_window_encode_plan", 1, W, H, n_frames, x, y, rw, rh, pitch, frame_stride,
+                               image_bytes, image_address, has_origins, out_capacity, slot_stride, n_cu)
+
+
+def window_encode16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, pitch=0, frame_stride=0, image_bytes=None,
+                         image_address=0, has_origins=False, out_capacity=0, slot_stride=0, n_cu=256):
+    """dbde16_hip_window_encode_plan: window_encode_plan for U16 sources (Codec.encode_window16)."""
+    return _window_encode_plan("dbde16_hip_window_encode_plan", 2, W, H, n_frames, x, y, rw, rh, pitch, frame_stride,
+                               image_bytes, image_address, has_origins, out_capacity, slot_stride, n_cu)
+
+
 def bin_pixels(rh, rw, bin, device=None):
     """int32 (ceil(rh / bin), ceil(rw / bin)): the pixels of each bin of an rw x rh window; bin * bin except in the
     last row and column, whose bins end at the window's edge."""
@@ -1302,6 +1360,89 @@ class Codec:
                                  y, rw, rh, out, out_offset, capacity, origins, slot_stride, out_offsets, out_bytes,
                                  origins_used, results)
 
+    def _window_source(self, images, pix, x, y, rw, rh, origins, capacity, slot_stride):
+        """(n, W, H, pitch, frame_stride, image_bytes, rw, rh) of a strided image tensor for the window encoders; raises
+        DbdeError naming the rule the C call would reject it by."""
+        dtypes = (torch.uint8,) if pix == 1 else (torch.int16, torch.uint16)
+        if images.dtype not in dtypes:
+            raise DbdeError(f"encode_window: images must be {' or '.join(str(d) for d in dtypes)}, not {images.dtype}")
+        if not images.is_cuda or images.dim() not in (2, 3):
+            raise DbdeError("encode_window: images must be a CUDA tensor of shape (n, H, W) or (H, W)")
+        n = images.shape[0] if images.dim() == 3 else 1
+        H, W = int(images.shape[-2]), int(images.shape[-1])
+        if H < 1 or W < 1:
+            raise DbdeError("encode_window: empty image")
+        if W > 1 and images.stride(-1) != 1:
+            raise DbdeError(f"encode_window: the innermost stride must be 1 (is {images.stride(-1)}): pixels of a row are adjacent")
+        pitch = images.stride(-2) * pix if H > 1 else W * pix
+        if pitch < W * pix:
+            raise DbdeError(f"encode_window: pitch {pitch} below W * PIX = {W * pix} (rows overlap)")
+        extent = (H - 1) * pitch + W * pix
+        stride = images.stride(0) * pix if images.dim() == 3 and n > 1 else H * pitch
+        if stride < extent:
+            raise DbdeError(f"encode_window: frame stride {stride} below (H-1) * pitch + W * PIX = {extent} (frames overlap)")
+        image_bytes = images.untyped_storage().nbytes() - images.storage_offset() * images.element_size()
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        if not (1 <= rw <= W and 1 <= rh <= H):
+            raise DbdeError(f"encode_window: window size {rw}x{rh} outside [1, {W}] x [1, {H}]")
+        if not (0 <= x <= W - rw and 0 <= y <= H - rh):
+            raise DbdeError(f"encode_window: window origin ({x}, {y}) outside [0, {W - rw}] x [0, {H - rh}]")
+        if origins is not None and (origins.dtype != torch.int32 or tuple(origins.shape) != (n, 2) or not origins.is_contiguous()):
+            raise DbdeError("encode_window: origins must be a contiguous int32 tensor of shape (n, 2)")
+        fn = "dbde_hip_window_encode_plan" if pix == 1 else "dbde16_hip_window_encode_plan"
+        pl = WindowEncodePlan()
+        rc = getattr(self.L, fn)(images.data_ptr(), image_bytes, W, H, pitch, stride, n, x, y, rw, rh,
+                                 0 if origins is None else 1, 0, 0, 1, C.byref(pl))
+        if rc != OK:
+            raise DbdeError(f"encode_window: {fn} rejects the source ({rc}): image_bytes {image_bytes} below "
+                            f"{(n - 1) * stride + extent}, or too many tiles / chunks in one call")
+        if slot_stride and slot_stride < pl.max_out_frame_bytes:
+            raise DbdeError(f"encode_window: slot_stride {slot_stride} below the window's worst case {pl.max_out_frame_bytes}")
+        need = (n - 1) * slot_stride + pl.max_out_frame_bytes if slot_stride else n * pl.max_out_frame_bytes
+        if capacity < need:
+            raise DbdeError(f"encode_window: capacity {capacity} below the worst case {need}")
+        return n, W, H, pitch, stride, image_bytes, rw, rh
+
+    def encode_window(self, images, out, out_offset, capacity, x=0, y=0, rw=None, rh=None, origins=None, first_index=0,
+                      indices=None, elapsed_ns=None, slot_stride=0, offsets=None, nbytes=None):
+        """Encodes the rw x rh window at (x, y) of each image of `images` -- a uint8 CUDA tensor (n, H, W) or (H, W) whose
+        innermost stride is 1; any other strides are taken as they are, so a sliced view such as frames[:, 3:34, 5:38]
+        goes in without a copy (pitch, frame stride and the readable extent come from the tensor's strides and storage).
+        Frames are written from out.data_ptr()+out_offset exactly as encode_frames writes the window's contiguous copy
+        (alloc_stream(rw, rh, n, slot_stride) sizes `out`).  origins: optional int32 device tensor (n, 2) of per-frame
+        (x, y), clamped into the source.  rw / rh default to the rest of the image.  Anything the C call would reject
+        raises DbdeError before it.  Returns (offsets, nbytes) int64 device tensors."""
+        n, W, H, pitch, stride, image_bytes, rw, rh = self._window_source(images, 1, x, y, rw, rh, origins, capacity, slot_stride)
+        if offsets is None:
+            offsets = torch.empty(n, dtype=torch.int64, device=self.device)
+        if nbytes is None:
+            nbytes = torch.empty(n, dtype=torch.int64, device=self.device)
+        rc = self.L.dbde_hip_encode_window(
+            self.h, images.data_ptr(), image_bytes, W, H, pitch, stride, n, x, y, rw, rh,
+            origins.data_ptr() if origins is not None else None, first_index,
+            indices.data_ptr() if indices is not None else None,
+            elapsed_ns.data_ptr() if elapsed_ns is not None else None,
+            out.data_ptr() + out_offset, capacity, slot_stride, offsets.data_ptr(), nbytes.data_ptr())
+        self._check(rc, "dbde_hip_encode_window")
+        return offsets, nbytes
+
+    def encode_window16(self, images, out, out_offset, capacity, x=0, y=0, rw=None, rh=None, origins=None, first_index=0,
+                        slot_stride=0, offsets=None, nbytes=None):
+        """encode_window for int16 / uint16 images, DBDE16 frames out (worst case per frame:
+        dbde16_hip_max_frame_bytes(rw, rh)); no indices / elapsed_ns, as encode_frames16 has none."""
+        n, W, H, pitch, stride, image_bytes, rw, rh = self._window_source(images, 2, x, y, rw, rh, origins, capacity, slot_stride)
+        if offsets is None:
+            offsets = torch.empty(n, dtype=torch.int64, device=self.device)
+        if nbytes is None:
+            nbytes = torch.empty(n, dtype=torch.int64, device=self.device)
+        rc = self.L.dbde16_hip_encode_window(
+            self.h, images.data_ptr(), image_bytes, W, H, pitch, stride, n, x, y, rw, rh,
+            origins.data_ptr() if origins is not None else None, first_index,
+            out.data_ptr() + out_offset, capacity, slot_stride, offsets.data_ptr(), nbytes.data_ptr())
+        self._check(rc, "dbde16_hip_encode_window")
+        return offsets, nbytes
+
     def trace_map(self, labels, n_labels=None):
         """A TraceMap of this codec from a label image (H, W): numpy, or a torch tensor on any device; 0 = no region,
         1..n_labels = region ids, n_labels defaulting to labels.max()."""
@@ -1617,6 +1758,18 @@ class FileWriter:
                                               elapsed_ns.data_ptr() if elapsed_ns is not None else None)
         if rc != OK:
             raise DbdeError(f"dbde_hip_writer_put failed ({rc}): {self.codec.L.dbde_hip_writer_error(self.h).decode()}")
+
+    def put_window(self, images, x=0, y=0, origins=None, first_index=0, indices=None, elapsed_ns=None):
+        """Appends the writer-sized (W x H) window at (x, y) of each image of a strided uint8 CUDA tensor (n, SH, SW) or
+        (SH, SW), as Codec.encode_window takes it (dbde_hip_writer_put_window)."""
+        cap = 1 << 62   # the writer's own windows are sized for the worst case
+        n, SW, SH, pitch, stride, image_bytes, _, _ = self.codec._window_source(images, 1, x, y, self.W, self.H, origins, cap, 0)
+        rc = self.codec.L.dbde_hip_writer_put_window(self.h, images.data_ptr(), image_bytes, SW, SH, pitch, stride, n, x, y,
+                                                     origins.data_ptr() if origins is not None else None, first_index,
+                                                     indices.data_ptr() if indices is not None else None,
+                                                     elapsed_ns.data_ptr() if elapsed_ns is not None else None)
+        if rc != OK:
+            raise DbdeError(f"dbde_hip_writer_put_window failed ({rc}): {self.codec.L.dbde_hip_writer_error(self.h).decode()}")
 
     def close(self):
         """Returns (frames written, file bytes)."""

@@ -23,6 +23,7 @@
 #include "dbde_roi_kernels.h"
 #include "dbde_scaled_kernels.h"
 #include "dbde_trace_kernels.h"
+#include "dbde_wenc_kernels.h"
 
 using namespace dbde;
 
@@ -103,6 +104,7 @@ struct dbde_hip_ctx {
     uint32_t exp_flags = 0;          // $DBDE_HIP_EXPERIMENT (tuning experiments only)
     uint32_t enc_grid = 0;           // resident workgroups for the persistent encoder
     uint32_t enc16_grid = 0;         // the same for the DBDE16 encoder (queried at its first call)
+    uint32_t wenc_grid[2] = {0, 0};  // the same for the window encoder, DBDE and DBDE16
     int n_cu = 0;
     int mid_dec_per_cu[2][3] = {};   // resident workgroups per CU of decode_mid_kernel (decode_mid_blocks_per_cu)
     uint64_t *diag = nullptr;        // [16] phase cycle sums of diagnostic launches
@@ -2228,6 +2230,177 @@ int dbde16_hip_encode_frames(dbde_hip_ctx *ctx, const uint16_t *d_images, int W,
     HIP_TRY(ctx, dbde16::launch_encode16(p, n_frames, ctx->enc16_grid, ctx->stream));
     span_end(ctx);
     return DBDE_HIP_OK;
+}
+
+// ---- window encode (include/dbde_hip.h) ------------------------------------------------------------
+struct WencPlan {
+    Geometry g;                       // of the window
+    uint64_t pitch, frame_stride, min_image_bytes, max_frame, capacity, workspace;
+    uint32_t lanes_per_row, units, cpf;
+    bool forwards;
+    int code;                         // of the broken rule
+};
+// nullptr when the arguments are good, else what is wrong with them (pl.code: the error code).  pix: 1 = DBDE, 2 = DBDE16.
+static const char *plan_wenc(uint64_t image_address, uint64_t image_bytes, int W, int H, uint64_t pitch, uint64_t frame_stride,
+                             int n_frames, int x0, int y0, int rw, int rh, bool has_origins, uint64_t out_capacity,
+                             bool check_capacity, uint64_t slot_stride, uint32_t pix, WencPlan &pl) {
+    pl.code = DBDE_HIP_ERR_ARG;
+    Geometry src;
+    if (n_frames < 0) return "n_frames < 0";
+    if (!geometry(W, H, src)) return "bad source size";
+    if (rw < 1 || rh < 1 || rw > W || rh > H) return "window size outside [1, W] x [1, H]";
+    if (x0 < 0 || y0 < 0 || x0 > W - rw || y0 > H - rh) return "window origin outside [0, W-rw] x [0, H-rh]";
+    if (!geometry(rw, rh, pl.g)) return "window too large";
+    const uint64_t row_bytes = (uint64_t)W * pix;
+    pl.pitch = pitch ? pitch : row_bytes;
+    if (pl.pitch < row_bytes) return "pitch below W * PIX";
+    if (pl.pitch >= (1ull << 40)) return "pitch too large";
+    const uint64_t frame_extent = (uint64_t)(H - 1) * pl.pitch + row_bytes;
+    pl.frame_stride = frame_stride ? frame_stride : (uint64_t)H * pl.pitch;
+    if (pl.frame_stride < frame_extent) return "frame_stride below (H-1) * pitch + W * PIX";
+    if (pl.frame_stride >= (1ull << 48)) return "frame_stride too large";
+    if (pix == 2u && ((pl.pitch | pl.frame_stride | image_address) & 1u)) return "DBDE16: odd pitch, frame_stride or base address";
+    pl.min_image_bytes = n_frames ? (uint64_t)(n_frames - 1) * pl.frame_stride + frame_extent : 0u;
+    if (image_bytes < pl.min_image_bytes) return "image_bytes below (n-1) * frame_stride + (H-1) * pitch + W * PIX";
+    pl.max_frame = 32ull + (pix == 2u ? 131ull : 66ull) * pl.g.T;
+    pl.capacity = n_frames == 0 ? 0u : (slot_stride ? (uint64_t)(n_frames - 1) * slot_stride + pl.max_frame : (uint64_t)n_frames * pl.max_frame);
+    if (slot_stride && slot_stride < pl.max_frame) {
+        if (pix == 2u) pl.code = DBDE_HIP_ERR_CAPACITY;   // (each as its frame encoder reports it)
+        return "slot_stride below the window's worst case";
+    }
+    if (check_capacity && out_capacity < pl.capacity) { pl.code = DBDE_HIP_ERR_CAPACITY; return "out_capacity below the worst case"; }
+    pl.forwards = !has_origins && rw == W && rh == H && pl.pitch == row_bytes && pl.frame_stride == (uint64_t)H * row_bytes;
+    pl.lanes_per_row = pix == 2u ? pl.g.w : (pl.g.w + 1u) / 2u;
+    const uint64_t units = (uint64_t)pl.g.h * pl.lanes_per_row;
+    pl.units = (uint32_t)units;
+    pl.cpf = (uint32_t)((units + kWencThreads - 1u) / kWencThreads);
+    if (!pl.forwards && (uint64_t)n_frames * pl.cpf >= (1ull << 31)) return "too many chunks in one call";
+    const uint64_t n = (uint64_t)n_frames, gpf = (pl.cpf + kWencGroup - 1u) / kWencGroup;
+    pl.workspace = 16u + 8u * (n * pl.cpf + n * gpf + n + (n + kWencGroup - 1u) / kWencGroup);
+    return nullptr;
+}
+
+static int wenc_plan_common(uint64_t image_address, size_t image_bytes, int W, int H, uint64_t pitch, uint64_t frame_stride,
+                            int n_frames, int x0, int y0, int rw, int rh, int has_origins, size_t out_capacity,
+                            uint64_t slot_stride, int n_cu, uint32_t pix, dbde_hip_window_encode_plan_t *plan) {
+    WencPlan pl;
+    if (!plan || n_cu < 1) return DBDE_HIP_ERR_ARG;
+    if (plan_wenc(image_address, image_bytes, W, H, pitch, frame_stride, n_frames, x0, y0, rw, rh, has_origins != 0,
+                  out_capacity, out_capacity != 0, slot_stride, pix, pl))
+        return pl.code;
+    memset(plan, 0, sizeof *plan);
+    plan->forwards = pl.forwards ? 1u : 0u;
+    plan->tiles_x = pl.g.w;
+    plan->tiles_y = pl.g.h;
+    plan->tiles = pl.g.T;
+    plan->pitch = pl.pitch;
+    plan->frame_stride = pl.frame_stride;
+    plan->min_image_bytes = pl.min_image_bytes;
+    plan->max_out_frame_bytes = pl.max_frame;
+    plan->out_capacity = pl.capacity;
+    if (pl.forwards) return DBDE_HIP_OK;
+    plan->lanes_per_row = pl.lanes_per_row;
+    plan->chunks_per_frame = pl.cpf;
+    plan->chunk_tiles = wenc_chunk_tiles(pix);
+    plan->record_group = kWencGroup;
+    plan->threads = kWencThreads;
+    plan->lds_bytes = kWencLdsBytes;
+    const uint64_t chunks = (uint64_t)n_frames * pl.cpf, resident = (uint64_t)n_cu * kWencBlocksPerCu;
+    plan->grid = chunks < resident ? chunks : resident;
+    plan->workspace_bytes = pl.workspace;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_window_encode_plan(uint64_t image_address, size_t image_bytes, int W, int H, uint64_t pitch, uint64_t frame_stride,
+                                int n_frames, int x0, int y0, int rw, int rh, int has_origins, size_t out_capacity,
+                                uint64_t slot_stride, int n_cu, dbde_hip_window_encode_plan_t *plan) {
+    return wenc_plan_common(image_address, image_bytes, W, H, pitch, frame_stride, n_frames, x0, y0, rw, rh, has_origins,
+                            out_capacity, slot_stride, n_cu, 1u, plan);
+}
+
+int dbde16_hip_window_encode_plan(uint64_t image_address, size_t image_bytes, int W, int H, uint64_t pitch, uint64_t frame_stride,
+                                  int n_frames, int x0, int y0, int rw, int rh, int has_origins, size_t out_capacity,
+                                  uint64_t slot_stride, int n_cu, dbde_hip_window_encode_plan_t *plan) {
+    return wenc_plan_common(image_address, image_bytes, W, H, pitch, frame_stride, n_frames, x0, y0, rw, rh, has_origins,
+                            out_capacity, slot_stride, n_cu, 2u, plan);
+}
+
+// Both window encoders (pix: 1 = DBDE, 2 = DBDE16), timing slot 0.
+static int encode_window_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_images, size_t image_bytes,
+                                int W, int H, uint64_t pitch, uint64_t frame_stride, int n_frames, int x0, int y0, int rw, int rh,
+                                const int32_t *d_origins, uint64_t first_index, const uint64_t *d_indices,
+                                const uint64_t *d_elapsed_ns, uint8_t *d_out, size_t out_capacity, uint64_t slot_stride,
+                                uint64_t *d_frame_offsets, uint64_t *d_frame_bytes) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    WencPlan pl;
+    if (const char *why = plan_wenc(reinterpret_cast<uintptr_t>(d_images), image_bytes, W, H, pitch, frame_stride, n_frames, x0,
+                                    y0, rw, rh, d_origins != nullptr, out_capacity, true, slot_stride, pix, pl))
+        return fail(ctx, pl.code, "%s: %s (W=%d H=%d pitch=%llu stride=%llu n=%d window %dx%d at %d,%d)", name, why, W, H,
+                    (unsigned long long)pitch, (unsigned long long)frame_stride, n_frames, rw, rh, x0, y0);
+    if (!d_images || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if (n_frames == 0) return DBDE_HIP_OK;
+    if (pl.forwards)   // exactly the frame encoders' layout: the plain case stays on the persistent encoder
+        return pix == 2u ? dbde16_hip_encode_frames(ctx, reinterpret_cast<const uint16_t *>(d_images), W, H, n_frames, first_index,
+                                                    d_out, out_capacity, slot_stride, d_frame_offsets, d_frame_bytes)
+                         : dbde_hip_encode_frames(ctx, d_images, W, H, n_frames, first_index, d_indices, d_elapsed_ns, d_out,
+                                                  out_capacity, slot_stride, d_frame_offsets, d_frame_bytes);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = grow(ctx, ctx->w16, ctx->w16_bytes, (size_t)pl.workspace, 1, true);
+    if (rc) return rc;
+    WencParams p;
+    memset(&p, 0, sizeof p);
+    p.images = d_images;
+    p.image_bytes = image_bytes;
+    p.pitch = pl.pitch;
+    p.frame_stride = pl.frame_stride;
+    p.origins = d_origins;
+    p.W = W; p.H = H; p.x0 = x0; p.y0 = y0; p.rw = rw; p.rh = rh;
+    p.narrow = (uint32_t)rw * pix < 16u ? 1u : 0u;
+    p.out = d_out;
+    p.frame_offsets = d_frame_offsets;
+    p.frame_bytes = d_frame_bytes;
+    p.indices = d_indices;
+    p.elapsed_ns = d_elapsed_ns;
+    p.first_index = first_index;
+    p.slot_stride = slot_stride;
+    p.w = pl.g.w; p.h = pl.g.h; p.T = pl.g.T;
+    p.lanes_per_row = pl.lanes_per_row;
+    p.units = pl.units;
+    p.chunks_per_frame = pl.cpf;
+    p.n_frames = (uint32_t)n_frames;
+    const size_t n = (size_t)n_frames, gpf = (pl.cpf + kWencGroup - 1u) / kWencGroup;
+    p.ticket = reinterpret_cast<uint32_t *>(ctx->w16);
+    p.state = reinterpret_cast<unsigned long long *>(ctx->w16 + 16);
+    p.gsum = p.state + n * pl.cpf;
+    p.fsize = p.gsum + n * gpf;
+    p.fgsum = p.fsize + n;
+    p.sticky = ctx->sticky;
+    p.force_tickets = (ctx->exp_flags & 1u) ? 1u : 0u;
+    uint32_t &resident = ctx->wenc_grid[pix - 1u];
+    if (!resident) resident = (uint32_t)(wenc_blocks_per_cu(pix) * ctx->n_cu);
+    span_begin(ctx, 0);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->w16, 0, (size_t)pl.workspace, ctx->stream));
+    HIP_TRY(ctx, launch_encode_window(p, pix, (ctx->exp_flags & 1024u) ? 3u : resident, ctx->stream));   // (experiment bit 10: three workgroups)
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_encode_window(dbde_hip_ctx *ctx, const uint8_t *d_images, size_t image_bytes, int W, int H, uint64_t pitch,
+                           uint64_t frame_stride, int n_frames, int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                           uint64_t first_index, const uint64_t *d_indices, const uint64_t *d_elapsed_ns, uint8_t *d_out,
+                           size_t out_capacity, uint64_t slot_stride, uint64_t *d_frame_offsets, uint64_t *d_frame_bytes) {
+    return encode_window_common(ctx, "encode_window", 1u, d_images, image_bytes, W, H, pitch, frame_stride, n_frames, x0, y0, rw,
+                                rh, d_origins, first_index, d_indices, d_elapsed_ns, d_out, out_capacity, slot_stride,
+                                d_frame_offsets, d_frame_bytes);
+}
+
+int dbde16_hip_encode_window(dbde_hip_ctx *ctx, const uint16_t *d_images, size_t image_bytes, int W, int H, uint64_t pitch,
+                             uint64_t frame_stride, int n_frames, int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                             uint64_t first_index, uint8_t *d_out, size_t out_capacity, uint64_t slot_stride,
+                             uint64_t *d_frame_offsets, uint64_t *d_frame_bytes) {
+    return encode_window_common(ctx, "encode_window16", 2u, reinterpret_cast<const uint8_t *>(d_images), image_bytes, W, H, pitch,
+                                frame_stride, n_frames, x0, y0, rw, rh, d_origins, first_index, nullptr, nullptr, d_out,
+                                out_capacity, slot_stride, d_frame_offsets, d_frame_bytes);
 }
 
 int dbde16_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,

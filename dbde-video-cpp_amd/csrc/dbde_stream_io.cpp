@@ -105,15 +105,27 @@ void writer_free(dbde_hip_writer *w) {
     delete w;
 }
 
+// Source of a put_window batch (dbde_hip_encode_window's arguments); nullptr = contiguous images of the writer's size.
+struct WindowSource {
+    size_t image_bytes;
+    int W, H;
+    uint64_t pitch, frame_stride;
+    int x0, y0;
+    const int32_t *d_origins;
+};
+
 int writer_put_batch(dbde_hip_writer *w, const uint8_t *d_images, int n, uint64_t first_index,
-                     const uint64_t *d_indices, const uint64_t *d_elapsed_ns) {
+                     const uint64_t *d_indices, const uint64_t *d_elapsed_ns, const WindowSource *win = nullptr) {
     hipStream_t st = static_cast<hipStream_t>(dbde_hip_stream_handle(w->ctx));
     Slot &s = w->slot[w->cur];
     Slot &other = w->slot[w->cur ^ 1];
     // this window was last used two batches ago: its bytes must be in the file before reuse
     if (!writer_flush(w, s)) return DBDE_HIP_ERR_HIP;
-    int rc = dbde_hip_encode_frames(w->ctx, d_images, w->W, w->H, n, first_index, d_indices, d_elapsed_ns, s.dev,
-                                    w->cap, 0, w->d_tail, w->d_tail + w->batch);
+    int rc = win ? dbde_hip_encode_window(w->ctx, d_images, win->image_bytes, win->W, win->H, win->pitch, win->frame_stride, n,
+                                          win->x0, win->y0, w->W, w->H, win->d_origins, first_index, d_indices, d_elapsed_ns,
+                                          s.dev, w->cap, 0, w->d_tail, w->d_tail + w->batch)
+                 : dbde_hip_encode_frames(w->ctx, d_images, w->W, w->H, n, first_index, d_indices, d_elapsed_ns, s.dev,
+                                          w->cap, 0, w->d_tail, w->d_tail + w->batch);
     if (rc != DBDE_HIP_OK) { w->err = dbde_hip_last_error(w->ctx); return rc; }
     // total = offset + size of the last frame
     if (hipMemcpyAsync(&w->h_tail[0], w->d_tail + (n - 1), 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -221,6 +233,32 @@ int dbde_hip_writer_put(dbde_hip_writer *w, const uint8_t *d_images, int n_frame
         const int n = n_frames - done < w->batch ? n_frames - done : w->batch;
         int rc = writer_put_batch(w, d_images + pixels * (size_t)done, n, first_index + (uint64_t)done,
                                   d_indices ? d_indices + done : nullptr, d_elapsed_ns ? d_elapsed_ns + done : nullptr);
+        if (rc != DBDE_HIP_OK) { w->failed = true; return rc; }
+        done += n;
+    }
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_writer_put_window(dbde_hip_writer *w, const uint8_t *d_images, size_t image_bytes, int src_W, int src_H,
+                               uint64_t pitch, uint64_t frame_stride, int n_frames, int x0, int y0, const int32_t *d_origins,
+                               uint64_t first_index, const uint64_t *d_indices, const uint64_t *d_elapsed_ns) {
+    if (!w || !d_images || n_frames < 0 || src_W < 1 || src_H < 1) return DBDE_HIP_ERR_ARG;
+    if (w->failed) return DBDE_HIP_ERR_HIP;
+    if (hipSetDevice(dbde_hip_device_index(w->ctx)) != hipSuccess) return DBDE_HIP_ERR_HIP;
+    // the whole call's arguments are checked before its first batch is written (a bad call leaves the writer usable)
+    dbde_hip_window_encode_plan_t plan;
+    if (dbde_hip_window_encode_plan(0, image_bytes, src_W, src_H, pitch, frame_stride, n_frames, x0, y0, w->W, w->H,
+                                    d_origins != nullptr, 0, 0, 1, &plan) != DBDE_HIP_OK) {
+        w->err = "writer: put_window: source layout or window rejected (dbde_hip_window_encode_plan)";
+        return DBDE_HIP_ERR_ARG;
+    }
+    for (int done = 0; done < n_frames;) {
+        const int n = n_frames - done < w->batch ? n_frames - done : w->batch;
+        const size_t skip = (size_t)plan.frame_stride * (size_t)done;
+        const WindowSource win = {image_bytes - skip, src_W, src_H, plan.pitch, plan.frame_stride, x0, y0,
+                                  d_origins ? d_origins + 2 * (size_t)done : nullptr};
+        int rc = writer_put_batch(w, d_images + skip, n, first_index + (uint64_t)done, d_indices ? d_indices + done : nullptr,
+                                  d_elapsed_ns ? d_elapsed_ns + done : nullptr, &win);
         if (rc != DBDE_HIP_OK) { w->failed = true; return rc; }
         done += n;
     }

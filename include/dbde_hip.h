@@ -268,6 +268,12 @@ int dbde_hip_writer_open(dbde_hip_ctx *ctx, const char *path, int W, int H, doub
 int dbde_hip_writer_put(dbde_hip_writer *w, const uint8_t *d_images, int n_frames,
                         uint64_t first_index, const uint64_t *d_indices,
                         const uint64_t *d_elapsed_ns);
+/* Appends the rw x rh = W x H (the writer's size) window at (x0, y0) of n_frames source images of src_W x src_H
+ * pixels (source arguments as dbde_hip_encode_window): the same double-buffered path as dbde_hip_writer_put. */
+int dbde_hip_writer_put_window(dbde_hip_writer *w, const uint8_t *d_images, size_t image_bytes, int src_W, int src_H,
+                               uint64_t pitch, uint64_t frame_stride, int n_frames, int x0, int y0,
+                               const int32_t *d_origins, uint64_t first_index, const uint64_t *d_indices,
+                               const uint64_t *d_elapsed_ns);
 const char *dbde_hip_writer_error(const dbde_hip_writer *w);
 /* Flushes, closes the file and frees the writer; totals are optional outputs. */
 int dbde_hip_writer_close(dbde_hip_writer *w, uint64_t *frames_written, uint64_t *bytes_written);
@@ -922,6 +928,73 @@ int dbde_hip_crop_plan(int W, int H, int n_frames, int x0, int y0, int rw, int r
                        dbde_hip_crop_plan_t *plan);
 int dbde16_hip_crop_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint64_t slot_stride,
                          dbde_hip_crop_plan_t *plan);
+
+/* ---- window encode: a pitched window of each source image as a frame ---------------------------- */
+/* Encodes the rw x rh window at (x0, y0) of each of n_frames source images into DBDE frames, reading the window where
+ * it lies: the mirror of dbde_hip_decode_roi, and dbde_hip_encode_frames for sources that are not n contiguous
+ * pitch-W images (a padded pitch, a ring buffer's frame stride, a region of a sensor, a tracker's moving window).
+ * Source: pixel (x, y) of image f is the byte at d_images + f*frame_stride + y*pitch + x*PIX, PIX = 1 (DBDE16: 2).
+ *   pitch and frame_stride are in BYTES; 0 means the compact value (W*PIX, H*pitch).  Otherwise pitch >= W*PIX and
+ *   frame_stride >= (H-1)*pitch + W*PIX.  DBDE: base, pitch and stride may have any byte alignment.  DBDE16: pitch and
+ *   stride are even and the base is 2-byte aligned.  image_bytes is the readable extent of d_images, as stream_bytes
+ *   is for the decoders: it must cover (n_frames-1)*frame_stride + (H-1)*pitch + W*PIX, and no byte at or beyond it
+ *   is read.
+ * Window: 1 <= rw <= W, 1 <= rh <= H, at any pixel position; tiles are counted from the window's own corner.
+ *   d_origins: optional device int32 [n_frames][2] (x, y) per frame, CLAMPED into [0, W-rw] x [0, H-rh] exactly as
+ *   dbde_hip_decode_roi clamps.  (x0, y0) must lie in that range either way.
+ * Output: frame f is byte for byte what dbde_hip_encode_frames writes for the contiguous rw x rh copy of that window
+ *   (the reference's dbde_pack_frame of it): headers, both layouts (slot_stride 0, or >= the worst case of an rw x rh
+ *   frame), d_frame_offsets, d_frame_bytes, d_indices / d_elapsed_ns, capacity rules and their error codes are that
+ *   call's own, taken for (rw, rh).  d_out may have any alignment.  Only the frames' bytes are written, and the output
+ *   does not depend on any source byte outside the window.  n_frames == 0 does nothing.
+ * Errors: any broken rule above is DBDE_HIP_ERR_ARG (DBDE_HIP_ERR_CAPACITY for out_capacity; for DBDE16 also for a
+ *   slot_stride below the worst case), with nothing launched and nothing written.  The kernel's own limits, also
+ *   DBDE_HIP_ERR_ARG: fewer than 2^27 tiles in the window and fewer than 2^31 chunks (256 lanes of 16 window bytes by
+ *   8 rows each) in one call; offsets inside the source are 64-bit, so a window's bytes are not limited (4096 x 3072
+ *   is 384 chunks a frame).
+ * A call that describes exactly dbde_hip_encode_frames' layout (whole frame, compact pitch and stride, no origins)
+ * is forwarded to it.  Small windows are not a separate form: a window of a few tiles occupies one mostly idle chunk
+ * and is bound by the launch.  Asynchronous on the context's stream; timing hook: slot 0. */
+int dbde_hip_encode_window(dbde_hip_ctx *ctx, const uint8_t *d_images, size_t image_bytes,
+                           int W, int H, uint64_t pitch, uint64_t frame_stride, int n_frames,
+                           int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                           uint64_t first_index, const uint64_t *d_indices, const uint64_t *d_elapsed_ns,
+                           uint8_t *d_out, size_t out_capacity, uint64_t slot_stride,
+                           uint64_t *d_frame_offsets, uint64_t *d_frame_bytes);
+/* The same for U16 pixels in, DBDE16 frames out (what dbde16_hip_encode_frames writes for the window's copy; it has no
+ * d_indices / d_elapsed_ns, so neither has this). */
+int dbde16_hip_encode_window(dbde_hip_ctx *ctx, const uint16_t *d_images, size_t image_bytes,
+                             int W, int H, uint64_t pitch, uint64_t frame_stride, int n_frames,
+                             int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                             uint64_t first_index, uint8_t *d_out, size_t out_capacity, uint64_t slot_stride,
+                             uint64_t *d_frame_offsets, uint64_t *d_frame_bytes);
+/* What the window encoders run (pure host arithmetic, like dbde_hip_crop_plan): validates exactly what they validate
+ * of sizes, strides and alignment and returns their error code.  image_address: the source's base address (only its
+ * alignment matters; 0 = aligned).  out_capacity: 0 = not checked.  has_origins: per-frame origins will be passed (such a call never forwards).
+ * n_cu: compute units of the device (the grid is min(chunks, 4 workgroups per CU)). */
+typedef struct dbde_hip_window_encode_plan_t {
+    uint32_t forwards;                /* 1: the call is dbde_hip_encode_frames' layout and goes there; the kernel fields are 0 */
+    uint32_t tiles_x, tiles_y, tiles; /* of the window */
+    uint32_t lanes_per_row;           /* lanes a tile row takes: ceil(tiles_x / 2) tile pairs (DBDE16: tiles_x tiles) */
+    uint32_t chunks_per_frame;        /* ceil(tiles_y * lanes_per_row / threads) */
+    uint32_t chunk_tiles;             /* tiles of a full chunk: 512 (DBDE16: 256) */
+    uint32_t record_group;            /* chunk (and frame) records per group of the two-level sums: 64 */
+    uint32_t threads, lds_bytes;      /* workgroup size and its LDS */
+    uint64_t grid;                    /* persistent workgroups */
+    uint64_t pitch, frame_stride;     /* as used: the compact values where 0 was passed */
+    uint64_t min_image_bytes;         /* the least image_bytes */
+    uint64_t max_out_frame_bytes;     /* worst case of one frame: max_frame_bytes(rw, rh) */
+    uint64_t out_capacity;            /* the least out_capacity for n_frames and slot_stride */
+    uint64_t workspace_bytes;         /* records, zeroed before each launch */
+} dbde_hip_window_encode_plan_t;
+int dbde_hip_window_encode_plan(uint64_t image_address, size_t image_bytes, int W, int H, uint64_t pitch,
+                                uint64_t frame_stride, int n_frames, int x0, int y0, int rw, int rh, int has_origins,
+                                size_t out_capacity, uint64_t slot_stride, int n_cu,
+                                dbde_hip_window_encode_plan_t *plan);
+int dbde16_hip_window_encode_plan(uint64_t image_address, size_t image_bytes, int W, int H, uint64_t pitch,
+                                  uint64_t frame_stride, int n_frames, int x0, int y0, int rw, int rh, int has_origins,
+                                  size_t out_capacity, uint64_t slot_stride, int n_cu,
+                                  dbde_hip_window_encode_plan_t *plan);
 
 /* ---- kernel timing hook for bench.py ---------------------------------------------------- */
 /* When enabled, every encode / decode call brackets its kernels with HIP events on the
