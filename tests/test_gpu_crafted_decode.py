@@ -8,6 +8,8 @@ lost coverage.  The experiment contexts ($DBDE_HIP_EXPERIMENT 16 and 1024) decod
 describes the default context only, so for them the assertion names the geometry's default form, not the launch
 their flags change.
 Expected values come from the oracle (tests/test_crafted_streams.py ties it to the reference on such frames).
+The geometries here are a handful; tests/test_decode_forms.py holds DECODE_CASES, the table with a row for every
+decoder form at every edge-tile margin, and tests/test_gpu_decode_forms.py runs it with this file's streams and checks.
 """
 import os
 
@@ -100,19 +102,35 @@ def bad_pool(rng, W, H, chunk_tiles, good):
     return bad + [cr.craft(rng, W, H, 16, "random", "boundary", "random")]
 
 
+POOL = 10 + len(cr.BREAKS) + 1     # the whole pool: valid_pool's ten bodies, a frame per broken rule, a DBDE16 frame
+
+
 class Stream:
     """n crafted frames (a pool of distinct bodies, each frame with its own random header), placed in one device
-    buffer, with the oracle's verdict, result row and image of every frame."""
+    buffer, with the oracle's verdict, result row and image of every frame.  `select`: the entries of the whole pool
+    (0 .. POOL-1: valid bodies, then bad_pool's frames) that the stream holds, in that order and cycled over the n
+    frames, whatever n is -- how a batch smaller than the pool gets every body and every break, a few per stream.
+    `used`: the pool entries the stream holds; `depths`: the depth bytes of every frame."""
 
-    def __init__(self, oracle, rng, W, H, n, how="concat", bad=True, chunk_tiles=0, u64s=None):
+    def __init__(self, oracle, rng, W, H, n, how="concat", bad=True, chunk_tiles=0, u64s=None, select=None,
+                 device="cuda"):
         import torch
-        good = valid_pool(rng, W, H, n)
-        pool = good + (bad_pool(rng, W, H, chunk_tiles, good) if bad and n > 1 else [])
-        order = rng.permutation(np.resize(np.arange(len(pool)), n))
-        order[0] = 0                      # the first frame decodes, so does the last
-        order[-1] = 0
-        if n >= 12 and len(good) > 4:     # the all-depth-8 frame at 8 consecutive places: payloads at every residue
-            order[1:9] = 4
+        if select is None:
+            good = valid_pool(rng, W, H, n)
+            pool = good + (bad_pool(rng, W, H, chunk_tiles, good) if bad and n > 1 else [])
+            order = rng.permutation(np.resize(np.arange(len(pool)), n))
+            order[0] = 0                      # the first frame decodes, so does the last
+            order[-1] = 0
+            if n >= 12 and len(good) > 4:     # the all-depth-8 frame at 8 consecutive places: payloads at every residue
+                order[1:9] = 4
+            self.used = {int(k) if k < len(good) else int(k) - len(good) + POOL - len(cr.BREAKS) - 1 for k in order}
+        else:
+            good = valid_pool(rng, W, H, POOL)
+            whole = good + bad_pool(rng, W, H, chunk_tiles, good)
+            assert len(whole) == POOL
+            pool = [whole[k] for k in select]
+            order = np.arange(n) % len(pool)
+            self.used = {int(select[k]) for k in order}
         want = [oracle.unpack_frame(p, W, H) for p in pool]
         self.frames, self.rows, self.images = [], [], []
         for k in order:
@@ -124,10 +142,25 @@ class Stream:
             self.rows.append((fh[0] if adv > 20 else 0xFFFFFFFF, fh[1], fh[2], adv))
             self.images.append(want[k][2] if adv > 20 else None)
         buf, self.lead, offs, self.total = cr.layout(self.frames, how, lead=32)
-        self.buf = torch.from_numpy(buf).cuda()
-        self.offs = torch.from_numpy(offs).cuda()
+        self.buf = torch.from_numpy(buf).to(device)
+        self.offs = torch.from_numpy(offs).to(device)
         self.offs_h = offs
         self.W, self.H, self.n = W, H, n
+
+    @property
+    def depths(self):
+        T = cr.tiles(self.W, self.H)
+        return [fr[24:24 + T] for fr in self.frames]
+
+
+def images_of(c, s, base):
+    """The (n, H, W) images of canvas `c` (host bytes), after the check that the guards in front of and behind them
+    still hold the fill."""
+    size = s.n * s.H * s.W
+    assert len(c) == PAD + base + size + PAD
+    assert (c[:PAD + base] == FILL).all(), "wrote in front of the images"
+    assert (c[PAD + base + size:] == FILL).all(), "wrote behind the images"
+    return c[PAD + base: PAD + base + size].reshape(s.n, s.H, s.W)
 
 
 def decode_into(codec, s, base):
@@ -138,10 +171,7 @@ def decode_into(codec, s, base):
     images = canvas[PAD + base: PAD + base + size].view(s.n, s.H, s.W)
     _, res = codec.decode_frames(s.buf, s.lead, s.total, s.offs, s.W, s.H, s.n, images=images)
     codec.sync()
-    c = canvas.cpu().numpy()
-    assert (c[:PAD + base] == FILL).all(), "wrote in front of the images"
-    assert (c[PAD + base + size:] == FILL).all(), "wrote behind the images"
-    return c[PAD + base: PAD + base + size].reshape(s.n, s.H, s.W), codec.parse_results(res), images.data_ptr()
+    return images_of(canvas.cpu().numpy(), s, base), codec.parse_results(res), images.data_ptr()
 
 
 def check_decode(got, rows, s, what):

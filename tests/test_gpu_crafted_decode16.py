@@ -4,7 +4,7 @@ U16 minima that wrap (min + value > 65535) at the boundary set of every depth 0.
 headers, and frames that break exactly one rule at its edge.  Runs of 256 tiles (the decoder's chunk) that are all
 depth 16, with frames at every byte offset mod 16, take both the swizzled all-depth-16 path (payload at a multiple of
 8 bytes) and the general path.  Expected values: the DBDE16 oracle (the extension's specification) and the oracle's
-header read.
+header read.  MARGIN_CASES give the decoder every right and bottom margin of a cut tile.
 """
 import numpy as np
 import pytest
@@ -20,6 +20,13 @@ FILL = 0xEEEE
 # (W, H, n, how frames are placed): "offsets" puts frame k at byte k mod 16
 CASES = [(8, 8, 40, "offsets"), (61, 37, 20, "residues"), (200, 123, 32, "offsets"), (1024, 768, 16, "offsets"),
          (2048, 1024, 3, "concat")]
+# The one decode form (runs of 256 tiles, one index workgroup per frame) at every right margin rm = W mod 8 and bottom
+# margin dm = H mod 8 in 1..7: frames of one chunk (2 x 2 tiles), and of two, 33 tiles across, so that tile rows
+# straddle the chunk boundary (33 does not divide 256).  A batch of 6 holds valid bodies only (Stream16 cuts its pool
+# to the batch), so the two-chunk frames come once more as batches of 20 with the rejected frames mixed in.
+MARGIN_CASES = [(8 + m, 16 - m, 20, ("offsets", "residues", "concat")[m % 3]) for m in range(1, 8)] \
+    + [(256 + m, 72 - m, 6, ("offsets", "residues", "concat")[m % 3]) for m in range(1, 8)] \
+    + [(256 + m, 64 + m, 20, ("residues", "concat", "offsets")[m % 3]) for m in range(1, 8)]
 
 
 @pytest.fixture(scope="module")
@@ -79,7 +86,8 @@ def check(got, rows, s, what):
                                  f"{tuple(bad[0])}: {got[f][tuple(bad[0])]} != {s.images[f][tuple(bad[0])]}")
 
 
-@pytest.mark.parametrize("W,H,n,how", CASES, ids=[f"{c[0]}x{c[1]}x{c[2]}" for c in CASES])
+@pytest.mark.parametrize("W,H,n,how", CASES + MARGIN_CASES,
+                         ids=[f"{c[0]}x{c[1]}x{c[2]}" for c in CASES + MARGIN_CASES])
 def test_crafted_frames_decode_like_the_oracle(codec, o16, oracle, W, H, n, how):   # noqa: F811
     import torch
     rng = np.random.default_rng(W * 4099 + H * 17 + n)
