@@ -593,11 +593,11 @@ int dbde_hip_encode_frames(dbde_hip_ctx *ctx, const uint8_t *d_images, int W, in
 
     // small launches (one frame per call above all): one workgroup per chunk, epoch-tagged records
     const bool small = pl.kernel == 1;
-    span_begin(ctx, 0);
     {
         int rc = attach_lookback(ctx, p, n_chunks, small);
         if (rc) return rc;
     }
+    span_begin(ctx, 0);   // (after the workspace: a failed attach returns with no span left open)
     if (small) HIP_TRY(ctx, launch_encode_small(p, fast_in, aligned_out, ctx->stream));
     else HIP_TRY(ctx, launch_encode(p, fast_in, aligned_out, ctx->stream));
     span_end(ctx);
@@ -2015,7 +2015,6 @@ int dbde_hip_index_stream_async(dbde_hip_ctx *ctx, const uint8_t *d_stream, size
     const uint64_t maxlen = 32ull + 66ull * g.T, meta = 32ull + 2ull * g.T;
     uint64_t n_seg = stream_bytes / (2 * maxlen);
     if (n_seg > 16) n_seg = 16;   // the signature searches (one maximal frame each, at worst) are the cost: few, wide segments (measured: 8-16)
-    span_begin(ctx, 3);
     if (n_seg >= 2 && max_frames > 0) {
         ScanParams sp;
         sp.stream = d_stream;
@@ -2039,8 +2038,10 @@ int dbde_hip_index_stream_async(dbde_hip_ctx *ctx, const uint8_t *d_stream, size
         sp.seg_count = reinterpret_cast<uint32_t *>(sp.seg_end + n_seg);
         sp.seg_ended = sp.seg_count + n_seg;
         sp.wg_per_seg = 4;                          // workgroups sharing a segment's signature search (measured: 1-4)
+        span_begin(ctx, 3);
         HIP_TRY(ctx, launch_scan_spec(sp, (uint32_t)n_seg, max_frames, d_frame_offsets, d_n_found, ctx->stream));
     } else {
+        span_begin(ctx, 3);
         HIP_TRY(ctx, launch_scan_stream(d_stream, stream_bytes, g.T, max_frames, d_frame_offsets, d_n_found, nullptr, ctx->stream));
     }
     span_end(ctx);
@@ -2192,9 +2193,9 @@ int dbde16_hip_encode_frames(dbde_hip_ctx *ctx, const uint16_t *d_images, int W,
             EncParams q = enc_params(ctx, g, W, H, n_frames, 2u, cpf2, 0u, reinterpret_cast<const uint8_t *>(d_images), d_out,
                                      slot_stride, first_index, d_frame_offsets, d_frame_bytes);
             const bool aligned_out = (reinterpret_cast<uintptr_t>(d_out) & 7u) == 0 && g.T % 8 == 0 && slot_stride % 8 == 0;
-            span_begin(ctx, 0);
             int rc = attach_lookback(ctx, q, q.n_chunks, false);
             if (rc) return rc;
+            span_begin(ctx, 0);
             HIP_TRY(ctx, launch_encode16_fast(q, fast_in, aligned_out, ctx->stream));
             span_end(ctx);
             return DBDE_HIP_OK;

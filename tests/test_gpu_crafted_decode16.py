@@ -41,7 +41,7 @@ def codec():
 class Stream16:
     """n crafted DBDE16 frames with random headers, placed in one device buffer; the oracle's row and image of each."""
 
-    def __init__(self, o16, oracle, rng, W, H, n, how):
+    def __init__(self, o16, oracle, rng, W, H, n, how, device="cuda"):
         import torch
         T = cr.tiles(W, H)
         good = [cr.all_pairs_frame(rng, p, "random", T, bits=16) for p in ("ones", "random")]
@@ -70,8 +70,8 @@ class Stream16:
             self.rows.append((fh[0] if used else 0xFFFFFFFF, fh[1], fh[2], 20 + used))
             self.images.append(img if used else None)
         buf, self.lead, offs, self.total = cr.layout(self.frames, how, lead=32)
-        self.buf = torch.from_numpy(buf).cuda()
-        self.offs = torch.from_numpy(offs).cuda()
+        self.buf = torch.from_numpy(buf).to(device)
+        self.offs = torch.from_numpy(offs).to(device)
         self.W, self.H, self.n = W, H, n
 
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import crafted as cr
+from family_refs import hist_expect as expect
 from test_gpu_project import Batch, Crafted
 
 pytestmark = pytest.mark.gpu
@@ -29,20 +30,6 @@ def codec(dv):
     assert c.arch.startswith("gfx950")
     yield c
     c.close()
-
-
-def expect(images, x, y, rw, rh, shift, bins, keep=None):
-    """int64 (n, bins): the counts of each frame's window (torch images (n, H, W) or a list of numpy images)."""
-    import torch
-    if isinstance(images, list):
-        images = torch.from_numpy(np.stack(images)) if images else torch.zeros((0, y + rh, x + rw), dtype=torch.uint8)
-    win = images[:, y:y + rh, x:x + rw].to(torch.int64)
-    b = (win >> shift).clamp(max=bins - 1).reshape(win.shape[0], -1)
-    out = torch.zeros((win.shape[0], bins), dtype=torch.int64, device=win.device)
-    for f in range(win.shape[0]):
-        if keep is None or keep[f]:
-            out[f] = torch.bincount(b[f], minlength=bins)
-    return out
 
 
 def check(h, want, what=""):

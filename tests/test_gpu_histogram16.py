@@ -6,6 +6,7 @@ the DBDE16 oracle's), v >> shift clamped into the last bin.  Depths 0-16, 12-bit
 import numpy as np
 import pytest
 
+from family_refs import hist_expect16 as expect16
 from test_gpu_roi16 import KINDS, Batch16, images16
 from test_oracle_u16 import o16, unpack16   # noqa: F401  (fixture + helper)
 
@@ -27,18 +28,6 @@ def codec(dv):
     assert c.arch.startswith("gfx950")
     yield c
     c.close()
-
-
-def expect16(images, x, y, rw, rh, shift, bins, keep=None):
-    """int64 (n, bins) from uint16 numpy images (n, H, W)."""
-    import torch
-    w = torch.from_numpy(np.ascontiguousarray(np.asarray(images)[:, y:y + rh, x:x + rw]).astype(np.int64))
-    b = (w >> shift).clamp(max=bins - 1).reshape(w.shape[0], -1)
-    out = torch.zeros((w.shape[0], bins), dtype=torch.int64)
-    for f in range(w.shape[0]):
-        if keep is None or keep[f]:
-            out[f] = torch.bincount(b[f], minlength=bins)
-    return out
 
 
 def twelve_bit(rng, n, W, H):

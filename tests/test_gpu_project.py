@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import crafted as cr
+from family_refs import reduce_numpy   # noqa: F401  (used here and imported from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -63,15 +64,6 @@ def reduce_images(images, x, y, rw, rh, keep=None):
         return dict(max=z.clone(), min=z + 255, sum=z.clone(), sumsq=z.clone(), count=0)
     w = win.to(torch.int64)
     return dict(max=w.amax(0), min=w.amin(0), sum=w.sum(0), sumsq=(w * w).sum(0), count=int(win.shape[0]))
-
-
-def reduce_numpy(images, x, y, rw, rh):
-    """The same over a list of (H, W) numpy images."""
-    if not images:
-        z = np.zeros((rh, rw), np.int64)
-        return dict(max=z, min=z + 255, sum=z, sumsq=z, count=0)
-    w = np.stack([im[y:y + rh, x:x + rw] for im in images]).astype(np.int64)
-    return dict(max=w.max(0), min=w.min(0), sum=w.sum(0), sumsq=(w * w).sum(0), count=len(images))
 
 
 def assert_projection(pr, want, stats=ALL, what=""):

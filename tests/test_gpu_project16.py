@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import crafted as cr
+from family_refs import reduce16
 from test_gpu_roi16 import KINDS, Batch16, images16
 from test_oracle_u16 import o16, unpack16   # noqa: F401  (fixture + helper)
 
@@ -31,15 +32,6 @@ def codec(dv):
     assert c.arch.startswith("gfx950")
     yield c
     c.close()
-
-
-def reduce16(images, x, y, rw, rh):
-    """int64 reductions of the window over a list (or array) of (H, W) uint16 images; the empty projection for none."""
-    if len(images) == 0:
-        z = np.zeros((rh, rw), np.int64)
-        return dict(max=z, min=z + 65535, sum=z, sumsq=z, count=0)
-    w = np.stack([np.asarray(im)[y:y + rh, x:x + rw] for im in images]).astype(np.int64)
-    return dict(max=w.max(0), min=w.min(0), sum=w.sum(0), sumsq=(w * w).sum(0), count=len(images))
 
 
 def values(t):

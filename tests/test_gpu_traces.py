@@ -8,6 +8,7 @@ the results rows must be dbde_hip_decode_frames' own.
 import numpy as np
 import pytest
 
+from family_refs import map_discs, reduce_labels   # noqa: F401  (used here and imported from here)
 from test_gpu_project import Batch, Crafted
 
 pytestmark = pytest.mark.gpu
@@ -33,21 +34,6 @@ def codec(dv):
 
 
 # ---- label maps ----------------------------------------------------------------------------------------------------
-def map_discs(W, H, seed=1, count=None):
-    """Random discs (later ones over earlier ones): whole and mixed tiles."""
-    rng = np.random.default_rng(seed)
-    lab = np.zeros((H, W), np.int32)
-    count = count or max(2, min(300, W * H // 400))
-    yy, xx = np.mgrid[0:H, 0:W]
-    r_max = max(2, min(W, H) // 6)
-    for k in range(count):
-        cx, cy, r = rng.integers(0, W), rng.integers(0, H), rng.integers(1, r_max + 1)
-        y0, y1, x0, x1 = max(0, cy - r), min(H, cy + r + 1), max(0, cx - r), min(W, cx + r + 1)
-        sub = (yy[y0:y1, x0:x1] - cy) ** 2 + (xx[y0:y1, x0:x1] - cx) ** 2 <= r * r
-        lab[y0:y1, x0:x1][sub] = k + 1
-    return lab, count
-
-
 def map_blocks(W, H, b=16):
     """8-aligned blocks of b x b, one label each: only whole tiles where the frame is a multiple of 8."""
     by, bx = np.mgrid[0:H, 0:W]
@@ -92,30 +78,6 @@ MAPS = {"discs": map_discs, "blocks": map_blocks, "pixels": map_pixels, "edges":
 
 
 # ---- expected values -----------------------------------------------------------------------------------------------
-def reduce_labels(images, labels, L, pix_max=255):
-    """int64 reductions of (n, H, W) images (torch, any integer type holding the values) over the label map:
-    dict of (n, L) int64 tensors on the images' device.  The empty reduction where a label has no pixels."""
-    import torch
-    dev = images.device
-    n = images.shape[0]
-    lab = torch.from_numpy(np.ascontiguousarray(labels, np.int64)).to(dev).reshape(-1)
-    keep = lab > 0
-    idx = (lab[keep] - 1).unsqueeze(0)
-    out = dict(max=torch.zeros((n, L), dtype=torch.int64, device=dev),
-               min=torch.full((n, L), pix_max, dtype=torch.int64, device=dev),
-               sum=torch.zeros((n, L), dtype=torch.int64, device=dev),
-               sumsq=torch.zeros((n, L), dtype=torch.int64, device=dev))
-    for f0 in range(0, n, 4):   # a few frames at a time: 4096 x 3072 int64 images are large
-        v = images[f0:f0 + 4].reshape(min(4, n - f0), -1)[:, keep].to(torch.int64)
-        ix = idx.expand(v.shape[0], -1)
-        sl = slice(f0, f0 + v.shape[0])
-        out["max"][sl] = out["max"][sl].scatter_reduce(1, ix, v, "amax", include_self=True)
-        out["min"][sl] = out["min"][sl].scatter_reduce(1, ix, v, "amin", include_self=True)
-        out["sum"][sl] = out["sum"][sl].scatter_add(1, ix, v)
-        out["sumsq"][sl] = out["sumsq"][sl].scatter_add(1, ix, v * v)
-    return out
-
-
 def values(t):
     """A trace output as int64 (max / min int16 tensors hold U16 bits)."""
     import torch
