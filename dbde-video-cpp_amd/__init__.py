@@ -66,6 +66,8 @@ C_ABI_SYMBOLS = [
     "dbde_hip_crop_frames", "dbde16_hip_crop_frames", "dbde_hip_crop_plan", "dbde16_hip_crop_plan",
     "dbde_hip_encode_window", "dbde16_hip_encode_window", "dbde_hip_window_encode_plan", "dbde16_hip_window_encode_plan",
     "dbde_hip_writer_put_window",
+    "dbde_hip_project_groups", "dbde16_hip_project_groups", "dbde_hip_project_groups_plan",
+    "dbde16_hip_project_groups_plan",
 ]
 
 
@@ -188,6 +190,13 @@ def lib():
     L.dbde16_hip_project.restype = i
     L.dbde16_hip_project_plan.argtypes = [i, i, i, i, i, i, i, C.c_uint, i, C.POINTER(ProjectPlan)]
     L.dbde16_hip_project_plan.restype = i
+    for fn in ("dbde_hip_project_groups", "dbde16_hip_project_groups"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, i, vp, i, i, i, vp, vp, vp, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_project_groups_plan", "dbde16_hip_project_groups_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, i, i, i, i, u64, u64, u64, u64, u64, i,
+                                   C.POINTER(GroupProjectPlan)]
+        getattr(L, fn).restype = i
     L.dbde_hip_trace_map_summary.argtypes = [vp, i, i, i, C.POINTER(TraceMapInfo), vp]
     L.dbde_hip_trace_map_summary.restype = i
     L.dbde_hip_trace_map_create.argtypes = [vp, vp, i, i, i, C.POINTER(vp)]
@@ -580,6 +589,120 @@ class Projection:
         """Per-pixel population standard deviation (float64, on the device); NaN where no frame contributed."""
         n = self.count.to(torch.float64)
         m = self.sum.to(torch.float64) / n
+        return (self.sumsq.to(torch.float64) / n - m * m).clamp_(min=0.0).sqrt_()
+
+
+SUM_U32, SUM_U16 = 0, 1
+
+
+def _sum_type(sum_dtype):
+    """torch.int32 (U32 bits) / torch.int16 (U16 bits), or SUM_U32 / SUM_U16 -> dbde_hip_project_groups' sum_type."""
+    if isinstance(sum_dtype, int) and sum_dtype in (SUM_U32, SUM_U16):
+        return sum_dtype
+    if torch is not None and sum_dtype == torch.int32:
+        return SUM_U32
+    if torch is not None and sum_dtype == torch.int16:
+        return SUM_U16
+    raise ValueError(f"sum_dtype must be torch.int32 or torch.int16, not {sum_dtype!r}")
+
+
+class GroupProjectPlan(C.Structure):
+    """dbde_hip_project_groups_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32),
+                ("index_split", C.c_uint32), ("threads", C.c_uint32), ("pieces_x", C.c_uint32),
+                ("runs", C.c_uint32), ("groups_per_run", C.c_uint32), ("max_group_frames", C.c_uint32),
+                ("stats", C.c_uint32), ("grid", C.c_uint64), ("sum_bytes", C.c_uint64), ("max_bytes", C.c_uint64),
+                ("min_bytes", C.c_uint64), ("sumsq_bytes", C.c_uint64), ("counts_bytes", C.c_uint64),
+                ("workspace_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def _project_groups_plan(fn, W, H, n_frames, x, y, rw, rh, group_frames, has_group_starts, n_groups, stats, sum_dtype,
+                         accumulate, n_cu, addresses):
+    """project_groups_plan / project_groups16_plan through the C function named fn."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    g = 0 if group_frames is None else int(group_frames)
+    if n_groups is None:
+        if has_group_starts or g < 1:
+            raise ValueError("n_groups is needed (only the uniform form implies it)")
+        n_groups = -(-n_frames // g)
+    mask = stats_mask(stats)
+    addr = {name: (4096 if mask & bit else 0) for name, bit in STATS.items()}
+    addr["counts"] = 4096
+    addr.update(addresses or {})
+    pl = GroupProjectPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, x, y, rw, rh, g, 1 if has_group_starts else 0, n_groups,
+                            _sum_type(sum_dtype), int(accumulate), addr["max"], addr["min"], addr["sum"], addr["sumsq"],
+                            addr["counts"], n_cu, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, g={g}, starts={has_group_starts}, "
+                         f"groups={n_groups}, {stats}) -> {rc}")
+    return pl.as_dict()
+
+
+def project_groups_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, group_frames=None, has_group_starts=False,
+                        n_groups=None, stats=("max", "min", "sum", "sumsq"), sum_dtype=SUM_U32, accumulate=False,
+                        n_cu=256, addresses=None):
+    """dbde_hip_project_groups_plan: the tile window, index geometry, launch and plane sizes of a grouped projection
+    (host arithmetic only).  n_groups defaults to ceil(n_frames / group_frames) in the uniform form.  addresses: optional
+    {"max" | "min" | "sum" | "sumsq" | "counts": address} standing for the call's output pointers (0 = NULL; the default
+    is an aligned address for every statistic in `stats`).  Raises ValueError where dbde_hip_project_groups would return
+    DBDE_HIP_ERR_ARG."""
+    return _project_groups_plan("dbde_hip_project_groups_plan", W, H, n_frames, x, y, rw, rh, group_frames,
+                                has_group_starts, n_groups, stats, sum_dtype, accumulate, n_cu, addresses)
+
+
+def project_groups16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, group_frames=None, has_group_starts=False,
+                          n_groups=None, stats=("max", "min", "sum", "sumsq"), sum_dtype=SUM_U32, accumulate=False,
+                          n_cu=256, addresses=None):
+    """dbde16_hip_project_groups_plan: project_groups_plan for DBDE16 streams (Codec.project_groups16)."""
+    return _project_groups_plan("dbde16_hip_project_groups_plan", W, H, n_frames, x, y, rw, rh, group_frames,
+                                has_group_starts, n_groups, stats, sum_dtype, accumulate, n_cu, addresses)
+
+
+class GroupProjection:
+    """Device tensors of a grouped projection (Codec.project_groups): max / min uint8 (n_groups, rh, rw), sum int32
+    holding the U32 bits (int16 holding U16 bits with sum_dtype=torch.int16), sumsq int64, counts int32 (n_groups,).
+    A statistic that was not asked for is None.  Codec.project_groups16's max / min are int16 tensors holding the U16
+    bits."""
+
+    def __init__(self, max=None, min=None, sum=None, sumsq=None, counts=None):
+        self.max, self.min, self.sum, self.sumsq, self.counts = max, min, sum, sumsq, counts
+
+    @classmethod
+    def empty(cls, n_groups, rh, rw, stats, device, pix=1, sum_dtype=None):
+        """Uninitialised planes for `stats`; pix: bytes per pixel of max / min (1: uint8, 2: int16 for DBDE16)."""
+        mask = stats_mask(stats)
+        if pix not in (1, 2):
+            raise ValueError(f"pix must be 1 or 2, not {pix!r}")
+        sum_dtype = torch.int32 if sum_dtype is None else sum_dtype
+        _sum_type(sum_dtype)
+        mm_dtype = torch.uint8 if pix == 1 else torch.int16
+        new = lambda dt: torch.empty((n_groups, rh, rw), dtype=dt, device=device)   # noqa: E731
+        return cls(new(mm_dtype) if mask & 1 else None, new(mm_dtype) if mask & 2 else None,
+                   new(sum_dtype) if mask & 4 else None, new(torch.int64) if mask & 8 else None,
+                   torch.zeros(n_groups, dtype=torch.int32, device=device))
+
+    def sums(self):
+        """The sums as int64 values (the U32 / U16 bits unsigned)."""
+        bits = 0xFFFF if self.sum.dtype == torch.int16 else 0xFFFFFFFF
+        return self.sum.to(torch.int64) & bits
+
+    def _n(self):
+        return (self.counts.to(torch.int64) & 0xFFFFFFFF).to(torch.float64).view(-1, 1, 1)
+
+    def mean(self):
+        """Per-group, per-pixel mean (float64, on the device); NaN for a group without an accepted frame."""
+        return self.sums().to(torch.float64) / self._n()
+
+    def std(self):
+        """Per-group, per-pixel population standard deviation (float64, on the device); NaN for a group with count 0."""
+        n = self._n()
+        m = self.sums().to(torch.float64) / n
         return (self.sumsq.to(torch.float64) / n - m * m).clamp_(min=0.0).sqrt_()
 
 
@@ -1183,6 +1306,60 @@ class Codec:
         its statistics are the ones computed.  Returns (Projection, results (n, 4) int64) like decode_frames."""
         return self._project("dbde_hip_project", 1, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh,
                              stats, out, accumulate, results)
+
+    def _project_groups(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, group_frames,
+                        group_starts, stats, sum_dtype, accumulate, out, results):
+        """project_groups / project_groups16 through the C function named fn; pix: bytes per pixel of max / min."""
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        if (group_frames is None) == (group_starts is None):
+            raise ValueError("give exactly one of group_frames= and group_starts=")
+        if group_starts is not None:
+            if not torch.is_tensor(group_starts):
+                group_starts = torch.as_tensor(np.asarray(group_starts, dtype=np.int64).astype(np.uint32).view(np.int32),
+                                               device=self.device)
+            if group_starts.dtype != torch.int32 or group_starts.dim() != 1 or not group_starts.is_contiguous():
+                raise ValueError("group_starts must be a contiguous 1-D int32 tensor (the U32 bits)")
+            n_groups, g = group_starts.numel() - 1, 0
+        else:
+            g = int(group_frames)
+            n_groups = -(-n // g) if g > 0 else 0
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out= (the projection to continue)")
+            out = GroupProjection.empty(max(n_groups, 0), rh, rw, stats, self.device, pix=pix, sum_dtype=sum_dtype)
+        sum_type = _sum_type(out.sum.dtype if out.sum is not None else sum_dtype)
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        if group_starts is None and n == 0 and g > 0:
+            return out, results   # no frame, no group: nothing to do (planes of no group have no address to pass)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                 W, H, n, x, y, rw, rh, g, ptr(group_starts), n_groups, sum_type,
+                                 1 if accumulate else 0, ptr(out.max), ptr(out.min), ptr(out.sum), ptr(out.sumsq),
+                                 ptr(out.counts), ptr(results) if n > 0 else None)
+        self._check(rc, fn)
+        return out, results
+
+    def project_groups(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x=0, y=0, rw=None, rh=None,
+                       group_frames=None, group_starts=None, stats=("max", "min", "sum", "sumsq"),
+                       sum_dtype=None, accumulate=False, out=None, results=None):
+        """Grouped temporal projection: Codec.project's reduction once per group of frames.  group_frames=g: group k is
+        frames [k*g, min((k+1)*g, n)).  group_starts: n_groups + 1 frame numbers (a sequence, or an int32 device tensor
+        holding U32 bits), group k is frames [s[k], s[k+1]) clamped into [0, n].  sum_dtype: torch.int32 (the default:
+        U32 bits) or torch.int16 (U16 bits; groups of at most 257 frames, no accumulate).  out: a GroupProjection to
+        write into (accumulate=True continues it).  Returns (GroupProjection, results (n, 4) int64)."""
+        return self._project_groups("dbde_hip_project_groups", 1, stream, stream_offset, stream_bytes, offsets, W, H, n,
+                                    x, y, rw, rh, group_frames, group_starts, stats,
+                                    torch.int32 if sum_dtype is None else sum_dtype, accumulate, out, results)
+
+    def project_groups16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x=0, y=0, rw=None, rh=None,
+                         group_frames=None, group_starts=None, stats=("max", "min", "sum", "sumsq"),
+                         sum_dtype=None, accumulate=False, out=None, results=None):
+        """project_groups for DBDE16 streams: max / min int16 tensors holding the U16 bits, U32 sums only."""
+        return self._project_groups("dbde16_hip_project_groups", 2, stream, stream_offset, stream_bytes, offsets, W, H,
+                                    n, x, y, rw, rh, group_frames, group_starts, stats,
+                                    torch.int32 if sum_dtype is None else sum_dtype, accumulate, out, results)
 
     def _histogram(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, shift, bins,
                    per_frame, total, out, accumulate, results):

@@ -17,6 +17,7 @@
 #include "dbde16_kernels.h"
 #include "dbde_binned_kernels.h"
 #include "dbde_crop_kernels.h"
+#include "dbde_gproject_kernels.h"
 #include "dbde_hist_kernels.h"
 #include "dbde_kernels.h"
 #include "dbde_project_kernels.h"
@@ -1104,6 +1105,213 @@ int dbde16_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream
                        uint64_t *d_count, dbde_hip_frame_result *d_results) {
     return project_common(ctx, "project16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
                           rh, accumulate, d_max, d_min, d_sum, d_sumsq, d_count, d_results);
+}
+
+// ---- grouped temporal projections --------------------------------------------------------
+struct GroupsPlan {
+    RoiPlan roi;                      // arguments, tile window and index geometry: the window decoder's (plan_roi)
+    uint32_t stats;
+    uint32_t pieces, rows, runs, gpr;
+    uint64_t grid;
+    uint64_t max_bytes, min_bytes, sum_bytes, sumsq_bytes, counts_bytes;
+};
+// Groups per run: a run is cut only to fill the device (about 4 workgroups per CU, project's segment rule with whole
+// groups as the unit) and never below kGProjMinFramesPerRun frames, which would start a pipeline for a handful of
+// frames.  The ragged form's groups live on the device: it counts n_frames / n_groups frames per group.
+// The *_addr arguments are the call's output pointers (0 = NULL); only their alignment is looked at.
+static constexpr uint32_t kGProjMinFramesPerRun = 32;
+static const char *plan_groups(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int group_frames,
+                               bool has_starts, int n_groups, int sum_type, int accumulate, uint64_t max_addr,
+                               uint64_t min_addr, uint64_t sum_addr, uint64_t sumsq_addr, uint64_t counts_addr,
+                               int n_cu, uint32_t pix, GroupsPlan &pl) {
+    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, pix == 2u ? kRoi16WideThreads : kRoiWideThreads))
+        return why;
+    const unsigned stats = (max_addr ? kProjMax : 0u) | (min_addr ? kProjMin : 0u) | (sum_addr ? kProjSum : 0u) |
+                           (sumsq_addr ? kProjSumSq : 0u);
+    if (!stats) return "no plane requested";
+    if (!counts_addr) return "d_counts is required";
+    if (accumulate != 0 && accumulate != 1) return "accumulate must be 0 or 1";
+    if (sum_type != DBDE_HIP_SUM_U32 && sum_type != DBDE_HIP_SUM_U16) return "unknown sum_type";
+    if (has_starts == (group_frames != 0)) return "exactly one of group_frames and d_group_starts must be given";
+    if (n_groups < 0) return "n_groups is negative";
+    const uint64_t n = (uint64_t)n_frames;
+    uint64_t max_group;   // frames the largest group can hold
+    if (has_starts) {
+        if (n_groups < 1) return "the ragged form needs n_groups >= 1";
+        if (n > kGProjMaxGroupFrames) return "the ragged form needs n_frames <= 65,536";
+        max_group = n;
+    } else {
+        if (group_frames < 1 || (uint32_t)group_frames > kGProjMaxGroupFrames) return "group_frames must be 1..65,536";
+        if ((uint64_t)n_groups != (n + (uint64_t)group_frames - 1u) / (uint64_t)group_frames)
+            return "n_groups must equal ceil(n_frames / group_frames)";
+        max_group = (uint64_t)group_frames;
+    }
+    if (sum_type == DBDE_HIP_SUM_U16) {
+        if (pix != 1u) return "DBDE16 sums are U32 only";
+        if (max_group > kGProjMaxGroupFramesU16) return "a U16 sum needs groups of at most 257 frames";
+        if (accumulate) return "a U16 sum cannot accumulate";
+    }
+    if ((max_addr | min_addr) & (pix - 1u)) return "U16 planes must be 2-byte aligned";
+    if (sum_addr & (sum_type == DBDE_HIP_SUM_U16 ? 1u : 3u)) return "d_sum is misaligned";
+    if (sumsq_addr & 7u) return "d_sumsq must be 8-byte aligned";
+    if (counts_addr & 3u) return "d_counts must be 4-byte aligned";
+    pl.stats = stats;
+    const uint32_t tiles = kProjTilesOf(pix);
+    pl.pieces = (pl.roi.ntx + tiles - 1u) / tiles;
+    pl.rows = pl.roi.nty;
+    const uint64_t base = (uint64_t)pl.pieces * pl.rows, ng = (uint64_t)n_groups;
+    const uint64_t target = 4ull * (uint64_t)(n_cu > 0 ? n_cu : 1);
+    uint64_t runs = base >= target ? 1u : (target + base - 1u) / base;
+    uint64_t per_group = has_starts ? (ng ? n / ng : 0u) : (uint64_t)group_frames;   // frames of a group (ragged: the mean)
+    if (per_group < 1u) per_group = 1u;
+    const uint64_t min_gpr = (kGProjMinFramesPerRun + per_group - 1u) / per_group;
+    uint64_t gpr = ng ? (ng + runs - 1u) / runs : 1u;
+    if (gpr < min_gpr) gpr = min_gpr;
+    if (gpr > ng && ng) gpr = ng;
+    if (gpr < 1u) gpr = 1u;
+    runs = ng ? (ng + gpr - 1u) / gpr : 0u;   // no empty run
+    pl.runs = (uint32_t)runs;
+    pl.gpr = (uint32_t)gpr;
+    pl.grid = base * runs;
+    if (pl.grid >= (1ull << 31)) return "too many workgroups in one call";
+    const uint64_t plane = (uint64_t)rw * (uint64_t)rh * ng;
+    pl.max_bytes = (stats & kProjMax) ? pix * plane : 0u;
+    pl.min_bytes = (stats & kProjMin) ? pix * plane : 0u;
+    pl.sum_bytes = (stats & kProjSum) ? (sum_type == DBDE_HIP_SUM_U16 ? 2u : 4u) * plane : 0u;
+    pl.sumsq_bytes = (stats & kProjSumSq) ? 8u * plane : 0u;
+    pl.counts_bytes = 4u * ng;
+    return nullptr;
+}
+
+static int groups_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int group_frames,
+                              int has_group_starts, int n_groups, int sum_type, int accumulate, uint64_t max_address,
+                              uint64_t min_address, uint64_t sum_address, uint64_t sumsq_address,
+                              uint64_t counts_address, int n_cu, uint32_t pix, dbde_hip_project_groups_plan_t *plan) {
+    GroupsPlan pl;
+    if (!plan || (has_group_starts != 0 && has_group_starts != 1) ||
+        plan_groups(W, H, n_frames, x0, y0, rw, rh, group_frames, has_group_starts != 0, n_groups, sum_type, accumulate,
+                    max_address, min_address, sum_address, sumsq_address, counts_address, n_cu, pix, pl))
+        return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->tile_x = (int32_t)pl.roi.tx0;
+    plan->tile_y = (int32_t)pl.roi.ty0;
+    plan->tiles_x = (int32_t)pl.roi.ntx;
+    plan->tiles_y = (int32_t)pl.roi.nty;
+    plan->chunks_per_frame = pl.roi.dg.cpf;
+    plan->chunk_tiles = pl.roi.dg.ct;
+    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
+    plan->index_split = pl.roi.split;
+    plan->threads = kProjThreads;
+    plan->pieces_x = pl.pieces;
+    plan->runs = pl.runs;
+    plan->groups_per_run = pl.gpr;
+    plan->max_group_frames = kGProjMaxGroupFrames;
+    plan->stats = pl.stats;
+    plan->grid = pl.grid;
+    plan->sum_bytes = pl.sum_bytes;
+    plan->max_bytes = pl.max_bytes;
+    plan->min_bytes = pl.min_bytes;
+    plan->sumsq_bytes = pl.sumsq_bytes;
+    plan->counts_bytes = pl.counts_bytes;
+    plan->workspace_bytes = 0;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_project_groups_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int group_frames,
+                                 int has_group_starts, int n_groups, int sum_type, int accumulate, uint64_t max_address,
+                                 uint64_t min_address, uint64_t sum_address, uint64_t sumsq_address,
+                                 uint64_t counts_address, int n_cu, dbde_hip_project_groups_plan_t *plan) {
+    return groups_plan_common(W, H, n_frames, x0, y0, rw, rh, group_frames, has_group_starts, n_groups, sum_type,
+                              accumulate, max_address, min_address, sum_address, sumsq_address, counts_address, n_cu, 1u,
+                              plan);
+}
+
+int dbde16_hip_project_groups_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int group_frames,
+                                   int has_group_starts, int n_groups, int sum_type, int accumulate, uint64_t max_address,
+                                   uint64_t min_address, uint64_t sum_address, uint64_t sumsq_address,
+                                   uint64_t counts_address, int n_cu, dbde_hip_project_groups_plan_t *plan) {
+    return groups_plan_common(W, H, n_frames, x0, y0, rw, rh, group_frames, has_group_starts, n_groups, sum_type,
+                              accumulate, max_address, min_address, sum_address, sumsq_address, counts_address, n_cu, 2u,
+                              plan);
+}
+
+// Both grouped projections: the index (pix: 1 = DBDE, 2 = DBDE16) in timing slot 1, the grouped kernel in slot 2.
+static int project_groups_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
+                                 size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                                 int x0, int y0, int rw, int rh, int group_frames, const uint32_t *d_group_starts,
+                                 int n_groups, int sum_type, int accumulate, void *d_max, void *d_min, void *d_sum,
+                                 uint64_t *d_sumsq, uint32_t *d_counts, dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    GroupsPlan pl;
+    if (const char *why = plan_groups(W, H, n_frames, x0, y0, rw, rh, group_frames, d_group_starts != nullptr, n_groups,
+                                      sum_type, accumulate, reinterpret_cast<uintptr_t>(d_max),
+                                      reinterpret_cast<uintptr_t>(d_min), reinterpret_cast<uintptr_t>(d_sum),
+                                      reinterpret_cast<uintptr_t>(d_sumsq), reinterpret_cast<uintptr_t>(d_counts),
+                                      ctx->n_cu, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d, g=%d groups=%d)", name, why, W,
+                    H, n_frames, rw, rh, x0, y0, group_frames, n_groups);
+    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if (n_groups == 0) return DBDE_HIP_OK;   // (uniform form, n_frames == 0)
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n_frames > 0) {
+        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
+        if (rc) return rc;
+    }
+    GProjParams p;
+    memset(&p, 0, sizeof p);
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.n_frames = (uint32_t)n_frames;
+    p.x0 = x0;
+    p.y0 = y0;
+    p.rw = rw;
+    p.rh = rh;
+    p.T = pl.roi.g.T;
+    p.w = pl.roi.g.w;
+    p.geom = pl.roi.dg;
+    p.tx0 = pl.roi.tx0;
+    p.ty0 = pl.roi.ty0;
+    p.rows = pl.rows;
+    p.pieces = pl.pieces;
+    p.runs = pl.runs;
+    p.gpr = pl.gpr;
+    p.n_groups = (uint32_t)n_groups;
+    p.group_frames = (uint32_t)group_frames;
+    p.group_starts = d_group_starts;
+    p.accumulate = accumulate;
+    p.sum16 = sum_type == DBDE_HIP_SUM_U16 ? 1u : 0u;
+    p.out_max = static_cast<uint8_t *>(d_max);
+    p.out_min = static_cast<uint8_t *>(d_min);
+    p.out_sum = d_sum;
+    p.out_sumsq = d_sumsq;
+    p.out_counts = d_counts;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_gproject(p, pl.stats, pix, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_project_groups(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                            const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                            int group_frames, const uint32_t *d_group_starts, int n_groups, int sum_type, int accumulate,
+                            uint8_t *d_max, uint8_t *d_min, void *d_sum, uint64_t *d_sumsq, uint32_t *d_counts,
+                            dbde_hip_frame_result *d_results) {
+    return project_groups_common(ctx, "project_groups", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0,
+                                 y0, rw, rh, group_frames, d_group_starts, n_groups, sum_type, accumulate, d_max, d_min,
+                                 d_sum, d_sumsq, d_counts, d_results);
+}
+
+int dbde16_hip_project_groups(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                              const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                              int group_frames, const uint32_t *d_group_starts, int n_groups, int sum_type, int accumulate,
+                              uint16_t *d_max, uint16_t *d_min, uint32_t *d_sum, uint64_t *d_sumsq, uint32_t *d_counts,
+                              dbde_hip_frame_result *d_results) {
+    return project_groups_common(ctx, "project_groups16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames,
+                                 x0, y0, rw, rh, group_frames, d_group_starts, n_groups, sum_type, accumulate, d_max,
+                                 d_min, d_sum, d_sumsq, d_counts, d_results);
 }
 
 // ---- region traces ----------------------------------------------------------------------------------------

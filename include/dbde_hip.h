@@ -171,6 +171,43 @@ int dbde_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_b
                      uint8_t *d_max, uint8_t *d_min, uint64_t *d_sum, uint64_t *d_sumsq,
                      uint64_t *d_count, dbde_hip_frame_result *d_results);
 
+/* Grouped temporal projection: dbde_hip_project's reduction done once per GROUP of frames -- every run
+ * of frames becomes one set of planes (temporal binning, block maxima, per-trial sums).
+ * Input, validation and results: the stream, stream_bytes, d_frame_offsets, the window and d_results are exactly
+ *   dbde_hip_project's (no per-frame origins, no byte read at or beyond stream_bytes; a rejected frame reports its
+ *   usual entry and adds nothing; the pixels reduced are the ones dbde_hip_decode_frames would write).
+ * Groups: exactly one of two forms.
+ *   uniform  group_frames = g, 1 <= g <= 65,536, d_group_starts == NULL: group k is frames [k*g, min((k+1)*g, n_frames));
+ *            n_groups must equal ceil(n_frames / g).  n_frames == 0 (n_groups == 0) does nothing.
+ *   ragged   group_frames == 0, d_group_starts a device U32 array of n_groups + 1 entries s[], n_groups >= 1: group k is
+ *            frames [b, e), b = min(s[k], n_frames), e = min(max(s[k+1], s[k]), n_frames).  The array is clamped, never
+ *            trusted: a decreasing entry gives an empty group, ranges may overlap, frames may belong to no group, and no
+ *            value can cause a read outside the n_frames offsets.  Needs n_frames <= 65,536 (the kernel's U32 bound on
+ *            the frames of one group).
+ * Outputs: each plane is [n_groups][rh][rw], row-major with pitch rw (64-bit indexing).  A NULL plane is neither
+ *   computed nor touched; at least one is required.  d_max / d_min hold U8 pixels at any address.  d_sum is U32 (4-byte
+ *   aligned), or with sum_type = DBDE_HIP_SUM_U16 a U16 plane (2-byte aligned), allowed only where no group can exceed
+ *   257 frames (257 * 255 = 65,535: uniform g <= 257, or the ragged form with n_frames <= 257) and accumulate == 0.
+ *   d_sumsq is U64, 8-byte aligned.  d_counts (required, U32 [n_groups], 4-byte aligned) receives the accepted frames
+ *   of each group.  An empty group, or one whose frames were all rejected, gets the empty projection: max 0, min 255,
+ *   sums 0, count 0.  Nothing outside the requested planes and d_counts is written.
+ * accumulate = 1 combines with what the planes and counts hold, by dbde_hip_project's rule applied per group (max of
+ *   maxima, min of minima, sums and counts added, modulo the planes' widths).
+ * Defining property: group k's planes equal what dbde_hip_project returns for frames [b_k, e_k) alone with
+ *   accumulate = 0, and d_counts[k] equals that call's *d_count.  Every value is an exact integer, independent of the
+ *   launch shape.
+ * Errors: DBDE_HIP_ERR_ARG, before anything is launched, for every broken rule above and for misaligned outputs.
+ * Asynchronous on the context's stream; workspace is the context's (the decode index's).  Timing hook: the index kernel
+ * in slot 1, the grouped projection kernel in slot 2. */
+enum { DBDE_HIP_SUM_U32 = 0, DBDE_HIP_SUM_U16 = 1 };
+int dbde_hip_project_groups(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                            const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                            int x0, int y0, int rw, int rh,
+                            int group_frames, const uint32_t *d_group_starts, int n_groups,
+                            int sum_type, int accumulate,
+                            uint8_t *d_max, uint8_t *d_min, void *d_sum, uint64_t *d_sumsq,
+                            uint32_t *d_counts, dbde_hip_frame_result *d_results);
+
 /* Builds the frame index of a concatenated frame sequence starting at d_stream (no video
  * header): hops 20 + 12 + 2T + 8*n64 from frame to frame (README.md:12-23) until max_frames
  * or the end of stream_bytes.  Writes offsets (device, max_frames) and returns the number of
@@ -332,6 +369,17 @@ int dbde16_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream
                        int x0, int y0, int rw, int rh, int accumulate,
                        uint16_t *d_max, uint16_t *d_min, uint64_t *d_sum, uint64_t *d_sumsq,
                        uint64_t *d_count, dbde_hip_frame_result *d_results);
+/* Grouped temporal projection of DBDE16 frames: dbde_hip_project_groups' contract with U16 pixels,
+ * validated as dbde16_hip_project validates.  d_max / d_min are U16 planes (2-byte aligned), d_sum is U32 only
+ * (65,536 * 65,535 < 2^32; sum_type must be DBDE_HIP_SUM_U32), d_sumsq U64.  The empty projection is max 0, min 65535,
+ * sums 0, count 0. */
+int dbde16_hip_project_groups(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                              const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                              int x0, int y0, int rw, int rh,
+                              int group_frames, const uint32_t *d_group_starts, int n_groups,
+                              int sum_type, int accumulate,
+                              uint16_t *d_max, uint16_t *d_min, uint32_t *d_sum, uint64_t *d_sumsq,
+                              uint32_t *d_counts, dbde_hip_frame_result *d_results);
 
 /* ---- multi-GPU: variable-length gather of the compressed stream to a root (RCCL over xGMI) ------------------- */
 /* Frames are independent, so the path shards by contiguous frame blocks (rank g of G owns frames
@@ -565,6 +613,43 @@ int dbde_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, in
  * sums (65,536 * 65,535 < 2^32), and workspace_bytes counts U16 max / min, U32 sum and U64 sumsq partials. */
 int dbde16_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats,
                             int n_cu, dbde_hip_project_plan_t *plan);
+
+/* What dbde_hip_project_groups runs (pure host arithmetic, like dbde_hip_project_plan): validates exactly what the call
+ * validates of its sizes, groups, sum_type, accumulate and output addresses (DBDE_HIP_ERR_ARG otherwise) and reports
+ * the tile window, the index geometry, the launch and the bytes of each plane.  has_group_starts: 1 for the ragged form
+ * (the call's d_group_starts != NULL).  The *_address arguments stand for the call's output pointers: 0 = NULL (the
+ * statistic is not computed), otherwise only the alignment counts.  n_cu: compute units of the device.
+ * The run rule: a workgroup takes one window tile row, one piece and a run of groups_per_run consecutive groups; runs
+ * are cut only to bring the launch to about 4 workgroups per CU and never to fewer than 32 frames (the ragged form
+ * counts n_frames / n_groups frames per group), so a large window has one run. */
+typedef struct dbde_hip_project_groups_plan_t {
+    int32_t tile_x, tile_y;           /* first tile column / row of the window */
+    int32_t tiles_x, tiles_y;         /* tiles across / down the window covers */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t threads;                 /* kernel: workgroup size (8 lanes per tile, DBDE16: 16) */
+    uint32_t pieces_x;                /* kernel: workgroups across a window tile row */
+    uint32_t runs;                    /* runs of consecutive groups, each walked by its own workgroups */
+    uint32_t groups_per_run;          /* groups of every run but the last (which may hold fewer) */
+    uint32_t max_group_frames;        /* the kernel's U32 bound on the frames of one group */
+    uint32_t stats;                   /* the statistics computed: max 1, min 2, sum 4, sumsq 8 */
+    uint64_t grid;                    /* kernel: pieces_x * tiles_y * runs workgroups */
+    uint64_t sum_bytes, max_bytes, min_bytes, sumsq_bytes;   /* bytes of each plane set (0 = not computed) */
+    uint64_t counts_bytes;            /* 4 * n_groups */
+    uint64_t workspace_bytes;         /* beyond the decode index's: none (the planes are written directly) */
+} dbde_hip_project_groups_plan_t;
+int dbde_hip_project_groups_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                                 int group_frames, int has_group_starts, int n_groups, int sum_type, int accumulate,
+                                 uint64_t max_address, uint64_t min_address, uint64_t sum_address,
+                                 uint64_t sumsq_address, uint64_t counts_address, int n_cu,
+                                 dbde_hip_project_groups_plan_t *plan);
+int dbde16_hip_project_groups_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                                   int group_frames, int has_group_starts, int n_groups, int sum_type, int accumulate,
+                                   uint64_t max_address, uint64_t min_address, uint64_t sum_address,
+                                   uint64_t sumsq_address, uint64_t counts_address, int n_cu,
+                                   dbde_hip_project_groups_plan_t *plan);
 
 /* ---- region traces: per frame and per labelled region, max / min / sum / sum of squares ---------- */
 /* A trace map is a label image (H x W int32, row-major, pitch W: 0 = no region, 1..n_labels = region id) classified
