@@ -888,9 +888,12 @@ int dbde16_hip_binned_plan(int W, int H, int n_frames, int x0, int y0, int rw, i
  *   sensor pixel's own correction, taken at the clamped origin.
  * Arithmetic: the subtraction and the multiplication are two IEEE binary32 operations, each rounded to nearest even
  *   (never p*G - D*G, never fused); v is then rounded once, to nearest even, to the output type.  F16 overflow goes to
- *   +-inf; F16 and BF16 subnormal results are produced, not flushed; the sign of a zero product is IEEE's.  F32
- *   subnormal intermediates follow the device's default denormal mode (not pinned here).  NaN / Inf in a map
- *   propagate; NaN payload bits are unspecified.
+ *   +-inf; F16 and BF16 subnormal results are produced, not flushed; the sign of a zero product is IEEE's (x - x is +0, the
+ *   product's sign is the XOR of its operands').  Binary32 subnormals are never flushed: a subnormal D or G is read at
+ *   its value, a subnormal difference or product is produced with IEEE gradual underflow (rounded to nearest even),
+ *   a product below half the smallest subnormal is +-0, and a subnormal v converts to the BF16 subnormal (or F16 zero)
+ *   nearest to it.  A product beyond the largest binary32 value is +-inf.  NaN / Inf in a map propagate; NaN payload
+ *   bits are unspecified.
  * Output: out_type is DBDE_HIP_OUT_F32, _F16 or _BF16; d_out is [n_frames][rh][rw] of that type, row-major, pitch rw,
  *   aligned to its element size only (not assumed 16-byte aligned).
  * Errors: DBDE_HIP_ERR_ARG as dbde_hip_decode_roi, and for an unknown out_type, a NULL d_out with n_frames > 0, or a

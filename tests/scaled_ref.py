@@ -12,6 +12,10 @@ non-zero |p - D| is at least the last bit of D (2^-23 D or more), and a uniform 
 1e-30: times 2^-8 the product stays far above the smallest normal binary32 (1.2e-38), and no F32 intermediate is
 subnormal.  F16 results overflow to inf (300 * 256 > 65504) and fall into the F16 subnormal range (below 6.1e-5).
 tests/test_scaled_ref.py checks all three on the maps themselves.
+
+The standard maps still avoid binary32 subnormals; that range, and the operands on which a rounding can go wrong
+(ties, double roundings, the overflow edges), belong to tests/scaled_witness.py: its exact integer reference is the
+definition, and tests/test_scaled_witness.py checks scaled_bits against it over the whole binary32 range.
 """
 import numpy as np
 
@@ -36,7 +40,8 @@ def bf16_bits(v):
 
 def value(p, dark, gain):
     """v as float32: (p - D) * G, the two operations in binary32."""
-    with np.errstate(invalid="ignore"):   # inf - inf, 0 * inf in maps that hold special values: NaN, as IEEE has it
+    # inf - inf, 0 * inf in maps that hold special values: NaN, as IEEE has it; products may overflow and underflow
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
         d = np.subtract(np.asarray(p).astype(np.float32), np.asarray(dark, np.float32), dtype=np.float32)
         return np.multiply(d, np.asarray(gain, np.float32), dtype=np.float32)
 
