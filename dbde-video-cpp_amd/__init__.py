@@ -63,6 +63,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_histogram", "dbde16_hip_histogram", "dbde_hip_histogram_plan", "dbde16_hip_histogram_plan",
     "dbde_hip_decode_binned", "dbde16_hip_decode_binned", "dbde_hip_binned_plan", "dbde16_hip_binned_plan",
     "dbde_hip_decode_scaled", "dbde16_hip_decode_scaled", "dbde_hip_scaled_plan", "dbde16_hip_scaled_plan",
+    "dbde_hip_decode_mask", "dbde16_hip_decode_mask", "dbde_hip_mask_plan", "dbde16_hip_mask_plan",
     "dbde_hip_crop_frames", "dbde16_hip_crop_frames", "dbde_hip_crop_plan", "dbde16_hip_crop_plan",
     "dbde_hip_encode_window", "dbde16_hip_encode_window", "dbde_hip_window_encode_plan", "dbde16_hip_window_encode_plan",
     "dbde_hip_writer_put_window",
@@ -230,6 +231,12 @@ def lib():
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_scaled_plan", "dbde16_hip_scaled_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, C.POINTER(ScaledPlan)]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_decode_mask", "dbde16_hip_decode_mask"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, i, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_mask_plan", "dbde16_hip_mask_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, C.POINTER(MaskPlan)]
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_crop_frames", "dbde16_hip_crop_frames"):
         getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, vp, sz, u64, vp, vp, vp, vp]
@@ -956,6 +963,88 @@ def scaled16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, dtype=OUT_F32):
     return _scaled_plan("dbde16_hip_scaled_plan", W, H, n_frames, x, y, rw, rh, dtype)
 
 
+MASK_INSIDE, MASK_OUTSIDE = 0, 1   # DBDE_HIP_MASK_* (include/dbde_hip.h)
+
+
+class MaskPlan(C.Structure):
+    """dbde_hip_mask_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("max_tiles_x", C.c_int32), ("max_tiles_y", C.c_int32), ("chunks_per_frame", C.c_uint32),
+                ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32), ("index_split", C.c_uint32),
+                ("threads", C.c_uint32), ("pieces_x", C.c_uint32), ("piece_words", C.c_uint32), ("lds_bytes", C.c_uint32),
+                ("words", C.c_uint32), ("pieces_x_fixed", C.c_uint32), ("piece_words_fixed", C.c_uint32),
+                ("reserved", C.c_uint32),
+                ("grid", C.c_uint64), ("grid_origins", C.c_uint64), ("mask_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+def _mask_plan(fn, W, H, n_frames, x, y, rw, rh):
+    """mask_plan / mask16_plan through the C function named fn."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    pl = MaskPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, x, y, rw, rh, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}) -> {rc}")
+    return pl.as_dict()
+
+
+def mask_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None):
+    """dbde_hip_mask_plan: the tile window, index geometry, launch, LDS, words per row and mask bytes of
+    Codec.decode_mask (host arithmetic only).  rw / rh default to the rest of the frame.  Raises ValueError where
+    dbde_hip_decode_mask would return DBDE_HIP_ERR_ARG for its sizes and window."""
+    return _mask_plan("dbde_hip_mask_plan", W, H, n_frames, x, y, rw, rh)
+
+
+def mask16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None):
+    """dbde16_hip_mask_plan: mask_plan for DBDE16 frames (Codec.decode_mask16)."""
+    return _mask_plan("dbde16_hip_mask_plan", W, H, n_frames, x, y, rw, rh)
+
+
+class Mask:
+    """Device tensors of a mask decode (Codec.decode_mask): bits (int64, (n, rh, words), words = ceil(rw / 64)) holds
+    bit (c & 63) of word (c >> 6) of row r for window pixel (r, c), the bits at and beyond rw being 0; counts (int32,
+    (n,)) the set bits per frame; boxes (int32, (n, 4)) x_min, y_min, x_max, y_max of the set bits in window
+    coordinates, inclusive, (rw, rh, -1, -1) for a frame with none.  An output that was not asked for is None."""
+
+    def __init__(self, bits=None, counts=None, boxes=None, rw=None):
+        self.bits, self.counts, self.boxes, self.rw = bits, counts, boxes, rw
+
+    @classmethod
+    def empty(cls, n, rh, rw, device, bits=True, counts=True, boxes=False):
+        """Zeroed outputs (a rejected frame's words then read 0)."""
+        words = -(-rw // 64)
+        return cls(torch.zeros((n, rh, words), dtype=torch.int64, device=device) if bits else None,
+                   torch.zeros((n,), dtype=torch.int32, device=device) if counts else None,
+                   torch.zeros((n, 4), dtype=torch.int32, device=device) if boxes else None, rw=rw)
+
+    def unpack(self):
+        """The mask as a bool tensor (n, rh, rw)."""
+        n, rh, words = self.bits.shape
+        sh = torch.arange(64, dtype=torch.int64, device=self.bits.device)
+        return ((self.bits.unsqueeze(-1) >> sh) & 1).to(torch.bool).reshape(n, rh, words * 64)[:, :, :self.rw]
+
+
+def band_from_background(bg, below, above=None):
+    """(lo, hi) maps in bg's dtype for Codec.decode_mask(..., outside=True): lo = clamp(bg - below), hi = clamp(bg +
+    above) (above defaults to below), so that the set bits are the pixels with p < bg - below or p > bg + above.  bg:
+    uint8 (DBDE) or int16 holding the U16 bits (DBDE16, as decode_frames16 returns its images)."""
+    above = below if above is None else above
+    if bg.dtype == torch.uint8:
+        v, top = bg.to(torch.int32), 255
+    elif bg.dtype == torch.int16:
+        v, top = bg.to(torch.int32) & 0xFFFF, 65535
+    else:
+        raise ValueError(f"bg must be uint8 or int16 (U16 bits), not {bg.dtype}")
+    lo, hi = (v - int(below)).clamp(0, top), (v + int(above)).clamp(0, top)
+    if bg.dtype == torch.uint8:
+        return lo.to(torch.uint8).contiguous(), hi.to(torch.uint8).contiguous()
+    as16 = lambda t: torch.where(t > 32767, t - 65536, t).to(torch.int16).contiguous()   # noqa: E731
+    return as16(lo), as16(hi)
+
+
 class CropPlan(C.Structure):
     """dbde_hip_crop_plan_t (include/dbde_hip.h)."""
     _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
@@ -1498,6 +1587,77 @@ class Codec:
         the output type is dtype=)."""
         return self._decode_scaled("dbde16_hip_decode_scaled", stream, stream_offset, stream_bytes, offsets, W, H, n, x,
                                    y, rw, rh, dtype, dark, gain, origins, out, results)
+
+    def _decode_mask(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, lo, hi, outside,
+                     origins, mask, counts, boxes, results):
+        """decode_mask / decode_mask16 through the C function named fn."""
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        map_dtype, top = (torch.uint8, 255) if pix == 1 else (torch.int16, 65535)
+
+        def term(v, name, default):
+            """(map pointer or None, scalar) of lo= / hi=."""
+            if v is None:
+                return None, default
+            if isinstance(v, torch.Tensor):
+                if v.dtype != map_dtype or tuple(v.shape) != (H, W) or not v.is_contiguous() or not v.is_cuda:
+                    raise DbdeError(f"{fn}: {name} must be a contiguous {map_dtype} device tensor of shape ({H}, {W}), "
+                                    f"not {v.dtype} {tuple(v.shape)}")
+                return v.data_ptr(), default
+            if int(v) != v or not 0 <= int(v) <= top:
+                raise DbdeError(f"{fn}: {name}={v!r} is not an integer in [0, {top}]")
+            return None, int(v)
+
+        lo_ptr, lo0 = term(lo, "lo", 0)
+        hi_ptr, hi0 = term(hi, "hi", top)
+        n0 = max(n, 0)
+        if mask is None:
+            mask = Mask.empty(n0, rh, rw, self.device, bits=True, counts=bool(counts), boxes=bool(boxes))
+        else:
+            mask.rw = rw
+            words = -(-rw // 64)
+            for name, t, dt, want in (("bits", mask.bits, torch.int64, n0 * rh * words), ("counts", mask.counts, torch.int32, n0),
+                                      ("boxes", mask.boxes, torch.int32, 4 * n0)):
+                if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() < want):
+                    raise DbdeError(f"{fn}: mask.{name} must be a contiguous {dt} device tensor of at least {want} "
+                                    f"elements, not {t.dtype} {tuple(t.shape)}")
+            if mask.bits is None and mask.counts is None and mask.boxes is None:
+                raise DbdeError(f"{fn}: the Mask has no output")
+        if results is None:
+            results = torch.empty((n0, 4), dtype=torch.int64, device=self.device)
+        if n == 0:   # nothing to do (empty tensors have no address to pass): the arguments are still checked
+            try:
+                _mask_plan(fn.replace("decode_mask", "mask_plan"), W, H, 0, x, y, rw, rh)
+            except ValueError as e:   # the same error as with frames to decode
+                raise DbdeError(f"{fn}: {e}") from None
+            return mask, results
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                 W, H, n, x, y, rw, rh, ptr(origins), MASK_OUTSIDE if outside else MASK_INSIDE,
+                                 lo_ptr, lo0, hi_ptr, hi0, ptr(mask.bits), ptr(mask.counts), ptr(mask.boxes),
+                                 results.data_ptr())
+        self._check(rc, fn)
+        return mask, results
+
+    def decode_mask(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x=0, y=0, rw=None, rh=None,
+                    lo=None, hi=None, outside=False, origins=None, mask=None, counts=True, boxes=False, results=None):
+        """Threshold mask of the rw x rh window at (x, y) of n frames (frame f at
+        stream.data_ptr()+stream_offset+offsets[f]): one bit per pixel, set where lo <= pixel <= hi (outside=True: where
+        pixel < lo or pixel > hi), straight from the stream.  lo / hi: None (0 / 255), an integer, or a contiguous uint8
+        device tensor (H, W) in FRAME coordinates; lo > hi is an empty band.  rw / rh default to the rest of the frame.
+        origins: optional int32 device tensor (n, 2) of per-frame (x, y), clamped into the frame as decode_roi clamps
+        them.  counts / boxes: also the set bits per frame / their bounding boxes.  mask: a Mask to write into; its
+        tensors are the outputs computed (counts / boxes are then ignored; bits may be None).
+        Returns (Mask, results (n, 4) int64) like decode_frames."""
+        return self._decode_mask("dbde_hip_decode_mask", 1, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y,
+                                 rw, rh, lo, hi, outside, origins, mask, counts, boxes, results)
+
+    def decode_mask16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, x=0, y=0, rw=None, rh=None,
+                      lo=None, hi=None, outside=False, origins=None, mask=None, counts=True, boxes=False, results=None):
+        """DBDE16 threshold mask: decode_mask's arguments and results over U16 pixels; lo / hi default to 0 / 65535,
+        maps are int16 tensors holding the U16 bits (as decode_frames16 returns its images)."""
+        return self._decode_mask("dbde16_hip_decode_mask", 2, stream, stream_offset, stream_bytes, offsets, W, H, n, x,
+                                 y, rw, rh, lo, hi, outside, origins, mask, counts, boxes, results)
 
     def _crop_frames(self, fn, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, out, out_offset,
                      capacity, origins, slot_stride, out_offsets, out_bytes, origins_used, results):

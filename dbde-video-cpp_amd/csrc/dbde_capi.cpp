@@ -20,6 +20,7 @@
 #include "dbde_gproject_kernels.h"
 #include "dbde_hist_kernels.h"
 #include "dbde_kernels.h"
+#include "dbde_mask_kernels.h"
 #include "dbde_project_kernels.h"
 #include "dbde_roi_kernels.h"
 #include "dbde_scaled_kernels.h"
@@ -2053,6 +2054,153 @@ int dbde16_hip_decode_scaled(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t 
                              const float *d_gain, float gain0, void *d_out, dbde_hip_frame_result *d_results) {
     return decode_scaled_common(ctx, "decode_scaled16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames,
                                 x0, y0, rw, rh, d_origins, out_type, d_dark, dark0, d_gain, gain0, d_out, d_results);
+}
+
+// ---- threshold mask decode ----------------------------------------------------------------------------------
+struct MaskPlan {
+    RoiPlan roi;                      // arguments, tile window and index geometry: the window decoder's (plan_roi)
+    uint32_t words, threads;
+    uint32_t piece_words, pieces;               // with per-frame origins: any x mod 8
+    uint32_t piece_words_fixed, pieces_fixed;   // at (x0, y0): one more word per piece when x0 is a multiple of 8
+    uint64_t grid, grid_origins, mask_bytes;
+};
+// Pieces are cut in window coordinates (whole mask words), so their number does not depend on the origin.
+static const char *plan_mask(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint32_t pix, MaskPlan &pl) {
+    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, kMaskWideThreadsOf(pix))) return why;
+    pl.words = ((uint32_t)rw + 63u) / 64u;
+    pl.threads = pl.words <= kMaskNarrowWords ? kMaskNarrowThreads : kMaskWideThreadsOf(pix);
+    // as few pieces as the workgroup's tiles allow, the words spread evenly over them
+    const uint32_t cap = kMaskPieceWordsOf(pl.threads), cap_fixed = x0 % 8 == 0 ? kMaskAlignedPieceWordsOf(pl.threads) : cap;
+    pl.pieces = (pl.words + cap - 1u) / cap;
+    pl.piece_words = (pl.words + pl.pieces - 1u) / pl.pieces;
+    pl.pieces_fixed = (pl.words + cap_fixed - 1u) / cap_fixed;
+    pl.piece_words_fixed = (pl.words + pl.pieces_fixed - 1u) / pl.pieces_fixed;
+    pl.grid = (uint64_t)n_frames * pl.roi.nty * pl.pieces_fixed;
+    pl.grid_origins = (uint64_t)n_frames * pl.roi.max_ty * pl.pieces;
+    if (pl.grid_origins >= (1ull << 31)) return "too many workgroups in one call";
+    pl.mask_bytes = (uint64_t)n_frames * (uint64_t)rh * pl.words * 8u;
+    return nullptr;
+}
+
+static int mask_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint32_t pix,
+                            dbde_hip_mask_plan_t *plan) {
+    MaskPlan pl;
+    if (!plan || plan_mask(W, H, n_frames, x0, y0, rw, rh, pix, pl)) return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->tile_x = (int32_t)pl.roi.tx0;
+    plan->tile_y = (int32_t)pl.roi.ty0;
+    plan->tiles_x = (int32_t)pl.roi.ntx;
+    plan->tiles_y = (int32_t)pl.roi.nty;
+    plan->max_tiles_x = (int32_t)pl.roi.max_tx;
+    plan->max_tiles_y = (int32_t)pl.roi.max_ty;
+    plan->chunks_per_frame = pl.roi.dg.cpf;
+    plan->chunk_tiles = pl.roi.dg.ct;
+    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
+    plan->index_split = pl.roi.split;
+    plan->threads = pl.threads;
+    plan->pieces_x = pl.pieces;
+    plan->piece_words = pl.piece_words;
+    plan->lds_bytes = kMaskLdsBytesOf(pl.threads, pix);
+    plan->words = pl.words;
+    plan->pieces_x_fixed = pl.pieces_fixed;
+    plan->piece_words_fixed = pl.piece_words_fixed;
+    plan->grid = pl.grid;
+    plan->grid_origins = pl.grid_origins;
+    plan->mask_bytes = pl.mask_bytes;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_mask_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_mask_plan_t *plan) {
+    return mask_plan_common(W, H, n_frames, x0, y0, rw, rh, 1u, plan);
+}
+
+int dbde16_hip_mask_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_mask_plan_t *plan) {
+    return mask_plan_common(W, H, n_frames, x0, y0, rw, rh, 2u, plan);
+}
+
+// Both mask decoders: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the counts' and boxes'
+// initialisation and the mask kernel in slot 2.
+static int decode_mask_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
+                              size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
+                              int y0, int rw, int rh, const int32_t *d_origins, int mode, const void *d_lo_map,
+                              uint32_t lo0, const void *d_hi_map, uint32_t hi0, uint64_t *d_mask, uint32_t *d_counts,
+                              int32_t *d_boxes, dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    MaskPlan pl;
+    if (const char *why = plan_mask(W, H, n_frames, x0, y0, rw, rh, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", name, why, W, H, n_frames,
+                    rw, rh, x0, y0);
+    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if (mode != DBDE_HIP_MASK_INSIDE && mode != DBDE_HIP_MASK_OUTSIDE)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: mode %d is neither INSIDE nor OUTSIDE", name, mode);
+    const uint32_t pix_max = pix == 1u ? 0xFFu : 0xFFFFu;
+    if (lo0 > pix_max || hi0 > pix_max)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: thresholds %u, %u above %u", name, lo0, hi0, pix_max);
+    if (!d_mask && !d_counts && !d_boxes) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: no output requested", name);
+    if (reinterpret_cast<uintptr_t>(d_mask) & 7u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the mask must be 8-byte aligned", name);
+    if ((reinterpret_cast<uintptr_t>(d_counts) | reinterpret_cast<uintptr_t>(d_boxes)) & 3u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the counts and boxes must be 4-byte aligned", name);
+    if ((reinterpret_cast<uintptr_t>(d_lo_map) | reinterpret_cast<uintptr_t>(d_hi_map)) & (pix - 1u))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the maps must be %u-byte aligned", name, pix);
+    if (n_frames == 0) return DBDE_HIP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
+    if (rc) return rc;
+
+    MaskParams p;
+    memset(&p, 0, sizeof p);
+    p.roi.stream = d_stream;
+    p.roi.frame_offsets = d_frame_offsets;
+    p.roi.stream_bytes = stream_bytes;
+    p.roi.chunk_off = ctx->chunk_off;
+    p.roi.frame_ok = ctx->frame_ok;
+    p.roi.origins = d_origins;
+    p.roi.W = W;
+    p.roi.H = H;
+    p.roi.x0 = x0;
+    p.roi.y0 = y0;
+    p.roi.rw = rw;
+    p.roi.rh = rh;
+    p.roi.w = pl.roi.g.w;
+    p.roi.h = pl.roi.g.h;
+    p.roi.T = pl.roi.g.T;
+    p.roi.geom = pl.roi.dg;
+    p.roi.rows = d_origins ? pl.roi.max_ty : pl.roi.nty;
+    p.roi.pieces = d_origins ? pl.pieces : pl.pieces_fixed;
+    p.lo_map = d_lo_map;
+    p.hi_map = d_hi_map;
+    p.lo0 = lo0;
+    p.hi0 = hi0;
+    p.outside = mode == DBDE_HIP_MASK_OUTSIDE ? kMaskOutside : kMaskInside;
+    p.words = pl.words;
+    p.piece_words = d_origins ? pl.piece_words : pl.piece_words_fixed;
+    p.mask = d_mask;
+    p.counts = d_counts;
+    p.boxes = d_boxes;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_mask_init(d_counts, d_boxes, (uint32_t)n_frames, rw, rh, ctx->stream));
+    HIP_TRY(ctx, launch_decode_mask(p, (uint32_t)n_frames, pl.threads, pix, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_decode_mask(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                         const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                         const int32_t *d_origins, int mode, const uint8_t *d_lo_map, uint32_t lo0,
+                         const uint8_t *d_hi_map, uint32_t hi0, uint64_t *d_mask, uint32_t *d_counts, int32_t *d_boxes,
+                         dbde_hip_frame_result *d_results) {
+    return decode_mask_common(ctx, "decode_mask", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0,
+                              rw, rh, d_origins, mode, d_lo_map, lo0, d_hi_map, hi0, d_mask, d_counts, d_boxes, d_results);
+}
+
+int dbde16_hip_decode_mask(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                           const int32_t *d_origins, int mode, const uint16_t *d_lo_map, uint32_t lo0,
+                           const uint16_t *d_hi_map, uint32_t hi0, uint64_t *d_mask, uint32_t *d_counts,
+                           int32_t *d_boxes, dbde_hip_frame_result *d_results) {
+    return decode_mask_common(ctx, "decode_mask16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0,
+                              rw, rh, d_origins, mode, d_lo_map, lo0, d_hi_map, hi0, d_mask, d_counts, d_boxes, d_results);
 }
 
 // ---- compressed-domain crop ---------------------------------------------------------------------------------

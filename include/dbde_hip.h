@@ -940,6 +940,79 @@ int dbde_hip_scaled_plan(int W, int H, int n_frames, int x0, int y0, int rw, int
 int dbde16_hip_scaled_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int out_type,
                            dbde_hip_scaled_plan_t *plan);
 
+/* ---- threshold mask decode: a bit per pixel straight from the stream ---------------------------- */
+/* Mask decode: for the rw x rh window of each of n_frames frames, one bit per pixel -- whether the decoded value lies
+ * inside (or outside) a band -- plus, optionally, the number of set bits per frame and their bounding box, straight from
+ * the compressed bytes (no integer image is written).
+ * Input and validation: the stream, the window, d_origins and d_results are exactly dbde_hip_decode_roi's -- the same
+ *   index kernel, the same clamping of per-frame origins into [0, W-rw] x [0, H-rh], the same result entries.  No byte
+ *   at or beyond stream_bytes is read.  n_frames == 0 does nothing.
+ * Predicate: for the pixel at FRAME coordinates (X, Y) with decoded value p -- exactly the byte dbde_hip_decode_frames
+ *   writes, wrapping minima included --
+ *     L = d_lo_map ? d_lo_map[Y*W + X] : lo0        Hh = d_hi_map ? d_hi_map[Y*W + X] : hi0
+ *   and the bit is set iff L <= p <= Hh (DBDE_HIP_MASK_INSIDE) or iff p < L or p > Hh (DBDE_HIP_MASK_OUTSIDE).  L > Hh
+ *   is legal: the band is empty.  The maps are [H][W] in the pixel type, pitch W, in frame coordinates: a moving window
+ *   (d_origins) keeps each sensor pixel's own thresholds, taken at the clamped origin.  Bright objects are lo = t,
+ *   hi = 255; dark objects lo = 0, hi = t; |p - bg| > delta is lo = clamp(bg - delta), hi = clamp(bg + delta), OUTSIDE.
+ * Mask: d_mask is U64 [n_frames][rh][words], words = ceil(rw / 64), 8-byte aligned; bit (c & 63) of word (c >> 6) of
+ *   row r is window pixel (r, c); the bits at and beyond rw of a row's last word are written as 0 (on a little-endian
+ *   host: numpy.packbits(bitorder="little") of rows padded to a multiple of 64).  Every word of an accepted frame is
+ *   written, by one plain store; nothing outside the n_frames*rh*words words is written.
+ * Optional outputs: d_counts is U32 [n_frames], the set bits of each frame; d_boxes is I32 [n_frames][4], x_min, y_min,
+ *   x_max, y_max of the set bits in window coordinates, inclusive, (rw, rh, -1, -1) for a frame with none.  Either may
+ *   be NULL, and so may d_mask; at least one of the three is required.
+ * A rejected frame leaves its mask words untouched; its count is 0 and its box the empty box; d_results has the verdict.
+ * Errors: DBDE_HIP_ERR_ARG as dbde_hip_decode_roi, and for an unknown mode, lo0 or hi0 above 255, no output requested,
+ *   or a misaligned d_mask (8), d_counts or d_boxes (4).
+ * Asynchronous on the context's stream; workspace (the decode index) is the context's, grown on demand.  Timing hook:
+ *   the index kernel in slot 1, the mask kernel (with the counts' and boxes' initialisation) in slot 2. */
+enum { DBDE_HIP_MASK_INSIDE = 0, DBDE_HIP_MASK_OUTSIDE = 1 };
+int dbde_hip_decode_mask(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                         const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                         int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                         int mode, const uint8_t *d_lo_map, uint32_t lo0,
+                         const uint8_t *d_hi_map, uint32_t hi0,
+                         uint64_t *d_mask, uint32_t *d_counts, int32_t *d_boxes,
+                         dbde_hip_frame_result *d_results);
+/* Mask decode of DBDE16 frames: dbde_hip_decode_mask's contract with U16 pixels, U16 maps (2-byte aligned) and
+ * thresholds up to 65535.  Validation is dbde16_hip_decode_frames' own; p is exactly the U16 value it writes. */
+int dbde16_hip_decode_mask(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                           int x0, int y0, int rw, int rh, const int32_t *d_origins,
+                           int mode, const uint16_t *d_lo_map, uint32_t lo0,
+                           const uint16_t *d_hi_map, uint32_t hi0,
+                           uint64_t *d_mask, uint32_t *d_counts, int32_t *d_boxes,
+                           dbde_hip_frame_result *d_results);
+/* What dbde_hip_decode_mask runs (pure host arithmetic, like dbde_hip_scaled_plan): validates exactly what
+ * dbde_hip_decode_mask validates of its sizes and window (DBDE_HIP_ERR_ARG otherwise) and reports dbde_hip_roi_plan's
+ * tile window and index geometry, the mask kernel's launch and LDS, and the mask's size.  A workgroup owns piece_words
+ * whole mask words of one window tile row (pieces are cut in window coordinates, so no word is shared) and decodes the
+ * at most 8 * piece_words + 1 <= threads tiles that overlap them at any x mod 8.  Without per-frame origins and with x0
+ * a multiple of 8, threads / 8 words are exactly threads tiles: the _fixed fields. */
+typedef struct dbde_hip_mask_plan_t {
+    int32_t tile_x, tile_y;           /* first tile column / row of the window at (x0, y0) */
+    int32_t tiles_x, tiles_y;         /* tiles across / down the window at (x0, y0) covers */
+    int32_t max_tiles_x, max_tiles_y; /* the most any per-frame origin needs */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t threads;                 /* mask kernel: workgroup size (64 for windows of at most 7 words, else 256; DBDE16: 128) */
+    uint32_t pieces_x;                /* with origins: workgroups per window tile row = ceil(words / (threads / 8 - 1)) */
+    uint32_t piece_words;             /* with origins: mask words of a row per workgroup = ceil(words / pieces_x) */
+    uint32_t lds_bytes;               /* LDS per workgroup (payload reused as the band; the scan; block bits; wave results) */
+    uint32_t words;                   /* U64 words per mask row = ceil(rw / 64) */
+    uint32_t pieces_x_fixed;          /* at (x0, y0): pieces_x, with threads / 8 words at most when x0 % 8 == 0 */
+    uint32_t piece_words_fixed;       /* at (x0, y0): ceil(words / pieces_x_fixed) */
+    uint32_t reserved;
+    uint64_t grid;                    /* workgroups without per-frame origins */
+    uint64_t grid_origins;            /* workgroups with per-frame origins */
+    uint64_t mask_bytes;              /* n_frames * rh * words * 8 */
+} dbde_hip_mask_plan_t;
+int dbde_hip_mask_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_mask_plan_t *plan);
+/* The same for dbde16_hip_decode_mask: its index and 128 threads (15 words) per workgroup for windows wider than 7 words. */
+int dbde16_hip_mask_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_mask_plan_t *plan);
+
 /* ---- compressed-domain crop: a window of each frame as a new stream ------------------------------ */
 /* Crops the rw x rh window at (x0, y0) out of each of n_frames DBDE frames and writes it as a complete DBDE frame of an
  * rw x rh image, without decoding the window: tiles whose valid pixels are unchanged are COPIED (depth byte, minimum,
