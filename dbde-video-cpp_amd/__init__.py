@@ -64,6 +64,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_decode_binned", "dbde16_hip_decode_binned", "dbde_hip_binned_plan", "dbde16_hip_binned_plan",
     "dbde_hip_decode_scaled", "dbde16_hip_decode_scaled", "dbde_hip_scaled_plan", "dbde16_hip_scaled_plan",
     "dbde_hip_decode_mask", "dbde16_hip_decode_mask", "dbde_hip_mask_plan", "dbde16_hip_mask_plan",
+    "dbde_hip_decode_patches", "dbde16_hip_decode_patches", "dbde_hip_patches_plan", "dbde16_hip_patches_plan",
     "dbde_hip_crop_frames", "dbde16_hip_crop_frames", "dbde_hip_crop_plan", "dbde16_hip_crop_plan",
     "dbde_hip_encode_window", "dbde16_hip_encode_window", "dbde_hip_window_encode_plan", "dbde16_hip_window_encode_plan",
     "dbde_hip_writer_put_window",
@@ -237,6 +238,12 @@ def lib():
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_mask_plan", "dbde16_hip_mask_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, C.POINTER(MaskPlan)]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_decode_patches", "dbde16_hip_decode_patches"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, vp, vp, i, C.c_uint32, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_patches_plan", "dbde16_hip_patches_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, C.POINTER(PatchPlan)]
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_crop_frames", "dbde16_hip_crop_frames"):
         getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, vp, sz, u64, vp, vp, vp, vp]
@@ -1045,6 +1052,70 @@ def band_from_background(bg, below, above=None):
     return as16(lo), as16(hi)
 
 
+PATCH_CLAMP, PATCH_FILL = 0, 1   # DBDE_HIP_PATCH_* (include/dbde_hip.h)
+
+
+def patch_edge_mode(edge):
+    """"clamp" / "fill" (or DBDE_HIP_PATCH_CLAMP / _FILL as an int) -> the C-ABI's edge mode."""
+    if isinstance(edge, str):
+        if edge not in ("clamp", "fill"):
+            raise ValueError(f"edge must be 'clamp' or 'fill', not {edge!r}")
+        return PATCH_CLAMP if edge == "clamp" else PATCH_FILL
+    return int(edge)
+
+
+class PatchPlan(C.Structure):
+    """dbde_hip_patches_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("max_tiles_x", C.c_int32), ("max_tiles_y", C.c_int32), ("rows_per_workgroup", C.c_uint32),
+                ("groups_per_patch", C.c_uint32), ("threads", C.c_uint32), ("chunks_per_frame", C.c_uint32),
+                ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32), ("index_split", C.c_uint32),
+                ("lds_bytes", C.c_uint32), ("grid", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def _patches_plan(fn, W, H, n_frames, pw, ph, n_patches, edge):
+    """patches_plan / patches16_plan through the C function named fn."""
+    pl = PatchPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, pw, ph, n_patches, patch_edge_mode(edge), C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {pw}, {ph}, {n_patches}, {edge}) -> {rc}")
+    return pl.as_dict()
+
+
+def patches_plan(W, H, n_frames, pw, ph, n_patches, edge="clamp"):
+    """dbde_hip_patches_plan: the tiles a patch can span, the tile rows per workgroup, the workgroups per patch, the
+    index geometry, the grid and the output bytes of Codec.decode_patches (host arithmetic only).  Raises ValueError
+    where dbde_hip_decode_patches would return DBDE_HIP_ERR_ARG for its sizes and edge mode."""
+    return _patches_plan("dbde_hip_patches_plan", W, H, n_frames, pw, ph, n_patches, edge)
+
+
+def patches16_plan(W, H, n_frames, pw, ph, n_patches, edge="clamp"):
+    """dbde16_hip_patches_plan: patches_plan for DBDE16 frames (Codec.decode_patches16)."""
+    return _patches_plan("dbde16_hip_patches_plan", W, H, n_frames, pw, ph, n_patches, edge)
+
+
+def origins_from_centres(centres, pw, ph):
+    """Patch origins from object centres: (n, K, 2) float or int (x, y) centres -> int32 origins of the same shape,
+    origin = floor(c + 0.5) - p // 2 per axis (p = pw for x, ph for y): the centre is rounded half up to a pixel, and
+    that pixel is column pw // 2, row ph // 2 of the patch -- the middle pixel of an odd size, the one right of / below
+    the middle of an even size.  Results outside int32 are clamped to it (decode_patches treats such origins as far
+    outside the frame).  centres: a torch tensor (the origins stay on its device) or anything numpy takes."""
+    if torch.is_tensor(centres):
+        c = centres
+        if c.dim() != 3 or c.shape[2] != 2:
+            raise ValueError("centres must have shape (n, K, 2)")
+        half = torch.tensor([pw // 2, ph // 2], dtype=torch.int64, device=c.device)
+        r = torch.floor(c.to(torch.float64) + 0.5).to(torch.int64) if c.is_floating_point() else c.to(torch.int64)
+        return (r - half).clamp(-2 ** 31, 2 ** 31 - 1).to(torch.int32).contiguous()
+    c = np.asarray(centres)
+    if c.ndim != 3 or c.shape[2] != 2:
+        raise ValueError("centres must have shape (n, K, 2)")
+    r = np.floor(c.astype(np.float64) + 0.5).astype(np.int64) if c.dtype.kind == "f" else c.astype(np.int64)
+    return np.ascontiguousarray(np.clip(r - np.array([pw // 2, ph // 2], np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32))
+
+
 class CropPlan(C.Structure):
     """dbde_hip_crop_plan_t (include/dbde_hip.h)."""
     _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
@@ -1658,6 +1729,51 @@ class Codec:
         maps are int16 tensors holding the U16 bits (as decode_frames16 returns its images)."""
         return self._decode_mask("dbde16_hip_decode_mask", 2, stream, stream_offset, stream_bytes, offsets, W, H, n, x,
                                  y, rw, rh, lo, hi, outside, origins, mask, counts, boxes, results)
+
+    def _decode_patches(self, fn, dtype, stream, stream_offset, stream_bytes, offsets, W, H, n, pw, ph, origins, counts,
+                        edge, fill, out, used, results):
+        """decode_patches / decode_patches16 through the C function named fn; dtype: the patches' tensor type."""
+        if (not torch.is_tensor(origins) or origins.dtype != torch.int32 or origins.dim() != 3 or origins.shape[0] != n
+                or origins.shape[2] != 2 or not origins.is_contiguous()):
+            raise ValueError("origins must be a contiguous int32 device tensor of shape (n, K, 2)")
+        K = int(origins.shape[1])
+        if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 1
+                                   or counts.numel() != n or not counts.is_contiguous()):
+            raise ValueError("counts must be a contiguous 1-D int32 tensor of n entries (the U32 bits)")
+        if used is not None and (not torch.is_tensor(used) or used.dtype != torch.int32 or not used.is_contiguous()
+                                 or used.numel() < 2 * n * K):
+            raise ValueError("used must be a contiguous int32 device tensor of at least n * K * 2 entries")
+        if out is None:
+            out = torch.empty((n, K, ph, pw), dtype=dtype, device=self.device)
+        elif out.dtype != dtype or not out.is_contiguous() or out.numel() < n * K * ph * pw:
+            raise ValueError(f"out must be a contiguous {dtype} device tensor of at least n * K * ph * pw entries")
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(), W, H, n,
+                                 pw, ph, K, origins.data_ptr(), ptr(counts), patch_edge_mode(edge), int(fill),
+                                 out.data_ptr(), ptr(used), ptr(results) if n > 0 else None)
+        self._check(rc, fn)
+        return out, results
+
+    def decode_patches(self, stream, stream_offset, stream_bytes, offsets, W, H, n, pw, ph, origins, counts=None,
+                       edge="clamp", fill=0, out=None, used=None, results=None):
+        """Decodes K patches of pw x ph per frame of n frames (frame f at stream.data_ptr()+stream_offset+offsets[f]) in
+        one call.  origins: int32 device tensor (n, K, 2) of (x, y) per frame and patch (origins_from_centres makes them
+        from object centres).  edge="clamp": origins are clamped into the frame, patch (f, k) is decode_roi's window at
+        origins[f, k]; edge="fill": the patch sits where its origin says and its pixels outside the frame are fill.
+        counts: optional int32 (n,), the live patches of each frame; patches k >= counts[f] stay untouched.  used:
+        optional int32 (n, K, 2) that receives the origins used (the clamped ones in clamp mode).
+        Returns (patches uint8 (n, K, ph, pw), results (n, 4) int64) like decode_frames."""
+        return self._decode_patches("dbde_hip_decode_patches", torch.uint8, stream, stream_offset, stream_bytes, offsets,
+                                    W, H, n, pw, ph, origins, counts, edge, fill, out, used, results)
+
+    def decode_patches16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, pw, ph, origins, counts=None,
+                         edge="clamp", fill=0, out=None, used=None, results=None):
+        """DBDE16 patches: decode_patches' arguments and results with int16 patches holding the U16 bits (as
+        decode_frames16 returns its images); fill up to 65535."""
+        return self._decode_patches("dbde16_hip_decode_patches", torch.int16, stream, stream_offset, stream_bytes,
+                                    offsets, W, H, n, pw, ph, origins, counts, edge, fill, out, used, results)
 
     def _crop_frames(self, fn, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, out, out_offset,
                      capacity, origins, slot_stride, out_offsets, out_bytes, origins_used, results):

@@ -21,6 +21,7 @@
 #include "dbde_hist_kernels.h"
 #include "dbde_kernels.h"
 #include "dbde_mask_kernels.h"
+#include "dbde_patch_kernels.h"
 #include "dbde_project_kernels.h"
 #include "dbde_roi_kernels.h"
 #include "dbde_scaled_kernels.h"
@@ -2201,6 +2202,147 @@ int dbde16_hip_decode_mask(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t st
                            int32_t *d_boxes, dbde_hip_frame_result *d_results) {
     return decode_mask_common(ctx, "decode_mask16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0,
                               rw, rh, d_origins, mode, d_lo_map, lo0, d_hi_map, hi0, d_mask, d_counts, d_boxes, d_results);
+}
+
+// ---- patch decode -------------------------------------------------------------------------------------------
+struct PatchPlan {
+    Geometry g;
+    DecGeom dg;                       // the index's chunks (roi_index_geometry)
+    uint32_t mtx, mty;                // the most tiles any origin makes a patch span
+    uint32_t G, groups, split;
+    uint64_t grid, out_bytes;
+};
+// nullptr when the arguments are good, else what is wrong with them.
+static const char *plan_patches(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode, uint32_t pix,
+                                PatchPlan &pl) {
+    if (n_frames < 0) return "n_frames < 0";
+    if (!geometry(W, H, pl.g)) return "bad frame size";
+    if (edge_mode != DBDE_HIP_PATCH_CLAMP && edge_mode != DBDE_HIP_PATCH_FILL) return "edge mode is neither CLAMP nor FILL";
+    if (n_patches < 1) return "n_patches < 1";
+    if (pw < 1 || ph < 1) return "patch size below 1";
+    if (((uint32_t)pw + 6u) / 8u + 1u > kPatchMaxTilesX) return "a patch could be more than 64 tiles across (pw > 505)";
+    const bool clamp = edge_mode == DBDE_HIP_PATCH_CLAMP;
+    if (clamp && (pw > W || ph > H)) return "CLAMP mode: patch size outside [1, W] x [1, H]";
+    pl.dg = roi_index_geometry(pl.g.w, pl.g.h);
+    if (pl.dg.cpf > kMaxChunksPerFrame) return "frame too large";
+    // x mod 8 reaches 7 in general, min(7, W - pw) over the origins clamping leaves (plan_roi)
+    const uint64_t mx = clamp && (uint32_t)(W - pw) < 7u ? (uint32_t)(W - pw) : 7u;
+    const uint64_t my = clamp && (uint32_t)(H - ph) < 7u ? (uint32_t)(H - ph) : 7u;
+    pl.mtx = (uint32_t)((mx + (uint64_t)pw + 7u) / 8u);
+    pl.mty = (uint32_t)((my + (uint64_t)ph + 7u) / 8u);
+    pl.G = kPatchThreads / pl.mtx < 1u ? 1u : kPatchThreads / pl.mtx;
+    pl.groups = (pl.mty + pl.G - 1u) / pl.G;
+    pl.split = index_split_for(n_frames, pl.dg.cpf);
+    // (n_frames, n_patches < 2^31 and groups < 2^29: np is bounded before it is multiplied by groups, so nothing wraps)
+    const uint64_t np = (uint64_t)n_frames * (uint64_t)n_patches;
+    if (np >= (1ull << 31)) return "too many workgroups in one call";
+    pl.grid = np * pl.groups;
+    if (pl.grid >= (1ull << 31)) return "too many workgroups in one call";
+    if ((uint64_t)n_frames * (pl.dg.cpf + 1u) >= (1ull << 31)) return "too many chunks in one call";
+    pl.out_bytes = np * (uint64_t)ph * (uint64_t)pw * pix;   // (ph <= 512 groups: np * ph < 2^40)
+    return nullptr;
+}
+
+static int patches_plan_common(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode, uint32_t pix,
+                               dbde_hip_patches_plan_t *plan) {
+    PatchPlan pl;
+    memset(&pl, 0, sizeof pl);
+    if (!plan || plan_patches(W, H, n_frames, pw, ph, n_patches, edge_mode, pix, pl)) return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->max_tiles_x = (int32_t)pl.mtx;
+    plan->max_tiles_y = (int32_t)pl.mty;
+    plan->rows_per_workgroup = pl.G;
+    plan->groups_per_patch = pl.groups;
+    plan->threads = kPatchThreads;
+    plan->chunks_per_frame = pl.dg.cpf;
+    plan->chunk_tiles = pl.dg.ct;
+    plan->chunk_pieces = pl.dg.ct == pl.g.w || pl.dg.pieces > 1u ? pl.dg.pieces : 0u;
+    plan->index_split = pl.split;
+    plan->lds_bytes = kPatchPayBytesOf(pix);
+    plan->grid = pl.grid;
+    plan->out_bytes = pl.out_bytes;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_patches_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
+                          dbde_hip_patches_plan_t *plan) {
+    return patches_plan_common(W, H, n_frames, pw, ph, n_patches, edge_mode, 1u, plan);
+}
+
+int dbde16_hip_patches_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
+                            dbde_hip_patches_plan_t *plan) {
+    return patches_plan_common(W, H, n_frames, pw, ph, n_patches, edge_mode, 2u, plan);
+}
+
+// Both patch decoders: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the patch kernel in
+// slot 2.
+static int decode_patches_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
+                                 size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int pw,
+                                 int ph, int n_patches, const int32_t *d_origins, const uint32_t *d_counts, int edge_mode,
+                                 uint32_t fill, void *d_out, int32_t *d_used, dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    PatchPlan pl;
+    memset(&pl, 0, sizeof pl);
+    if (const char *why = plan_patches(W, H, n_frames, pw, ph, n_patches, edge_mode, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d, %d patches of %dx%d, edge mode %d)", name, why, W, H,
+                    n_frames, n_patches, pw, ph, edge_mode);
+    if (!d_stream || !d_frame_offsets || !d_origins || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    const uint32_t pix_max = pix == 1u ? 0xFFu : 0xFFFFu;
+    if (fill > pix_max) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: fill %u above %u", name, fill, pix_max);
+    if (reinterpret_cast<uintptr_t>(d_out) & (pix - 1u))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the output must be %u-byte aligned", name, pix);
+    if ((reinterpret_cast<uintptr_t>(d_origins) | reinterpret_cast<uintptr_t>(d_counts) | reinterpret_cast<uintptr_t>(d_used)) & 3u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: origins, counts and used origins must be 4-byte aligned", name);
+    if (n_frames == 0) return DBDE_HIP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.dg, pix, pl.split);
+    if (rc) return rc;
+
+    PatchParams p;
+    memset(&p, 0, sizeof p);
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.origins = d_origins;
+    p.counts = d_counts;
+    p.out = static_cast<uint8_t *>(d_out);
+    p.used = d_used;
+    p.W = W;
+    p.H = H;
+    p.pw = pw;
+    p.ph = ph;
+    p.n_patches = (uint32_t)n_patches;
+    p.w = pl.g.w;
+    p.h = pl.g.h;
+    p.T = pl.g.T;
+    p.geom = pl.dg;
+    p.mtx = pl.mtx;
+    p.G = pl.G;
+    p.groups = pl.groups;
+    p.mode = edge_mode == DBDE_HIP_PATCH_FILL ? kPatchFill : kPatchClamp;
+    p.fill = fill;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_decode_patches(p, (uint32_t)n_frames, pix, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_decode_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                            const uint64_t *d_frame_offsets, int W, int H, int n_frames, int pw, int ph, int n_patches,
+                            const int32_t *d_origins, const uint32_t *d_counts, int edge_mode, uint32_t fill,
+                            uint8_t *d_out, int32_t *d_used, dbde_hip_frame_result *d_results) {
+    return decode_patches_common(ctx, "decode_patches", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, pw,
+                                 ph, n_patches, d_origins, d_counts, edge_mode, fill, d_out, d_used, d_results);
+}
+
+int dbde16_hip_decode_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                              const uint64_t *d_frame_offsets, int W, int H, int n_frames, int pw, int ph, int n_patches,
+                              const int32_t *d_origins, const uint32_t *d_counts, int edge_mode, uint32_t fill,
+                              uint16_t *d_out, int32_t *d_used, dbde_hip_frame_result *d_results) {
+    return decode_patches_common(ctx, "decode_patches16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, pw,
+                                 ph, n_patches, d_origins, d_counts, edge_mode, fill, d_out, d_used, d_results);
 }
 
 // ---- compressed-domain crop ---------------------------------------------------------------------------------

@@ -1013,6 +1013,68 @@ int dbde_hip_mask_plan(int W, int H, int n_frames, int x0, int y0, int rw, int r
 /* The same for dbde16_hip_decode_mask: its index and 128 threads (15 words) per workgroup for windows wider than 7 words. */
 int dbde16_hip_mask_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_mask_plan_t *plan);
 
+/* ---- patch decode: many small windows per frame in one call -------------------------------------- */
+/* Patch decode: n_patches windows of one size pw x ph per frame, each with its own origin per frame (one cut-out per
+ * tracked object), decoded straight from the compressed stream by ONE index pass and one kernel.  Frame f starts at
+ * d_stream + d_frame_offsets[f] (any byte alignment); patch (f, k) goes to d_out + (f*n_patches + k)*ph*pw pixels,
+ * row-major, pitch pw; d_out may have any alignment of the pixel size.  Patches may overlap or coincide.
+ *   d_origins: device int32 [n_frames][n_patches][2] (x, y), required.
+ *   edge_mode: DBDE_HIP_PATCH_CLAMP -- the origin is clamped into [0, W-pw] x [0, H-ph], and patch (f, k) equals, byte
+ *              for byte, what dbde_hip_decode_roi writes for frame f with that origin; requires pw <= W and ph <= H.
+ *              DBDE_HIP_PATCH_FILL -- the patch sits exactly where the origin says: its pixels inside the frame equal
+ *              the full decode, its pixels outside the frame are `fill` (only the low 8 bits may be set; DBDE16: 16),
+ *              a patch wholly outside the frame is all fill.  Any int32 origin is legal, INT32_MIN and INT32_MAX
+ *              included (nothing overflows: x is first clamped into [-pw, W], y into [-ph, H], which gives the same
+ *              patch); pw > W or ph > H is allowed.
+ *   d_counts:  optional device uint32 [n_frames]; min(d_counts[f], n_patches) is the number of live patches of frame f,
+ *              NULL means all of them.  Patches k >= count and their d_used entries stay untouched.
+ *   d_used:    optional device int32 [n_frames][n_patches][2]: the origin actually used -- the clamped one in CLAMP
+ *              mode, the given one in FILL mode.
+ *   d_results: as in dbde_hip_decode_frames (header fields; consumed = the whole frame's length), may be NULL.
+ * Validation is dbde_hip_decode_frames' own (the same index kernel on dbde_hip_roi_plan's geometry): a rejected frame
+ * reports the same result entry and leaves all its patches and d_used entries untouched.  No byte at or beyond
+ * stream_bytes is read; nothing outside the n_frames*n_patches*ph*pw pixels (and d_used) is written.  n_frames == 0
+ * does nothing.  DBDE_HIP_ERR_ARG: n_patches < 1; pw or ph < 1; a patch that could be more than 64 tiles across,
+ * (pw + 6)/8 + 1 > 64, so pw <= 505 (ph has no limit); in CLAMP mode pw > W or ph > H; a frame too large for the index
+ * (more than 32768 chunks); n_frames * n_patches * groups_per_patch >= 2^31; a null stream, offsets, origins or output;
+ * an unknown edge mode; fill above the pixel type.  Asynchronous on the context's stream; timing hook: the index kernel
+ * in slot 1, the patch kernel in slot 2. */
+enum { DBDE_HIP_PATCH_CLAMP = 0, DBDE_HIP_PATCH_FILL = 1 };
+int dbde_hip_decode_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                            const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                            int pw, int ph, int n_patches, const int32_t *d_origins, const uint32_t *d_counts,
+                            int edge_mode, uint32_t fill, uint8_t *d_out, int32_t *d_used,
+                            dbde_hip_frame_result *d_results);
+/* Patch decode of DBDE16 frames: dbde_hip_decode_patches' contract with U16 pixels (d_out 2-byte aligned, fill up to
+ * 65535).  Validation is dbde16_hip_decode_frames' own; CLAMP-mode patches equal dbde16_hip_decode_roi's windows. */
+int dbde16_hip_decode_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                              const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                              int pw, int ph, int n_patches, const int32_t *d_origins, const uint32_t *d_counts,
+                              int edge_mode, uint32_t fill, uint16_t *d_out, int32_t *d_used,
+                              dbde_hip_frame_result *d_results);
+/* What dbde_hip_decode_patches runs (pure host arithmetic, like dbde_hip_roi_plan): refuses exactly the arguments the
+ * call refuses, pointers and fill aside (DBDE_HIP_ERR_ARG), and reports the launch.  A 64-lane workgroup takes
+ * rows_per_workgroup = max(1, 64 / max_tiles_x) tile rows of one patch, one tile per lane. */
+typedef struct dbde_hip_patches_plan_t {
+    int32_t max_tiles_x, max_tiles_y; /* the most tiles any origin makes a patch span: (pw + 6)/8 + 1 across, (ph + 6)/8 + 1
+                                         down; in CLAMP mode (min(7, W - pw) + pw + 7)/8, as dbde_hip_roi_plan */
+    uint32_t rows_per_workgroup;      /* tile rows of one patch per workgroup */
+    uint32_t groups_per_patch;        /* workgroups per patch = ceil(max_tiles_y / rows_per_workgroup) */
+    uint32_t threads;                 /* workgroup size: 64 */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t lds_bytes;               /* LDS per workgroup (the rows' payload ranges, reused as the band) */
+    uint64_t grid;                    /* workgroups: n_frames * n_patches * groups_per_patch */
+    uint64_t out_bytes;               /* n_frames * n_patches * ph * pw * pixel size */
+} dbde_hip_patches_plan_t;
+int dbde_hip_patches_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
+                          dbde_hip_patches_plan_t *plan);
+/* The same for dbde16_hip_decode_patches: its index, LDS and output size. */
+int dbde16_hip_patches_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
+                            dbde_hip_patches_plan_t *plan);
+
 /* ---- compressed-domain crop: a window of each frame as a new stream ------------------------------ */
 /* Crops the rw x rh window at (x0, y0) out of each of n_frames DBDE frames and writes it as a complete DBDE frame of an
  * rw x rh image, without decoding the window: tiles whose valid pixels are unchanged are COPIED (depth byte, minimum,
