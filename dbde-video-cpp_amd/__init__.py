@@ -70,6 +70,8 @@ C_ABI_SYMBOLS = [
     "dbde_hip_writer_put_window",
     "dbde_hip_project_groups", "dbde16_hip_project_groups", "dbde_hip_project_groups_plan",
     "dbde16_hip_project_groups_plan",
+    "dbde_hip_project_weighted", "dbde16_hip_project_weighted", "dbde_hip_project_weighted_plan",
+    "dbde16_hip_project_weighted_plan",
 ]
 
 
@@ -198,6 +200,12 @@ def lib():
     for fn in ("dbde_hip_project_groups_plan", "dbde16_hip_project_groups_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, i, i, i, i, u64, u64, u64, u64, u64, i,
                                    C.POINTER(GroupProjectPlan)]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_project_weighted", "dbde16_hip_project_weighted"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, i, sz, i, i, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_project_weighted_plan", "dbde16_hip_project_weighted_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, u64, i, u64, u64, u64, i, C.POINTER(WeightedProjectPlan)]
         getattr(L, fn).restype = i
     L.dbde_hip_trace_map_summary.argtypes = [vp, i, i, i, C.POINTER(TraceMapInfo), vp]
     L.dbde_hip_trace_map_summary.restype = i
@@ -718,6 +726,91 @@ class GroupProjection:
         n = self._n()
         m = self.sums().to(torch.float64) / n
         return (self.sumsq.to(torch.float64) / n - m * m).clamp_(min=0.0).sqrt_()
+
+
+WPROJ_MAX_REGRESSORS = 8
+WPROJ_ONE_SEGMENT = 1
+REJECTED_CONSUMED = 20       # `consumed` of a frame that failed validation (results[:, 3]); an accepted frame has more
+
+
+def accepted_frames(results):
+    """bool (n,): the frames of a results tensor (n, 4) that passed validation.  The verdict is read from `consumed`: a
+    rejected frame reports 20, an accepted one its whole size; header.u64s is whatever the stream's header holds."""
+    return results[:, 3] != REJECTED_CONSUMED
+
+
+class WeightedProjectPlan(C.Structure):
+    """dbde_hip_project_weighted_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32),
+                ("index_split", C.c_uint32), ("threads", C.c_uint32), ("pieces_x", C.c_uint32),
+                ("segments", C.c_uint32), ("frames_per_segment", C.c_uint32), ("max_frames_per_segment", C.c_uint32),
+                ("regressors", C.c_uint32), ("grid", C.c_uint64), ("combine_grid", C.c_uint64),
+                ("workspace_bytes", C.c_uint64), ("lds_bytes", C.c_uint32), ("reserved_", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved_"}
+
+
+def _wproject_plan(fn, W, H, n_frames, x, y, rw, rh, regressors, n_cu, one_segment, weight_stride, addresses):
+    """wproject_plan / wproject16_plan through the C function named fn."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    addr = {"weights": 4096, "out": 4096, "count": 4096}
+    addr.update(addresses or {})
+    flags = one_segment if isinstance(one_segment, int) and not isinstance(one_segment, bool) else (
+        WPROJ_ONE_SEGMENT if one_segment else 0)
+    stride = max(n_frames, 0) if weight_stride is None else weight_stride
+    pl = WeightedProjectPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, x, y, rw, rh, regressors, stride, flags, addr["weights"], addr["out"],
+                            addr["count"], n_cu, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, R={regressors}, stride={stride}, "
+                         f"flags={flags}) -> {rc}")
+    return pl.as_dict()
+
+
+def wproject_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, regressors=1, n_cu=256, one_segment=False,
+                  weight_stride=None, addresses=None):
+    """dbde_hip_project_weighted_plan: the tile window, index geometry, launch, segments and workspace of a weighted
+    projection (host arithmetic only).  rw / rh default to the rest of the frame, weight_stride to n_frames.
+    one_segment: True / False (or an int: the raw flags).  addresses: optional {"weights" | "out" | "count": address}
+    standing for the call's pointers (0 = NULL; aligned by default).  Raises ValueError where
+    dbde_hip_project_weighted would return DBDE_HIP_ERR_ARG."""
+    return _wproject_plan("dbde_hip_project_weighted_plan", W, H, n_frames, x, y, rw, rh, regressors, n_cu, one_segment,
+                          weight_stride, addresses)
+
+
+def wproject16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, regressors=1, n_cu=256, one_segment=False,
+                    weight_stride=None, addresses=None):
+    """dbde16_hip_project_weighted_plan: wproject_plan for DBDE16 streams (Codec.project_weighted16)."""
+    return _wproject_plan("dbde16_hip_project_weighted_plan", W, H, n_frames, x, y, rw, rh, regressors, n_cu,
+                          one_segment, weight_stride, addresses)
+
+
+class WeightedProjection:
+    """Device tensors of a weighted projection (Codec.project_weighted): out float32 (R, rh, rw), plane r holding the
+    sum over the accepted frames of weights[r][f] * pixel; count int64 (1,), the frames that contributed."""
+
+    def __init__(self, out=None, count=None):
+        self.out, self.count = out, count
+
+    @classmethod
+    def empty(cls, R, rh, rw, device):
+        """Uninitialised planes and a zero count."""
+        return cls(torch.empty((R, rh, rw), dtype=torch.float32, device=device),
+                   torch.zeros(1, dtype=torch.int64, device=device))
+
+    @staticmethod
+    def weight_sums(weights, results):
+        """Sum of the accepted frames' weights per regressor: float64 (R,), on the weights' device.  weights: (R, >= n)
+        or (>= n,); results: the (n, 4) int64 tensor the call returned (accepted_frames reads the verdicts).  A torch
+        helper, not a kernel: it is what turns plane r into a covariance with `Projection.sum` (regressors.pearson)."""
+        w = weights if weights.dim() == 2 else weights.view(1, -1)
+        n = results.shape[0]
+        ok = accepted_frames(results).to(w.device)
+        w64 = w[:, :n].to(torch.float64)
+        return torch.where(ok.view(1, -1), w64, torch.zeros_like(w64)).sum(1)
 
 
 class TraceMapInfo(C.Structure):
@@ -1466,6 +1559,61 @@ class Codec:
         its statistics are the ones computed.  Returns (Projection, results (n, 4) int64) like decode_frames."""
         return self._project("dbde_hip_project", 1, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh,
                              stats, out, accumulate, results)
+
+    def _project_weighted(self, fn, stream, stream_offset, stream_bytes, offsets, W, H, n, weights, x, y, rw, rh, out,
+                          accumulate, one_segment, results):
+        """project_weighted / project_weighted16 through the C function named fn."""
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        if weights.dim() == 1:
+            weights = weights.view(1, -1)
+        if weights.dim() != 2 or weights.dtype != torch.float32 or not weights.is_cuda:
+            raise ValueError("weights must be a float32 device tensor (R, >= n) or (>= n,)")
+        R = weights.shape[0]
+        if R < 1 or weights.shape[1] < n or (weights.shape[1] > 1 and weights.stride(1) != 1):
+            raise ValueError("weights need at least one row, n columns and unit stride along the frames")
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out= (the projection to continue)")
+            out = WeightedProjection.empty(R, rh, rw, self.device)
+        if tuple(out.out.shape) != (R, rh, rw) or out.out.dtype != torch.float32 or not out.out.is_contiguous():
+            raise ValueError(f"out.out must be a contiguous float32 tensor ({R}, {rh}, {rw})")
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        flags = WPROJ_ONE_SEGMENT if one_segment else 0
+        for r0 in range(0, R, WPROJ_MAX_REGRESSORS):   # more than 8 rows: successive calls (the index pass repeats)
+            rows = weights[r0: r0 + WPROJ_MAX_REGRESSORS]
+            stride = rows.stride(0) if rows.shape[0] > 1 else max(rows.shape[1], n)
+            count = out.count
+            if r0 > 0:   # the frames are counted once: the later calls count into a spare that the output keeps alive
+                if getattr(out, "_spare_count", None) is None:
+                    out._spare_count = torch.zeros_like(out.count)
+                count = out._spare_count
+            rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                     W, H, n, x, y, rw, rh, rows.data_ptr(), rows.shape[0], stride,
+                                     1 if accumulate else 0, flags, out.out[r0: r0 + rows.shape[0]].data_ptr(),
+                                     count.data_ptr(), results.data_ptr() if n > 0 else None)
+            self._check(rc, fn)
+        return out, results
+
+    def project_weighted(self, stream, stream_offset, stream_bytes, offsets, W, H, n, weights, x=0, y=0, rw=None,
+                         rh=None, out=None, accumulate=False, one_segment=False, results=None):
+        """Weighted temporal projection of the rw x rh window at (x, y) over n frames: plane r is the sum over the
+        accepted frames f of weights[r][f] * pixel, a chain of F32 fused multiply-adds in frame order (the defined value:
+        include/dbde_hip.h).  weights: float32 device tensor (R, >= n) with unit stride along the frames and any row
+        stride, so a column slice weights[:, a:b] goes in without a copy; 1-D means R = 1.  Only columns [0, n) are read.
+        More than 8 rows are served by successive calls of at most 8 rows into slices of one output; the index pass then
+        repeats once per call.  out: a WeightedProjection to write into (accumulate=True adds to it; unlike the integer
+        projections, a run split into accumulating calls may differ in the last bits).  one_segment=True gives the pure
+        frame-order chain whatever the device.  Returns (WeightedProjection, results (n, 4) int64)."""
+        return self._project_weighted("dbde_hip_project_weighted", stream, stream_offset, stream_bytes, offsets, W, H, n,
+                                      weights, x, y, rw, rh, out, accumulate, one_segment, results)
+
+    def project_weighted16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, weights, x=0, y=0, rw=None,
+                           rh=None, out=None, accumulate=False, one_segment=False, results=None):
+        """project_weighted for DBDE16 streams (U16 pixels; every one is exact in float32)."""
+        return self._project_weighted("dbde16_hip_project_weighted", stream, stream_offset, stream_bytes, offsets, W, H,
+                                      n, weights, x, y, rw, rh, out, accumulate, one_segment, results)
 
     def _project_groups(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, group_frames,
                         group_starts, stats, sum_dtype, accumulate, out, results):

@@ -381,6 +381,53 @@ int dbde16_hip_project_groups(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t
                               uint16_t *d_max, uint16_t *d_min, uint32_t *d_sum, uint64_t *d_sumsq,
                               uint32_t *d_counts, dbde_hip_frame_result *d_results);
 
+/* Weighted temporal projection: R = n_regressors F32 planes of the rw x rh window,
+ *   out[r][y][x] = sum over the accepted frames f of w[r][f] * p_f[y][x],   r = 0 .. R - 1,
+ * reduced straight from the compressed bytes (no image is written).  One primitive for Fourier components at a
+ * stimulus frequency, per-pixel trends, exponentially weighted backgrounds, GLM regressor maps and correlation maps.
+ * Inputs and outputs:
+ *   The stream, the window and its argument rules, the validation, d_results, the stream_bytes rule and the timing
+ *   slots (index 1, projection kernels 2) are dbde_hip_project's; there are no per-frame origins.
+ *   The weight of frame f for regressor r is d_weights[r * weight_stride + f]: a 4-byte aligned device array of F32,
+ *   weight_stride >= n_frames (in elements).  Only the entries [r][0 .. n_frames) are read.  Weights are not inspected:
+ *   infinities and NaNs propagate by IEEE rules.  1 <= n_regressors <= DBDE_HIP_WPROJ_MAX_REGRESSORS.
+ *   d_out is [n_regressors][rh][rw] F32, row-major, 4-byte aligned, indexed in 64 bits.  d_count (one U64, 8-byte
+ *   aligned, required) receives the number of frames that contributed, as in dbde_hip_project.
+ * The defined value (checked bit for bit).  The frames are cut into S segments of fps frames (both reported by the
+ *   plan; the last segment may hold fewer).  Partial P_s is the chain acc = fmaf(w[r][f], (float)p_f, acc) over the
+ *   accepted frames f of segment s in ascending f, started at +0.0f: one fused multiply-add each, a single rounding to
+ *   nearest even, denormal operands and results kept.  A rejected frame executes no multiply-add: its weight is never
+ *   used, so a NaN weight at a rejected frame leaves the output finite.  The result is
+ *       ((prior + P_0) + P_1) + ... + P_{S-1}
+ *   with F32 round-to-nearest-even additions in ascending s.  prior is what d_out holds when accumulate = 1; when
+ *   accumulate = 0 it is absent and the chain starts at P_0.
+ *   accumulate = 0 with no accepted frame (n_frames == 0 included) writes +0.0 planes and count 0.  accumulate = 1
+ *   with n_frames == 0 changes nothing.  Unlike the integer projections, splitting a run of frames into consecutive
+ *   accumulating calls may change the last bits of the result: the additions round.
+ * flags: DBDE_HIP_WPROJ_ONE_SEGMENT forces S = 1; the result is then the pure frame-order chain, independent of the
+ *   device's compute unit count and of the plan.  Without it S is chosen by dbde_hip_project's rule for the same
+ *   window, n_frames and compute units (65,536 frames per segment at most), so the two plans agree.
+ * Errors: DBDE_HIP_ERR_ARG for everything dbde_hip_project rejects of its sizes, window and pointers, n_regressors
+ *   outside 1..8, NULL d_weights / d_out / d_count, a misaligned d_weights / d_out / d_count, weight_stride < n_frames
+ *   and unknown flag bits.
+ * Asynchronous on the context's stream; workspace as dbde_hip_project, with the F32 partials the plan reports. */
+enum { DBDE_HIP_WPROJ_MAX_REGRESSORS = 8 };
+enum { DBDE_HIP_WPROJ_ONE_SEGMENT = 1 };   /* flags */
+int dbde_hip_project_weighted(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                              const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                              int x0, int y0, int rw, int rh,
+                              const float *d_weights, int n_regressors, size_t weight_stride,
+                              int accumulate, int flags,
+                              float *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results);
+/* The same for DBDE16 frames: dbde_hip_project_weighted's contract with U16 pixels, validated as dbde16_hip_project
+ * validates.  (float)p_f is exact for every U16 pixel. */
+int dbde16_hip_project_weighted(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                                const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                                int x0, int y0, int rw, int rh,
+                                const float *d_weights, int n_regressors, size_t weight_stride,
+                                int accumulate, int flags,
+                                float *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results);
+
 /* ---- multi-GPU: variable-length gather of the compressed stream to a root (RCCL over xGMI) ------------------- */
 /* Frames are independent, so the path shards by contiguous frame blocks (rank g of G owns frames
  * [g*N/G, (g+1)*N/G)): every rank encodes its block with dbde_hip_encode_frames (slot_stride 0) and its output is
@@ -650,6 +697,40 @@ int dbde16_hip_project_groups_plan(int W, int H, int n_frames, int x0, int y0, i
                                    uint64_t max_address, uint64_t min_address, uint64_t sum_address,
                                    uint64_t sumsq_address, uint64_t counts_address, int n_cu,
                                    dbde_hip_project_groups_plan_t *plan);
+
+/* What dbde_hip_project_weighted runs (pure host arithmetic, like dbde_hip_project_plan): validates exactly what the
+ * call validates of its sizes, window, n_regressors, weight_stride, flags and addresses (DBDE_HIP_ERR_ARG otherwise)
+ * and reports the tile window, the index geometry, the launch and its workspace.  The fields are
+ * dbde_hip_project_plan_t's, with regressors in place of a statistics set; segments and frames_per_segment are S and
+ * fps of the defined value.  weights_address, out_address and count_address stand for the call's pointers (0 = NULL,
+ * rejected); n_cu: compute units of the device (the call uses its context's). */
+typedef struct dbde_hip_project_weighted_plan_t {
+    int32_t tile_x, tile_y;           /* first tile column / row of the window */
+    int32_t tiles_x, tiles_y;         /* tiles across / down the window covers */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t threads;                 /* projection kernel: workgroup size */
+    uint32_t pieces_x;                /* projection kernel: workgroups across a window tile row */
+    uint32_t segments;                /* S: frame segments, each folded by its own workgroups (1 with ONE_SEGMENT) */
+    uint32_t frames_per_segment;      /* fps: frames of every segment but the last (which may hold fewer) */
+    uint32_t max_frames_per_segment;  /* dbde_hip_project's bound, kept so that the two plans agree */
+    uint32_t regressors;              /* R */
+    uint64_t grid;                    /* projection kernel: pieces_x * tiles_y * segments workgroups */
+    uint64_t combine_grid;            /* combine kernel: workgroups (0 = one segment, no combine) */
+    uint64_t workspace_bytes;         /* F32 partials: 4 * S * R * rw * rh rounded up to 16 (0 for one segment) */
+    uint32_t lds_bytes;               /* projection kernel: LDS per workgroup */
+    uint32_t reserved_;
+} dbde_hip_project_weighted_plan_t;
+int dbde_hip_project_weighted_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                                   int n_regressors, uint64_t weight_stride, int flags,
+                                   uint64_t weights_address, uint64_t out_address, uint64_t count_address,
+                                   int n_cu, dbde_hip_project_weighted_plan_t *plan);
+int dbde16_hip_project_weighted_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                                     int n_regressors, uint64_t weight_stride, int flags,
+                                     uint64_t weights_address, uint64_t out_address, uint64_t count_address,
+                                     int n_cu, dbde_hip_project_weighted_plan_t *plan);
 
 /* ---- region traces: per frame and per labelled region, max / min / sum / sum of squares ---------- */
 /* A trace map is a label image (H x W int32, row-major, pitch W: 0 = no region, 1..n_labels = region id) classified
