@@ -65,6 +65,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_decode_scaled", "dbde16_hip_decode_scaled", "dbde_hip_scaled_plan", "dbde16_hip_scaled_plan",
     "dbde_hip_decode_mask", "dbde16_hip_decode_mask", "dbde_hip_mask_plan", "dbde16_hip_mask_plan",
     "dbde_hip_decode_patches", "dbde16_hip_decode_patches", "dbde_hip_patches_plan", "dbde16_hip_patches_plan",
+    "dbde_hip_patch_moments", "dbde16_hip_patch_moments", "dbde_hip_patch_moments_plan", "dbde16_hip_patch_moments_plan",
     "dbde_hip_crop_frames", "dbde16_hip_crop_frames", "dbde_hip_crop_plan", "dbde16_hip_crop_plan",
     "dbde_hip_encode_window", "dbde16_hip_encode_window", "dbde_hip_window_encode_plan", "dbde16_hip_window_encode_plan",
     "dbde_hip_writer_put_window",
@@ -252,6 +253,12 @@ def lib():
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_patches_plan", "dbde16_hip_patches_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, C.POINTER(PatchPlan)]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_patch_moments", "dbde16_hip_patch_moments"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, vp, vp, i, C.c_uint32, C.c_uint32, i, vp, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_patch_moments_plan", "dbde16_hip_patch_moments_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, C.POINTER(PatchMomentsPlan)]
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_crop_frames", "dbde16_hip_crop_frames"):
         getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, vp, sz, u64, vp, vp, vp, vp]
@@ -1209,6 +1216,100 @@ def origins_from_centres(centres, pw, ph):
     return np.ascontiguousarray(np.clip(r - np.array([pw // 2, ph // 2], np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32))
 
 
+MOMENT_COUNT, MOMENT_VALUE, MOMENT_ABOVE, MOMENT_BELOW = 0, 1, 2, 3   # DBDE_HIP_MOMENT_* (include/dbde_hip.h)
+MOMENT_WEIGHTS = {"count": MOMENT_COUNT, "value": MOMENT_VALUE, "above": MOMENT_ABOVE, "below": MOMENT_BELOW}
+
+
+def moment_weight_mode(weight):
+    """"count" / "value" / "above" / "below" (or DBDE_HIP_MOMENT_* as an int) -> the C-ABI's weight mode."""
+    if isinstance(weight, str):
+        if weight not in MOMENT_WEIGHTS:
+            raise ValueError(f"weight must be one of {sorted(MOMENT_WEIGHTS)}, not {weight!r}")
+        return MOMENT_WEIGHTS[weight]
+    return int(weight)
+
+
+class PatchMomentsPlan(C.Structure):
+    """dbde_hip_patch_moments_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("max_tiles_x", C.c_int32), ("max_tiles_y", C.c_int32), ("rows_per_workgroup", C.c_uint32),
+                ("steps_per_patch", C.c_uint32), ("threads", C.c_uint32), ("chunks_per_frame", C.c_uint32),
+                ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32), ("index_split", C.c_uint32),
+                ("lds_bytes", C.c_uint32), ("grid", C.c_uint64), ("moments_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def _patch_moments_plan(fn, W, H, n_frames, pw, ph, n_patches, edge):
+    """patch_moments_plan / patch_moments16_plan through the C function named fn."""
+    pl = PatchMomentsPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, pw, ph, n_patches, patch_edge_mode(edge), C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {pw}, {ph}, {n_patches}, {edge}) -> {rc}")
+    return pl.as_dict()
+
+
+def patch_moments_plan(W, H, n_frames, pw, ph, n_patches, edge="clamp"):
+    """dbde_hip_patch_moments_plan: the tiles a patch can span, the tile rows per step and the steps one workgroup
+    walks per patch, the index geometry, the grid and the bytes of moments of Codec.patch_moments (host arithmetic
+    only).  Raises ValueError where dbde_hip_patch_moments would return DBDE_HIP_ERR_ARG for its sizes and edge mode."""
+    return _patch_moments_plan("dbde_hip_patch_moments_plan", W, H, n_frames, pw, ph, n_patches, edge)
+
+
+def patch_moments16_plan(W, H, n_frames, pw, ph, n_patches, edge="clamp"):
+    """dbde16_hip_patch_moments_plan: patch_moments_plan for DBDE16 frames (Codec.patch_moments16)."""
+    return _patch_moments_plan("dbde16_hip_patch_moments_plan", W, H, n_frames, pw, ph, n_patches, edge)
+
+
+class PatchMoments:
+    """What Codec.patch_moments returns: per frame and patch the eight sums over the selected pixels,
+    moments[f, k] = (N, S, Sx, Sy, Sxx, Sxy, Syy, Sww) as int64 (n, K, 8) in PATCH coordinates (column j, row i); bbox
+    (optional) int32 (n, K, 4) = (j_min, i_min, j_max, i_max), (pw, ph, -1, -1) where nothing is selected; used int32
+    (n, K, 2), the origins the patches were taken at.  Entries of rejected frames and of patches beyond a frame's count
+    hold whatever the tensors held before the call.  The derived quantities are float64 torch tensors on the moments'
+    device (numpy arrays work the same way through PatchMoments(torch.from_numpy(...), ...))."""
+
+    def __init__(self, moments, bbox, used, pw, ph):
+        self.moments, self.bbox, self.used, self.pw, self.ph = moments, bbox, used, int(pw), int(ph)
+
+    def count(self):
+        """N: the selected pixels, int64 (n, K)."""
+        return self.moments[..., 0]
+
+    def mass(self):
+        """S: the sum of the weights, int64 (n, K)."""
+        return self.moments[..., 1]
+
+    def _means(self):
+        m = self.moments.to(torch.float64)
+        S = m[..., 1]
+        S = torch.where(S == 0, torch.full_like(S, float("nan")), S)
+        return m, S, m[..., 2] / S, m[..., 3] / S
+
+    def centroid(self):
+        """(n, K, 2) float64 (x, y) in FRAME coordinates: used + (Sx / S, Sy / S); NaN where S = 0."""
+        _, _, mx, my = self._means()
+        return torch.stack((mx, my), dim=-1) + self.used.to(torch.float64)
+
+    def covariance(self):
+        """(n, K, 2, 2) float64 [[cxx, cxy], [cxy, cyy]]: the central second moments over S, cxx = Sxx / S - (Sx / S)^2,
+        cxy = Sxy / S - (Sx / S)(Sy / S), cyy = Syy / S - (Sy / S)^2; NaN where S = 0."""
+        m, S, mx, my = self._means()
+        cxx, cxy, cyy = m[..., 4] / S - mx * mx, m[..., 5] / S - mx * my, m[..., 6] / S - my * my
+        return torch.stack((torch.stack((cxx, cxy), dim=-1), torch.stack((cxy, cyy), dim=-1)), dim=-2)
+
+    def orientation(self):
+        """(angle, major, minor), float64 (n, K) each: the angle of the major axis against the x axis in radians, in
+        (-pi/2, pi/2], 0.5 atan2(2 cxy, cxx - cyy), and the axis lengths 2 sqrt(eigenvalue) of the covariance (the
+        semi-axes of a uniformly filled ellipse); NaN where S = 0."""
+        c = self.covariance()
+        cxx, cxy, cyy = c[..., 0, 0], c[..., 0, 1], c[..., 1, 1]
+        half, diff = (cxx + cyy) / 2, (cxx - cyy) / 2
+        root = torch.sqrt(diff * diff + cxy * cxy)
+        angle = 0.5 * torch.atan2(2 * cxy, cxx - cyy)
+        return angle, 2 * torch.sqrt(half + root), 2 * torch.sqrt(torch.clamp(half - root, min=0))
+
+
 class CropPlan(C.Structure):
     """dbde_hip_crop_plan_t (include/dbde_hip.h)."""
     _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
@@ -1922,6 +2023,72 @@ class Codec:
         decode_frames16 returns its images); fill up to 65535."""
         return self._decode_patches("dbde16_hip_decode_patches", torch.int16, stream, stream_offset, stream_bytes,
                                     offsets, W, H, n, pw, ph, origins, counts, edge, fill, out, used, results)
+
+    def _patch_moments(self, fn, stream, stream_offset, stream_bytes, offsets, W, H, n, pw, ph, origins, lo, hi, weight,
+                       counts, edge, out, bbox, used, results):
+        """patch_moments / patch_moments16 through the C function named fn."""
+        if (not torch.is_tensor(origins) or origins.dtype != torch.int32 or origins.dim() != 3 or origins.shape[0] != n
+                or origins.shape[2] != 2 or not origins.is_contiguous()):
+            raise ValueError("origins must be a contiguous int32 device tensor of shape (n, K, 2)")
+        K = int(origins.shape[1])
+        if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 1
+                                   or counts.numel() != n or not counts.is_contiguous()):
+            raise ValueError("counts must be a contiguous 1-D int32 tensor of n entries (the U32 bits)")
+        # what the C call refuses of the scalars, checked here as well: the call is not made when n == 0, and ctypes would
+        # take lo, hi and the mode modulo 2^32 before the C range check sees them
+        lo, hi, mode, top = int(lo), int(hi), moment_weight_mode(weight), 0xFFFF if fn.startswith("dbde16") else 0xFF
+        if not (0 <= lo <= top and 0 <= hi <= top):
+            raise DbdeError(f"{fn}: thresholds lo={lo}, hi={hi} outside [0, {top}]")
+        if mode not in MOMENT_WEIGHTS.values():
+            raise DbdeError(f"{fn}: unknown weight mode {mode}")
+        if used is None:
+            used = torch.empty((n, K, 2), dtype=torch.int32, device=self.device)
+        elif not torch.is_tensor(used) or used.dtype != torch.int32 or not used.is_contiguous() or used.numel() < 2 * n * K:
+            raise ValueError("used must be a contiguous int32 device tensor of at least n * K * 2 entries")
+        if bbox is True:
+            bbox = torch.empty((n, K, 4), dtype=torch.int32, device=self.device)
+        elif bbox is False:
+            bbox = None
+        elif bbox is not None and (not torch.is_tensor(bbox) or bbox.dtype != torch.int32 or not bbox.is_contiguous()
+                                   or bbox.numel() < 4 * n * K):
+            raise ValueError("bbox must be a contiguous int32 device tensor of at least n * K * 4 entries")
+        if out is None:
+            out = torch.empty((n, K, 8), dtype=torch.int64, device=self.device)
+        elif not torch.is_tensor(out) or out.dtype != torch.int64 or not out.is_contiguous() or out.numel() < 8 * n * K:
+            raise ValueError("out must be a contiguous int64 device tensor of at least n * K * 8 entries")
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        if n == 0:   # nothing to do (empty tensors have no address to pass): the sizes are still checked
+            try:
+                _patch_moments_plan(fn + "_plan", W, H, 0, pw, ph, max(K, 1), edge)
+            except ValueError as e:
+                raise DbdeError(f"{fn}: {e}") from None
+            return PatchMoments(out, bbox, used, pw, ph), results
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(), W, H, n,
+                                 pw, ph, K, origins.data_ptr(), ptr(counts), patch_edge_mode(edge), lo, hi,
+                                 mode, out.data_ptr(), ptr(bbox), used.data_ptr(),
+                                 ptr(results) if n > 0 else None)
+        self._check(rc, fn)
+        return PatchMoments(out, bbox, used, pw, ph), results
+
+    def patch_moments(self, stream, stream_offset, stream_bytes, offsets, W, H, n, pw, ph, origins, lo, hi,
+                      weight="above", counts=None, edge="clamp", out=None, bbox=None, used=None, results=None):
+        """Thresholded image moments of K patches of pw x ph per frame of n frames (frame f at
+        stream.data_ptr()+stream_offset+offsets[f]) in one call, straight from the stream: no pixel is written.
+        origins, counts and edge as in decode_patches, except that a patch pixel outside the frame counts for nothing
+        (there is no fill).  A pixel p is selected when lo <= p <= hi; its weight is 1 ("count"), p ("value"), p - lo
+        ("above") or hi - p ("below").  out: optional int64 (n, K, 8) to write the sums into; bbox: True for the
+        selected pixels' boxes, or an int32 (n, K, 4) tensor to write them into; used: optional int32 (n, K, 2).
+        Returns (PatchMoments, results (n, 4) int64) like decode_frames."""
+        return self._patch_moments("dbde_hip_patch_moments", stream, stream_offset, stream_bytes, offsets, W, H, n, pw,
+                                   ph, origins, lo, hi, weight, counts, edge, out, bbox, used, results)
+
+    def patch_moments16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, pw, ph, origins, lo, hi,
+                        weight="above", counts=None, edge="clamp", out=None, bbox=None, used=None, results=None):
+        """DBDE16 patch moments: patch_moments' arguments and results over U16 pixels (lo, hi up to 65535)."""
+        return self._patch_moments("dbde16_hip_patch_moments", stream, stream_offset, stream_bytes, offsets, W, H, n,
+                                   pw, ph, origins, lo, hi, weight, counts, edge, out, bbox, used, results)
 
     def _crop_frames(self, fn, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, out, out_offset,
                      capacity, origins, slot_stride, out_offsets, out_bytes, origins_used, results):

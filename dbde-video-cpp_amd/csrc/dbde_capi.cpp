@@ -21,6 +21,7 @@
 #include "dbde_hist_kernels.h"
 #include "dbde_kernels.h"
 #include "dbde_mask_kernels.h"
+#include "dbde_moment_kernels.h"
 #include "dbde_patch_kernels.h"
 #include "dbde_project_kernels.h"
 #include "dbde_roi_kernels.h"
@@ -2491,6 +2492,133 @@ int dbde16_hip_decode_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t
                               uint16_t *d_out, int32_t *d_used, dbde_hip_frame_result *d_results) {
     return decode_patches_common(ctx, "decode_patches16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, pw,
                                  ph, n_patches, d_origins, d_counts, edge_mode, fill, d_out, d_used, d_results);
+}
+
+// ---- patch moments ------------------------------------------------------------------------------------------
+// The sizes and the edge mode are the patch decoder's (plan_patches); what is added is the height limit that keeps every
+// sum inside 64 bits, and the launch: one workgroup per patch that walks the patch's groups of tile rows itself.
+static const char *plan_moments(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode, uint32_t pix,
+                                PatchPlan &pl) {
+    if (const char *why = plan_patches(W, H, n_frames, pw, ph, n_patches, edge_mode, pix, pl)) return why;
+    if (ph > kMomentMaxHeight) return "patch higher than 512 rows (the sums could pass 64 bits)";
+    static_assert(kMomentMaxTilesX == kPatchMaxTilesX && kMomentThreads == kPatchThreads, "plan_patches' geometry is the kernel's");
+    static_assert(kMomentClamp == DBDE_HIP_PATCH_CLAMP && kMomentFill == DBDE_HIP_PATCH_FILL, "edge modes");
+    static_assert(kMomentCount == DBDE_HIP_MOMENT_COUNT && kMomentValue == DBDE_HIP_MOMENT_VALUE &&
+                  kMomentAbove == DBDE_HIP_MOMENT_ABOVE && kMomentBelow == DBDE_HIP_MOMENT_BELOW, "weight modes");
+    return nullptr;
+}
+
+static int moments_plan_common(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode, uint32_t pix,
+                               dbde_hip_patch_moments_plan_t *plan) {
+    PatchPlan pl;
+    memset(&pl, 0, sizeof pl);
+    if (!plan || plan_moments(W, H, n_frames, pw, ph, n_patches, edge_mode, pix, pl)) return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->max_tiles_x = (int32_t)pl.mtx;
+    plan->max_tiles_y = (int32_t)pl.mty;
+    plan->rows_per_workgroup = pl.G;
+    plan->steps_per_patch = pl.groups;
+    plan->threads = kMomentThreads;
+    plan->chunks_per_frame = pl.dg.cpf;
+    plan->chunk_tiles = pl.dg.ct;
+    plan->chunk_pieces = pl.dg.ct == pl.g.w || pl.dg.pieces > 1u ? pl.dg.pieces : 0u;
+    plan->index_split = pl.split;
+    plan->lds_bytes = kMomentPayBytesOf(pix);
+    plan->grid = (uint64_t)n_frames * (uint64_t)n_patches;
+    plan->moments_bytes = plan->grid * 64u;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_patch_moments_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
+                                dbde_hip_patch_moments_plan_t *plan) {
+    return moments_plan_common(W, H, n_frames, pw, ph, n_patches, edge_mode, 1u, plan);
+}
+
+int dbde16_hip_patch_moments_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
+                                  dbde_hip_patch_moments_plan_t *plan) {
+    return moments_plan_common(W, H, n_frames, pw, ph, n_patches, edge_mode, 2u, plan);
+}
+
+// Both calls: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the moments kernel in slot 2.
+static int patch_moments_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
+                                size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int pw,
+                                int ph, int n_patches, const int32_t *d_origins, const uint32_t *d_counts, int edge_mode,
+                                uint32_t lo, uint32_t hi, int weight_mode, uint64_t *d_moments, int32_t *d_bbox,
+                                int32_t *d_used, dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    PatchPlan pl;
+    memset(&pl, 0, sizeof pl);
+    if (const char *why = plan_moments(W, H, n_frames, pw, ph, n_patches, edge_mode, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d, %d patches of %dx%d, edge mode %d)", name, why, W, H,
+                    n_frames, n_patches, pw, ph, edge_mode);
+    if (!d_stream || !d_frame_offsets || !d_origins || !d_moments) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    const uint32_t pix_max = pix == 1u ? 0xFFu : 0xFFFFu;
+    if (lo > pix_max || hi > pix_max)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: threshold %u above %u", name, lo > pix_max ? lo : hi, pix_max);
+    if (weight_mode < DBDE_HIP_MOMENT_COUNT || weight_mode > DBDE_HIP_MOMENT_BELOW)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: unknown weight mode %d", name, weight_mode);
+    if (reinterpret_cast<uintptr_t>(d_moments) & 7u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the moments must be 8-byte aligned", name);
+    if ((reinterpret_cast<uintptr_t>(d_origins) | reinterpret_cast<uintptr_t>(d_counts) | reinterpret_cast<uintptr_t>(d_used) |
+         reinterpret_cast<uintptr_t>(d_bbox)) & 3u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: origins, counts, boxes and used origins must be 4-byte aligned", name);
+    if (n_frames == 0) return DBDE_HIP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.dg, pix, pl.split);
+    if (rc) return rc;
+
+    MomentParams p;
+    memset(&p, 0, sizeof p);
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.origins = d_origins;
+    p.counts = d_counts;
+    p.moments = d_moments;
+    p.bbox = d_bbox;
+    p.used = d_used;
+    p.W = W;
+    p.H = H;
+    p.pw = pw;
+    p.ph = ph;
+    p.n_patches = (uint32_t)n_patches;
+    p.w = pl.g.w;
+    p.h = pl.g.h;
+    p.T = pl.g.T;
+    p.geom = pl.dg;
+    p.mtx = pl.mtx;
+    p.G = pl.G;
+    p.steps = pl.groups;
+    p.mode = edge_mode == DBDE_HIP_PATCH_FILL ? kMomentFill : kMomentClamp;
+    p.lo = lo;
+    p.hi = hi;
+    p.weight = (uint32_t)weight_mode;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_patch_moments(p, (uint32_t)n_frames, pix, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_patch_moments(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int pw, int ph, int n_patches,
+                           const int32_t *d_origins, const uint32_t *d_counts, int edge_mode, uint32_t lo, uint32_t hi,
+                           int weight_mode, uint64_t *d_moments, int32_t *d_bbox, int32_t *d_used,
+                           dbde_hip_frame_result *d_results) {
+    return patch_moments_common(ctx, "patch_moments", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, pw, ph,
+                                n_patches, d_origins, d_counts, edge_mode, lo, hi, weight_mode, d_moments, d_bbox, d_used,
+                                d_results);
+}
+
+int dbde16_hip_patch_moments(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                             const uint64_t *d_frame_offsets, int W, int H, int n_frames, int pw, int ph, int n_patches,
+                             const int32_t *d_origins, const uint32_t *d_counts, int edge_mode, uint32_t lo, uint32_t hi,
+                             int weight_mode, uint64_t *d_moments, int32_t *d_bbox, int32_t *d_used,
+                             dbde_hip_frame_result *d_results) {
+    return patch_moments_common(ctx, "patch_moments16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, pw,
+                                ph, n_patches, d_origins, d_counts, edge_mode, lo, hi, weight_mode, d_moments, d_bbox,
+                                d_used, d_results);
 }
 
 // ---- compressed-domain crop ---------------------------------------------------------------------------------

@@ -1156,6 +1156,70 @@ int dbde_hip_patches_plan(int W, int H, int n_frames, int pw, int ph, int n_patc
 int dbde16_hip_patches_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
                             dbde_hip_patches_plan_t *plan);
 
+/* ---- patch moments: centroid and shape sums per tracked window ----------------------------------- */
+/* Patch moments: for each of n_patches windows of one size pw x ph per frame, each with its own origin per frame (as in
+ * dbde_hip_decode_patches), the thresholded image moments up to second order, straight from the compressed stream by
+ * ONE index pass and one kernel; no pixel is written.  Stream, offsets, d_origins, d_counts, d_used, d_results,
+ * validation and the two edge modes are dbde_hip_decode_patches' own, with one difference: there is no fill value.  A
+ * patch pixel outside the frame (the encoder's padding beyond W or H included) is not part of any sum; a FILL-mode
+ * patch wholly outside the frame gives all zeros and an empty box.
+ *   Selection: pixel p at patch row i (0 <= i < ph), column j (0 <= j < pw), inside the frame, is selected when
+ *     lo <= p <= hi.  lo > hi is legal and selects nothing.
+ *   Weight w of a selected pixel, by weight_mode: DBDE_HIP_MOMENT_COUNT w = 1; _VALUE w = p; _ABOVE w = p - lo (a bright
+ *     object over a dark level); _BELOW w = hi - p (a dark object under a bright level).
+ *   d_moments: device uint64 [n_frames][n_patches][8], 8-byte aligned, required.  Over the selected pixels of patch
+ *     (f, k): [0] N = sum 1, [1] S = sum w, [2] Sx = sum w j, [3] Sy = sum w i, [4] Sxx = sum w j^2, [5] Sxy = sum w i j,
+ *     [6] Syy = sum w i^2, [7] Sww = sum w^2.  Coordinates are relative to the patch, so with pw <= 505 and ph <= 512
+ *     every sum stays below 2^63: 65535 * 511^2 * 505 * 512 < 2^63 bounds Syy, the largest, with 511^2 taken for every
+ *     row (a DBDE16 patch of all 65535 gives 65535 * 505 * sum i^2, about 2^50.4), and Sww is at most 65535^2 * 505 * 512
+ *     < 2^50.  All arithmetic is integer: the sums are exact and do not depend on the launch.
+ *   d_bbox: optional device int32 [n_frames][n_patches][4], 4-byte aligned: (j_min, i_min, j_max, i_max) of the
+ *     selected pixels, (pw, ph, -1, -1) when none is selected.
+ * A rejected frame, and a patch k >= min(d_counts[f], n_patches), leave their moments, box and used entries untouched;
+ * the caller zeroes nothing beforehand, every live entry is written once by plain stores.  No byte at or beyond
+ * stream_bytes is read; nothing outside the three outputs is written.  n_frames == 0 does nothing.
+ * DBDE_HIP_ERR_ARG: whatever dbde_hip_decode_patches refuses for the same sizes and edge mode; ph > 512; lo or hi above
+ * the pixel maximum (255; DBDE16: 65535); an unknown weight mode; a null stream, offsets, origins or d_moments; d_moments
+ * not 8-byte aligned, d_bbox (or origins, counts, used) not 4-byte aligned.  Asynchronous on the context's stream; timing
+ * hook: the index kernel in slot 1, the moments kernel in slot 2. */
+enum { DBDE_HIP_MOMENT_COUNT = 0, DBDE_HIP_MOMENT_VALUE = 1, DBDE_HIP_MOMENT_ABOVE = 2, DBDE_HIP_MOMENT_BELOW = 3 };
+int dbde_hip_patch_moments(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                           int pw, int ph, int n_patches, const int32_t *d_origins, const uint32_t *d_counts,
+                           int edge_mode, uint32_t lo, uint32_t hi, int weight_mode,
+                           uint64_t *d_moments, int32_t *d_bbox, int32_t *d_used,
+                           dbde_hip_frame_result *d_results);
+/* Patch moments of DBDE16 frames: the same contract over U16 pixels (lo, hi up to 65535).  Validation is
+ * dbde16_hip_decode_frames' own. */
+int dbde16_hip_patch_moments(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                             const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                             int pw, int ph, int n_patches, const int32_t *d_origins, const uint32_t *d_counts,
+                             int edge_mode, uint32_t lo, uint32_t hi, int weight_mode,
+                             uint64_t *d_moments, int32_t *d_bbox, int32_t *d_used,
+                             dbde_hip_frame_result *d_results);
+/* What dbde_hip_patch_moments runs (pure host arithmetic, shared with the call): refuses exactly the arguments the call
+ * refuses, pointers and thresholds aside (DBDE_HIP_ERR_ARG), and reports the launch.  ONE 64-lane workgroup takes a
+ * whole patch: it walks steps_per_patch groups of rows_per_workgroup = max(1, 64 / max_tiles_x) tile rows, one tile per
+ * lane, and keeps the sums in registers (a 505 x 512 patch is 65 steps of one wave). */
+typedef struct dbde_hip_patch_moments_plan_t {
+    int32_t max_tiles_x, max_tiles_y; /* the most tiles any origin makes a patch span, as dbde_hip_patches_plan */
+    uint32_t rows_per_workgroup;      /* tile rows of one patch per step */
+    uint32_t steps_per_patch;         /* groups of tile rows one workgroup walks = ceil(max_tiles_y / rows_per_workgroup) */
+    uint32_t threads;                 /* workgroup size: 64 */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t lds_bytes;               /* LDS per workgroup (the rows' payload ranges) */
+    uint64_t grid;                    /* workgroups: n_frames * n_patches */
+    uint64_t moments_bytes;           /* n_frames * n_patches * 64 */
+} dbde_hip_patch_moments_plan_t;
+int dbde_hip_patch_moments_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
+                                dbde_hip_patch_moments_plan_t *plan);
+/* The same for dbde16_hip_patch_moments: its index and LDS. */
+int dbde16_hip_patch_moments_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
+                                  dbde_hip_patch_moments_plan_t *plan);
+
 /* ---- compressed-domain crop: a window of each frame as a new stream ------------------------------ */
 /* Crops the rw x rh window at (x0, y0) out of each of n_frames DBDE frames and writes it as a complete DBDE frame of an
  * rw x rh image, without decoding the window: tiles whose valid pixels are unchanged are COPIED (depth byte, minimum,
