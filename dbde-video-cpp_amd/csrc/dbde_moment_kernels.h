@@ -52,10 +52,14 @@ struct MomentParams {
     uint32_t mode;                  // kMomentClamp / kMomentFill
     uint32_t lo, hi;                // the band: a pixel p is selected when lo <= p <= hi
     uint32_t weight;                // kMomentCount / Value / Above / Below
+    uint32_t block0;                // the workgroup number of this launch's first workgroup (launch_patch_moments sets it)
 };
 
-// One workgroup per (frame, patch); grid = n_frames * n_patches (the host keeps it below 2^31).  pix: bytes per pixel,
-// 1 = DBDE, 2 = DBDE16.
+// A launch's grid is counted in work-items: workgroups * kMomentThreads must stay below 2^32.
+constexpr uint32_t kMomentMaxGrid = (1u << 26) - 1u;
+
+// One workgroup per (frame, patch): n_frames * n_patches of them (the host keeps that below 2^31), in as many launches
+// of at most kMomentMaxGrid workgroups as that takes.  pix: bytes per pixel, 1 = DBDE, 2 = DBDE16.
 hipError_t launch_patch_moments(const MomentParams &p, uint32_t n_frames, uint32_t pix, hipStream_t s);
 
 }  // namespace dbde

@@ -109,7 +109,8 @@ __global__ __launch_bounds__(kMomentThreads, PIX == 1u ? 7 : 4) void patch_momen
     static_assert(kMomentThreads * 64u * PIX + 32u * kMomentThreads <= kPayBytes, "G <= 64 row ranges must fit");
 
     const uint32_t lane = threadIdx.x;
-    const uint32_t k = blockIdx.x % p.n_patches, f = blockIdx.x / p.n_patches;
+    const uint32_t b = p.block0 + blockIdx.x;
+    const uint32_t k = b % p.n_patches, f = b / p.n_patches;
     if (!p.frame_ok[f]) return;   // rejected frame: its entries stay untouched
     if (p.counts) {
         const uint32_t cnt = p.counts[f];
@@ -396,13 +397,20 @@ __global__ __launch_bounds__(kMomentThreads, PIX == 1u ? 7 : 4) void patch_momen
     }
 }
 
-hipError_t launch_patch_moments(const MomentParams &p, uint32_t n_frames, uint32_t pix, hipStream_t s) {
-    const uint32_t grid = n_frames * p.n_patches;   // (the host keeps it below 2^31)
-    if (pix == 1u)
-        hipLaunchKernelGGL((patch_moments_kernel<1>), dim3(grid), dim3(kMomentThreads), 0, s, p);
-    else
-        hipLaunchKernelGGL((patch_moments_kernel<2>), dim3(grid), dim3(kMomentThreads), 0, s, p);
-    return hipGetLastError();
+hipError_t launch_patch_moments(const MomentParams &p0, uint32_t n_frames, uint32_t pix, hipStream_t s) {
+    const uint32_t total = n_frames * p0.n_patches;   // (the host keeps it below 2^31)
+    MomentParams p = p0;
+    // a grid of 2^26 workgroups or more is 2^32 work-items or more, which one launch does not take
+    for (p.block0 = 0; p.block0 < total; p.block0 += kMomentMaxGrid) {
+        const uint32_t grid = total - p.block0 < kMomentMaxGrid ? total - p.block0 : kMomentMaxGrid;
+        if (pix == 1u)
+            hipLaunchKernelGGL((patch_moments_kernel<1>), dim3(grid), dim3(kMomentThreads), 0, s, p);
+        else
+            hipLaunchKernelGGL((patch_moments_kernel<2>), dim3(grid), dim3(kMomentThreads), 0, s, p);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace dbde

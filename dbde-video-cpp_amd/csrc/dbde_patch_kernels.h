@@ -44,10 +44,15 @@ struct PatchParams {
     uint32_t groups;                // workgroups per patch: ceil(the most tile rows a patch spans / G)
     uint32_t mode;                  // kPatchClamp / kPatchFill
     uint32_t fill;                  // kPatchFill: the pixel outside the frame
+    uint32_t block0;                // the workgroup number of this launch's first workgroup (launch_decode_patches sets it)
 };
 
-// One workgroup per (frame, patch, group of G tile rows); grid = n_frames * n_patches * groups (the host keeps it below
-// 2^31).  pix: bytes per pixel, 1 = DBDE, 2 = DBDE16.
+// A launch's grid is counted in work-items: workgroups * kPatchThreads must stay below 2^32.
+constexpr uint32_t kPatchMaxGrid = (1u << 26) - 1u;
+
+// One workgroup per (frame, patch, group of G tile rows): n_frames * n_patches * groups of them (the host keeps that
+// below 2^31), in as many launches of at most kPatchMaxGrid workgroups as that takes.  pix: bytes per pixel, 1 = DBDE,
+// 2 = DBDE16.
 hipError_t launch_decode_patches(const PatchParams &p, uint32_t n_frames, uint32_t pix, hipStream_t s);
 
 }  // namespace dbde

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kPatchThreads) void decode_patches_kernel(PatchPara
     const Pix *band = reinterpret_cast<const Pix *>(s_pay);
 
     const uint32_t lane = threadIdx.x;
-    uint32_t b = blockIdx.x;
+    uint32_t b = p.block0 + blockIdx.x;
     const uint32_t grp = b % p.groups;
     b /= p.groups;
     const uint32_t k = b % p.n_patches, f = b / p.n_patches;
@@ -291,13 +291,20 @@ __global__ __launch_bounds__(kPatchThreads) void decode_patches_kernel(PatchPara
     }
 }
 
-hipError_t launch_decode_patches(const PatchParams &p, uint32_t n_frames, uint32_t pix, hipStream_t s) {
-    const uint32_t grid = n_frames * p.n_patches * p.groups;   // (the host keeps it below 2^31)
-    if (pix == 1u)
-        hipLaunchKernelGGL((decode_patches_kernel<1>), dim3(grid), dim3(kPatchThreads), 0, s, p);
-    else
-        hipLaunchKernelGGL((decode_patches_kernel<2>), dim3(grid), dim3(kPatchThreads), 0, s, p);
-    return hipGetLastError();
+hipError_t launch_decode_patches(const PatchParams &p0, uint32_t n_frames, uint32_t pix, hipStream_t s) {
+    const uint32_t total = n_frames * p0.n_patches * p0.groups;   // (the host keeps it below 2^31)
+    PatchParams p = p0;
+    // a grid of 2^26 workgroups or more is 2^32 work-items or more, which one launch does not take
+    for (p.block0 = 0; p.block0 < total; p.block0 += kPatchMaxGrid) {
+        const uint32_t grid = total - p.block0 < kPatchMaxGrid ? total - p.block0 : kPatchMaxGrid;
+        if (pix == 1u)
+            hipLaunchKernelGGL((decode_patches_kernel<1>), dim3(grid), dim3(kPatchThreads), 0, s, p);
+        else
+            hipLaunchKernelGGL((decode_patches_kernel<2>), dim3(grid), dim3(kPatchThreads), 0, s, p);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace dbde

@@ -12,7 +12,7 @@ test_gpu_crafted_decode16.Stream16 with rejected frames mixed in, "encoder-writt
 encoders' byte-for-byte parity with them is established elsewhere), each with the oracle's result row and image of
 every frame.  An Op is (name, bits, run, expect, plan) plus the shapes of its outputs: run() makes the call into
 guarded canvases, expect() gives every output element for element -- the family references of binned_ref, crop_ref,
-scaled_ref, wenc_ref, family_refs and the oracles -- with the canvas fill where a rejected frame must leave its
+scaled_ref, wenc_ref, gproject_ref, mask_ref, patch_ref, moments_ref, wproject_ref, family_refs and the oracles -- with the canvas fill where a rejected frame must leave its
 output alone, plan() what the planner reports (and the index launch the call makes).  Everything is integer or
 bit-exact by specification: every comparison is equality.
 
@@ -41,9 +41,14 @@ TABLE, SELF, FUSED = 0, 1, 2
 MID = 3
 RESIDENT = 513                   # workgroups the persistent encoders hold (encode_plan's default, test_encode_forms)
 
-CONSUMERS8 = ("decode_frames", "decode_roi", "project", "traces", "histogram", "decode_binned", "decode_scaled",
-              "crop_frames")
+OLD_CONSUMERS8 = ("decode_frames", "decode_roi", "project", "traces", "histogram", "decode_binned", "decode_scaled",
+                  "crop_frames")
+NEW_CONSUMERS8 = ("project_groups", "decode_mask", "decode_patches", "project_weighted", "patch_moments")
+CONSUMERS8 = OLD_CONSUMERS8 + NEW_CONSUMERS8
 CONSUMERS = CONSUMERS8 + tuple(c + "16" for c in CONSUMERS8)
+# (the sixteen the first chains were written for, in their order then, and the ten of the five newer families)
+OLD_CONSUMERS = OLD_CONSUMERS8 + tuple(c + "16" for c in OLD_CONSUMERS8)
+NEW_CONSUMERS = NEW_CONSUMERS8 + tuple(c + "16" for c in NEW_CONSUMERS8)
 # the windows of each pool geometry: the whole frame, and an odd-sized one at a multiple of 8 (crop, binned)
 WINDOWS = {(200, 123): ((0, 0, 200, 123), (48, 16, 101, 60)), (72, 72): ((0, 0, 72, 72), (8, 8, 40, 33)),
            (200, 40): ((0, 0, 200, 40), (16, 8, 77, 27))}
@@ -236,6 +241,12 @@ def assert_pool_properties(P):
         pl = roi(D.W, D.H, D.n, 0, 0, D.W, D.H)
         assert pl["chunks_per_frame"] < 8 and pl["index_split"] == 1 and not all(D.ok), pl
         assert pl["chunks_per_frame"] != roi(A.W, A.H, A.n, 0, 0, A.W, A.H)["chunks_per_frame"]
+        # the patch families index the whole frame whatever the patch: PATCH splits on A, not on D, not on C's 300 frames
+        for fn in ("patches", "patch_moments"):
+            plan = getattr(dv, fn + suffix(b) + "_plan")
+            for edge in ("clamp", "fill"):
+                split = {p.name[0]: plan(p.W, p.H, p.n, *PATCH, PATCHES_PER_FRAME, edge)["index_split"] for p in (A, C, D)}
+                assert split["A"] > 1 and split["C"] == 1 and split["D"] == 1, (fn, b, edge, split)
     assert dv.decode_plan(72, 72, 300)["kernel"] == MID
     for k, want in (("split", "split"), ("table", "table"), ("self", "self"), ("fused", "fused"), ("mid", None)):
         E = P["E" + k]
@@ -765,14 +776,425 @@ for _b in (8, 16):
                                  prepare=lambda codec, pool, prm: origins_dev(pool, prm))
 
 
+# ---- the five newer families: what they share ------------------------------------------------------------------------
+PATCH = (24, 16)                 # pw x ph of the patch families: inside every pool geometry, more than one tile row
+PATCHES_PER_FRAME = 6
+
+
+def suffix(bits):
+    return "" if bits == 8 else "16"
+
+
+def images_or_none(pool, f0, n):
+    return [pool.images[f] if pool.ok[f] else None for f in range(f0, f0 + n)]
+
+
+def parts_of(prm, f0, n):
+    """The (f0, n) of every call whose frames the step's shared outputs hold: of a continuation (prm["cuts"]: the frame
+    numbers its parts begin and end at) the parts up to this one, else the step itself."""
+    if prm.get("acc") is None:
+        return [(f0, n)]
+    cuts = prm["cuts"]
+    assert f0 in cuts[:-1] and f0 + n == cuts[cuts.index(f0) + 1] and cuts[0] == prm["acc_from"], prm
+    return [(a, b - a) for a, b in zip(cuts, cuts[1:]) if a <= f0]
+
+
+def continues(prm):
+    return bool(prm.get("acc") is not None and prm["acc_from"] < prm.get("f0", 0))
+
+
+def device_cus():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def band_of(pool, prm):
+    """(lo, hi) of a step: "mid" the middle half of the range, "empty" lo > hi, "tile" the minimum and maximum of one
+    8 x 8 tile of the pool's first accepted image (the sites of a decision taken from the tile's header alone)."""
+    top = (1 << pool.bits) - 1
+    kind = prm.get("band", "mid")
+    if kind == "mid":
+        return top // 4, top - top // 4
+    if kind == "empty":
+        return top // 2, top // 2 - 1
+    assert kind == "tile"
+    im = next(im for im in pool.images if im is not None)
+    ty, tx = (pool.H // 16) * 8, (pool.W // 16) * 8
+    return int(im[ty:ty + 8, tx:tx + 8].min()), int(im[ty:ty + 8, tx:tx + 8].max())
+
+
+def patch_origins_of(pool, prm):
+    """(n, K, 2) int64 origins: inside the frame, across its edges and wholly outside it."""
+    f0, n = frames_of(pool, prm)
+    pw, ph = PATCH
+    rng = np.random.default_rng(pool.W * 137 + pool.H * 11 + n + f0)
+    org = np.stack([rng.integers(-pw - 2, pool.W + 3, (n, PATCHES_PER_FRAME)),
+                    rng.integers(-ph - 2, pool.H + 3, (n, PATCHES_PER_FRAME))], -1).astype(np.int64)
+    if n:
+        org[0, 0] = (-pw, -ph)                                    # wholly outside
+        org[-1, -1] = (pool.W - pw // 2, pool.H - ph // 2)        # across the far corner
+    return org
+
+
+def patch_counts_of(pool, prm):
+    """None, or the live patches per frame: a 0, a value above K, everything between."""
+    if not prm.get("counts"):
+        return None
+    f0, n = frames_of(pool, prm)
+    K = PATCHES_PER_FRAME
+    return np.resize(np.array([K + 3, 0, 1, K, 2, K - 1], np.int64), n)
+
+
+def _patch_inputs(pool, prm):
+    """The device origins (for a call without frames: those of one frame, which is never read) and counts."""
+    import torch
+    f0, n = frames_of(pool, prm)
+    key = (pool.name, f0, n, bool(prm.get("counts")))
+    src = prm if n else dict(prm, n=1)
+    org = const(("patch_org",) + key, lambda: torch.from_numpy(patch_origins_of(pool, src).astype(np.int32)).cuda())
+    cnt = patch_counts_of(pool, src)
+    if cnt is not None:
+        cnt = const(("patch_cnt",) + key, lambda: torch.from_numpy(cnt.astype(np.int32)).cuda())
+    return org, cnt
+
+
+# project_groups -------------------------------------------------------------------------------------------------------
+GROUP_STARTS = (0, 5, 5, 2, 9, 4000)      # pool frame numbers: [0, 5), two empty groups, [2, 9) overlapping, the rest
+
+
+def _grp_starts(pool, prm):
+    """None (the uniform form), or the call's group_starts: the step's, which count the pool's frames, from the call's
+    first frame on (a group that ends before it is empty, one that begins before it begins with it)."""
+    if prm.get("starts") is None:
+        return None
+    f0, n = frames_of(pool, prm)
+    return [max(int(s) - f0, 0) for s in prm["starts"]]
+
+
+def _grp_groups(pool, prm):
+    f0, n = frames_of(pool, prm)
+    return len(prm["starts"]) - 1 if prm.get("starts") is not None else -(-n // prm["g"])
+
+
+def _grp_outputs(pool, prm):
+    f0, n = frames_of(pool, prm)
+    x, y, rw, rh = window_of(pool, prm)
+    G = _grp_groups(pool, prm)
+    dts = dict(max=pix_dtype(pool.bits), min=pix_dtype(pool.bits), sum="int16" if prm.get("sum16") else "int32", sumsq="int64")
+    return dict({s: ((G, rh, rw), dts[s]) for s in prm.get("stats", ALL4)}, group_counts=((G,), "int32"), **results_spec(n))
+
+
+def _grp_starts_dev(pool, prm):
+    import torch
+    st = _grp_starts(pool, prm)
+    if st is None:
+        return None
+    return const(("starts", tuple(st)), lambda: torch.tensor(st, dtype=torch.int32, device="cuda"))
+
+
+def _grp_run(codec, pool, prm, out):
+    import torch
+    dv = dvm()
+    pr = dv.GroupProjection(counts=out["group_counts"].t, **{s: out[s].t for s in prm.get("stats", ALL4)})
+    fn = codec.project_groups if pool.bits == 8 else codec.project_groups16
+    fn(*stream_args(pool, prm), *window_of(pool, prm), group_frames=prm.get("g"), group_starts=_grp_starts_dev(pool, prm),
+       stats=prm.get("stats", ALL4), sum_dtype=torch.int16 if prm.get("sum16") else torch.int32, accumulate=continues(prm),
+       out=pr, results=out["results"].t)
+
+
+def _grp_reduce(pool, prm, parts):
+    """gproject_ref over the frames of every group, the calls `parts` taken together (every value is an exact integer:
+    the order does not matter)."""
+    import gproject_ref as gr
+    x, y, rw, rh = window_of(pool, prm)
+    G = _grp_groups(pool, prm)
+    frames = [[] for _ in range(G)]
+    for f0, n in parts:
+        step = dict(prm, f0=f0, n=n)
+        for k, (b, e) in enumerate(gr.group_ranges(n, prm.get("g"), _grp_starts(pool, step))):
+            frames[k] += list(range(f0 + b, f0 + e))
+    images = [pool.images[f] if pool.ok[f] else None for fs in frames for f in fs]
+    ends = np.cumsum([0] + [len(fs) for fs in frames])
+    return gr.reduce_groups(images, list(zip(ends[:-1], ends[1:])), x, y, rw, rh, pix=pool.bits // 8)
+
+
+def _grp_expect(pool, prm):
+    """Every group from gproject_ref (a group without frames holds the empty projection, which a call that does not
+    accumulate writes and one that does leaves as it is).  The last part of a continuation over the whole pool is the
+    one-call reference."""
+    import gproject_ref as gr
+    f0, n = frames_of(pool, prm)
+    x, y, rw, rh = window_of(pool, prm)
+    red = _grp_reduce(pool, prm, parts_of(prm, f0, n))
+    if prm.get("acc") is not None and prm["acc_from"] == 0 and f0 + n == pool.n:
+        whole = gr.reduce_groups(images_or_none(pool, 0, pool.n), gr.group_ranges(pool.n, prm.get("g"), prm.get("starts")),
+                                 x, y, rw, rh, pix=pool.bits // 8)
+        assert all(np.array_equal(whole[k], red[k]) for k in whole), "the parts do not add up to the one-call reference"
+        red = whole
+    want = {}
+    for s in prm.get("stats", ALL4):
+        if s in ("max", "min"):
+            want[s] = as_pix(red[s], pool.bits)
+        elif s == "sum":
+            want[s] = red[s].astype(np.uint16).view(np.int16) if prm.get("sum16") else red[s].astype(np.uint32).view(np.int32)
+        else:
+            want[s] = red[s].astype(np.int64)
+    return dict(want, group_counts=red["counts"].astype(np.int32), results=rows_array(pool.rows[f0:f0 + n]))
+
+
+def _grp_plan(pool, prm):
+    dv = dvm()
+    f0, n = frames_of(pool, prm)
+    x, y, rw, rh = window_of(pool, prm)
+    fn = dv.project_groups_plan if pool.bits == 8 else dv.project_groups16_plan
+    pl = fn(pool.W, pool.H, n, x, y, rw, rh, group_frames=prm.get("g"), has_group_starts=prm.get("starts") is not None,
+            n_groups=_grp_groups(pool, prm), stats=prm.get("stats", ALL4),
+            sum_dtype=dv.SUM_U16 if prm.get("sum16") else dv.SUM_U32, accumulate=continues(prm))
+    pl["index"] = index_of_roi_plan(pool.bits, n, pl)
+    return pl
+
+
+# decode_mask ----------------------------------------------------------------------------------------------------------
+def _mask_maps(pool):
+    """Per-pixel lo / hi maps in frame coordinates (unsigned host arrays): bands of every width, lo > hi among them."""
+    top = (1 << pool.bits) - 1
+    rng = np.random.default_rng(pool.W * 29 + pool.H * 3 + pool.bits)
+    lo = rng.integers(0, top // 2 + 1, (pool.H, pool.W))
+    hi = np.clip(lo + rng.integers(-(top // 8) - 1, top // 2 + 1, (pool.H, pool.W)), 0, top)
+    dt = np.uint8 if pool.bits == 8 else np.uint16
+    return lo.astype(dt), hi.astype(dt)
+
+
+def _mask_maps_dev(pool):
+    import torch
+    npd = np.uint8 if pool.bits == 8 else np.int16
+    return const(("mask_maps", pool.W, pool.H, pool.bits),
+                 lambda: tuple(torch.from_numpy(np.ascontiguousarray(m).view(npd)).cuda() for m in _mask_maps(pool)))
+
+
+def _mask_outputs(pool, prm):
+    f0, n = frames_of(pool, prm)
+    x, y, rw, rh = window_of(pool, prm)
+    spec = dict(words=((n, rh, (rw + 63) // 64), "int64"), counts=((n,), "int32"))
+    if prm.get("boxes"):
+        spec["boxes"] = ((n, 4), "int32")
+    return dict(spec, **results_spec(n))
+
+
+def _mask_run(codec, pool, prm, out):
+    dv = dvm()
+    x, y, rw, rh = window_of(pool, prm)
+    lo, hi = _mask_maps_dev(pool) if prm.get("maps") else band_of(pool, prm)
+    fn = codec.decode_mask if pool.bits == 8 else codec.decode_mask16
+    fn(*stream_args(pool, prm), x, y, rw, rh, lo=lo, hi=hi, outside=bool(prm.get("outside")), origins=origins_dev(pool, prm),
+       mask=dv.Mask(out["words"].t, out["counts"].t, out["boxes"].t if prm.get("boxes") else None, rw=rw),
+       results=out["results"].t)
+
+
+def _mask_expect(pool, prm):
+    """mask_ref's words, counts and boxes; a rejected frame leaves its words alone, counts 0 and has the empty box."""
+    import mask_ref
+    f0, n = frames_of(pool, prm)
+    x, y, rw, rh = window_of(pool, prm)
+    lo, hi = _mask_maps(pool) if prm.get("maps") else band_of(pool, prm)
+    mode = mask_ref.OUTSIDE if prm.get("outside") else mask_ref.INSIDE
+    words, counts, boxes = mask_ref.expected(images_or_zero(pool, f0, n), x, y, rw, rh, lo, hi, mode, origins_of(pool, prm))
+    words, counts = words.view(np.int64), counts.view(np.int32).copy()
+    for k in range(n):
+        if not pool.ok[f0 + k]:
+            words[k], counts[k], boxes[k] = FILLS["int64"], 0, (rw, rh, -1, -1)
+    want = dict(words=words, counts=counts, results=rows_array(pool.rows[f0:f0 + n]))
+    if prm.get("boxes"):
+        want["boxes"] = boxes
+    return want
+
+
+# decode_patches -------------------------------------------------------------------------------------------------------
+def _patch_fill(pool, prm):
+    return prm.get("fill", 0) & ((1 << pool.bits) - 1)
+
+
+def _patch_outputs(pool, prm):
+    f0, n = frames_of(pool, prm)
+    pw, ph = PATCH
+    K = PATCHES_PER_FRAME
+    return dict(out=((n, K, ph, pw), pix_dtype(pool.bits)), used=((n, K, 2), "int32"), **results_spec(n))
+
+
+def _patch_run(codec, pool, prm, out):
+    dv = dvm()
+    buf, lead, total, offs, W, H, n = stream_args(pool, prm)
+    pw, ph = PATCH
+    org, cnt = _patch_inputs(pool, prm)
+    fn = "decode_patches" if pool.bits == 8 else "decode_patches16"
+    if n == 0:     # (the wrapper would hand the call the address of an empty origins tensor: none)
+        rc = getattr(codec.L, ("dbde_hip_" if pool.bits == 8 else "dbde16_hip_") + "decode_patches")(
+            codec.h, buf.data_ptr() + lead, total, offs.data_ptr(), W, H, 0, pw, ph, PATCHES_PER_FRAME, org.data_ptr(),
+            cnt.data_ptr() if cnt is not None else None, dv.patch_edge_mode(prm.get("edge", "clamp")), _patch_fill(pool, prm),
+            out["out"].t.data_ptr(), out["used"].t.data_ptr(), None)
+        return codec._check(rc, fn)
+    getattr(codec, fn)(buf, lead, total, offs, W, H, n, pw, ph, org, counts=cnt, edge=prm.get("edge", "clamp"),
+                       fill=_patch_fill(pool, prm), out=out["out"].t, used=out["used"].t, results=out["results"].t)
+
+
+def _patch_expect(pool, prm):
+    import patch_ref
+    f0, n = frames_of(pool, prm)
+    pw, ph = PATCH
+    px = pix_dtype(pool.bits)
+    mode = patch_ref.CLAMP if prm.get("edge", "clamp") == "clamp" else patch_ref.FILL
+    got, used, live = patch_ref.expected(images_or_none(pool, f0, n), pool.W, pool.H, pw, ph, patch_origins_of(pool, prm),
+                                         patch_counts_of(pool, prm), mode, _patch_fill(pool, prm),
+                                         untouched=FILLS[px] & ((1 << pool.bits) - 1),
+                                         dtype=np.uint8 if pool.bits == 8 else np.uint16)
+    used[~live] = FILLS["int32"]
+    return dict(out=as_pix(got, pool.bits), used=used, results=rows_array(pool.rows[f0:f0 + n]))
+
+
+def _patch_plan(fn8, fn16):
+    def plan(pool, prm):
+        dv = dvm()
+        f0, n = frames_of(pool, prm)
+        pl = getattr(dv, fn8 if pool.bits == 8 else fn16)(pool.W, pool.H, n, *PATCH, PATCHES_PER_FRAME, prm.get("edge", "clamp"))
+        pl["index"] = index_of_roi_plan(pool.bits, n, pl)
+        return pl
+    return plan
+
+
+# patch_moments --------------------------------------------------------------------------------------------------------
+def _mom_outputs(pool, prm):
+    f0, n = frames_of(pool, prm)
+    K = PATCHES_PER_FRAME
+    spec = dict(moments=((n, K, 8), "int64"), used=((n, K, 2), "int32"))
+    if prm.get("bbox"):
+        spec["boxes"] = ((n, K, 4), "int32")
+    return dict(spec, **results_spec(n))
+
+
+def _mom_run(codec, pool, prm, out):
+    buf, lead, total, offs, W, H, n = stream_args(pool, prm)
+    org, cnt = _patch_inputs(pool, prm)
+    lo, hi = band_of(pool, prm)
+    fn = codec.patch_moments if pool.bits == 8 else codec.patch_moments16
+    fn(buf, lead, total, offs, W, H, n, *PATCH, org if n else org[:0], lo, hi, weight=prm.get("weight", "above"), counts=cnt,
+       edge=prm.get("edge", "clamp"), out=out["moments"].t, bbox=out["boxes"].t if prm.get("bbox") else None,
+       used=out["used"].t, results=out["results"].t)
+
+
+def _mom_expect(pool, prm):
+    import moments_ref
+    import patch_ref
+    f0, n = frames_of(pool, prm)
+    lo, hi = band_of(pool, prm)
+    mode = patch_ref.CLAMP if prm.get("edge", "clamp") == "clamp" else patch_ref.FILL
+    mom, box, used, live = moments_ref.expected(images_or_none(pool, f0, n), pool.W, pool.H, *PATCH, patch_origins_of(pool, prm),
+                                                patch_counts_of(pool, prm), mode, lo, hi,
+                                                moments_ref.WEIGHTS.index(prm.get("weight", "above")))
+    mom[~live] = FILLS["int64"]
+    box[~live] = FILLS["int32"]
+    used[~live] = FILLS["int32"]
+    want = dict(moments=np.array(mom.tolist(), np.int64).reshape(n, PATCHES_PER_FRAME, 8), used=used.astype(np.int32),
+                results=rows_array(pool.rows[f0:f0 + n]))
+    if prm.get("bbox"):
+        want["boxes"] = box.astype(np.int32)
+    return want
+
+
+# project_weighted -----------------------------------------------------------------------------------------------------
+def _wp_weights(pool, prm):
+    """(R, pool.n) float32: the weights of the pool's frames (a step takes the columns of its own)."""
+    import wproject_gpu as wg
+    R = prm.get("R", 1)
+    return wg.family(np.random.default_rng(pool.n * 31 + R), "normal", R, pool.n)
+
+
+def _wp_weights_dev(pool, prm):
+    """The step's columns of the device weights: a view whose rows lie pool.n (strided: pool.n + 7, NaN between them)
+    apart; for a call without frames the column of one frame, which is never read."""
+    import torch
+    import wproject_gpu as wg
+    w = _wp_weights(pool, prm)
+    make = (lambda: wg.strided(w)) if prm.get("strided") else (lambda: torch.from_numpy(w).cuda())
+    dev = const(("weights", pool.n, prm.get("R", 1), bool(prm.get("strided"))), make)
+    f0, n = frames_of(pool, prm)
+    return dev[:, f0:f0 + max(n, 1)]
+
+
+def _wp_outputs(pool, prm):
+    f0, n = frames_of(pool, prm)
+    x, y, rw, rh = window_of(pool, prm)
+    return dict(out=((prm.get("R", 1), rh, rw), "int32"), count=((1,), "int64"), **results_spec(n))
+
+
+def _wp_run(codec, pool, prm, out):
+    import torch
+    dv = dvm()
+    fn = codec.project_weighted if pool.bits == 8 else codec.project_weighted16
+    fn(*stream_args(pool, prm), _wp_weights_dev(pool, prm), *window_of(pool, prm),
+       out=dv.WeightedProjection(out["out"].t.view(torch.float32), out["count"].t), accumulate=continues(prm),
+       one_segment=bool(prm.get("one")), results=out["results"].t)
+
+
+def _wp_plan_for(pool, prm, n, n_cu):
+    dv = dvm()
+    x, y, rw, rh = window_of(pool, prm)
+    fn = dv.wproject_plan if pool.bits == 8 else dv.wproject16_plan
+    stride = (pool.n + 7 if prm.get("strided") else pool.n) if prm.get("R", 1) > 1 else max(n, 1)
+    return fn(pool.W, pool.H, n, x, y, rw, rh, regressors=prm.get("R", 1), n_cu=n_cu, one_segment=bool(prm.get("one")),
+              weight_stride=stride)
+
+
+def _wp_expect(pool, prm):
+    """The defined value (include/dbde_hip.h) as wproject_ref computes it, bit for bit: per call the chain of fused
+    multiply-adds of every segment the plan reports for this device, the partials added in order -- and, in a
+    continuation, added to what the parts before left, each part by its own plan."""
+    import wproject_ref as wr
+    f0, n = frames_of(pool, prm)
+    x, y, rw, rh = window_of(pool, prm)
+    w = _wp_weights(pool, prm)
+    value, count = None, 0
+    for a, m in parts_of(prm, f0, n):
+        pl = _wp_plan_for(pool, prm, m, device_cus()) if m else dict(segments=1, frames_per_segment=0)
+        value, c = wr.wproject(images_or_none(pool, a, m), w[:, a:a + m], x, y, rw, rh, segments=pl["segments"],
+                               fps=pl["frames_per_segment"], accumulate=value is not None, prior=value)
+        count += c
+    return dict(out=wr.bits(value), count=np.array([count], np.int64), results=rows_array(pool.rows[f0:f0 + n]))
+
+
+def _wp_plan(pool, prm):
+    f0, n = frames_of(pool, prm)
+    pl = _wp_plan_for(pool, prm, n, 256)
+    pl["index"] = index_of_roi_plan(pool.bits, n, pl)
+    return pl
+
+
+for _b in (8, 16):
+    _s = suffix(_b)
+    OPS["project_groups" + _s] = Op("project_groups" + _s, _b, "consumer", _grp_run, _grp_expect, _grp_plan, _grp_outputs,
+                                    prepare=lambda codec, pool, prm: _grp_starts_dev(pool, prm))
+    OPS["decode_mask" + _s] = Op("decode_mask" + _s, _b, "consumer", _mask_run, _mask_expect,
+                                 roi_family_plan("mask_plan", "mask16_plan"), _mask_outputs,
+                                 prepare=lambda codec, pool, prm: (origins_dev(pool, prm),
+                                                                   _mask_maps_dev(pool) if prm.get("maps") else None))
+    OPS["decode_patches" + _s] = Op("decode_patches" + _s, _b, "consumer", _patch_run, _patch_expect,
+                                    _patch_plan("patches_plan", "patches16_plan"), _patch_outputs,
+                                    prepare=lambda codec, pool, prm: _patch_inputs(pool, prm))
+    OPS["project_weighted" + _s] = Op("project_weighted" + _s, _b, "consumer", _wp_run, _wp_expect, _wp_plan, _wp_outputs,
+                                      prepare=lambda codec, pool, prm: _wp_weights_dev(pool, prm))
+    OPS["patch_moments" + _s] = Op("patch_moments" + _s, _b, "consumer", _mom_run, _mom_expect,
+                                   _patch_plan("patch_moments_plan", "patch_moments16_plan"), _mom_outputs,
+                                   prepare=lambda codec, pool, prm: _patch_inputs(pool, prm))
+
+
 # ---- interveners: a call with no frames, for every consumer --------------------------------------------------------
 def _zero_op(base):
     """The consumer `base` with n_frames = 0 (an empty tensor has no address, so the call is handed the buffers of one
-    frame): it returns at once and writes nothing -- but for project and histogram, which, not accumulating, write
-    their empty result: max 0, min the top value, sums, totals and counts 0."""
+    frame): it returns at once and writes nothing -- but for project, project_weighted and histogram, which, not
+    accumulating, write their empty result: max 0, min the top value, sums, planes, totals and counts 0."""
     zero = lambda prm: dict(prm, n=0, f0=0)    # noqa: E731
     one = lambda prm: dict(prm, n=1, f0=0)     # noqa: E731
-    written = {"project": ALL4 + ("count",), "histogram": ("total", "count")}.get(base.name.replace("16", ""), ())
+    written = {"project": ALL4 + ("count",), "histogram": ("total", "count"),
+               "project_weighted": ("out", "count")}.get(base.name.replace("16", ""), ())
 
     def expect(pool, prm):
         want = {k: filled(v[0], v[1]) for k, v in base.outputs(pool, one(prm)).items()}
@@ -823,6 +1245,55 @@ OPS["err:crop_capacity"] = Op("err:crop_capacity", 8, "err:crop_capacity", _err_
 _err_proj_outputs = lambda pool, prm: dict(count=((1,), "int64"), **results_spec(frames_of(pool, prm)[1]))   # noqa: E731
 OPS["err:project_no_statistic"] = Op("err:project_no_statistic", 8, "err:project_no_statistic", _err_project_run,
                                      _untouched(_err_proj_outputs), _no_plan, _err_proj_outputs, raises=True)
+
+
+# one per newer family: what the family's own argument-error test establishes as DBDE_HIP_ERR_ARG of the C call itself
+def _err_groups_run(codec, pool, prm, out):
+    """U16 sums cannot be continued."""
+    dv = dvm()
+    codec.project_groups(*stream_args(pool, prm), *window_of(pool, prm), group_frames=prm["g"], accumulate=True,
+                         out=dv.GroupProjection(sum=out["sum"].t, counts=out["group_counts"].t), results=out["results"].t)
+
+
+def _err_mask_run(codec, pool, prm, out):
+    """No output requested (the wrapper refuses that by itself: the C call is made directly)."""
+    buf, lead, total, offs, W, H, n = stream_args(pool, prm)
+    lo, hi = band_of(pool, prm)
+    rc = codec.L.dbde_hip_decode_mask(codec.h, buf.data_ptr() + lead, total, offs.data_ptr(), W, H, n, *window_of(pool, prm),
+                                      None, 0, None, lo, None, hi, None, None, None, out["results"].t.data_ptr())
+    codec._check(rc, "dbde_hip_decode_mask")
+
+
+def _err_patches_run(codec, pool, prm, out):
+    """An unknown edge mode."""
+    _patch_run(codec, pool, dict(prm, edge=2), out)
+
+
+def _err_weighted_run(codec, pool, prm, out):
+    """Nine regressors (the wrapper would make two calls of them: the C call is made directly)."""
+    buf, lead, total, offs, W, H, n = stream_args(pool, prm)
+    w = _wp_weights_dev(pool, prm)
+    rc = codec.L.dbde_hip_project_weighted(codec.h, buf.data_ptr() + lead, total, offs.data_ptr(), W, H, n,
+                                           *window_of(pool, prm), w.data_ptr(), 9, w.stride(0), 0, 0,
+                                           out["out"].t.data_ptr(), out["count"].t.data_ptr(), out["results"].t.data_ptr())
+    codec._check(rc, "dbde_hip_project_weighted")
+
+
+def _err_moments_run(codec, pool, prm, out):
+    """A patch of 513 rows in fill mode."""
+    buf, lead, total, offs, W, H, n = stream_args(pool, prm)
+    org, cnt = _patch_inputs(pool, prm)
+    codec.patch_moments(buf, lead, total, offs, W, H, n, PATCH[0], 513, org, *band_of(pool, prm), edge="fill",
+                        out=out["moments"].t, bbox=out["boxes"].t, used=out["used"].t, results=out["results"].t)
+
+
+for _name, _run, _outs, _prep in (
+        ("err:groups_u16_accumulate", _err_groups_run, _grp_outputs, None),
+        ("err:mask_no_output", _err_mask_run, _mask_outputs, None),
+        ("err:patches_edge_mode", _err_patches_run, _patch_outputs, lambda codec, pool, prm: _patch_inputs(pool, prm)),
+        ("err:weighted_nine_regressors", _err_weighted_run, _wp_outputs, lambda codec, pool, prm: _wp_weights_dev(pool, prm)),
+        ("err:moments_513_rows", _err_moments_run, _mom_outputs, lambda codec, pool, prm: _patch_inputs(pool, prm))):
+    OPS[_name] = Op(_name, 8, _name, _run, _untouched(_outs), _no_plan, _outs, prepare=_prep, raises=True)
 
 
 # ---- interveners: the encoders -------------------------------------------------------------------------------------

@@ -4,20 +4,29 @@ CHAINS maps a name to a list of steps (op, pool, params) over the ops and pools 
 touches a GPU: from the plan functions (the ones the entry points themselves call) and the pools alone, the tests below
 work out the state every step leaves in the context and the state every step meets, and require:
 
-  1. index state: each of the sixteen index consumers runs directly after a call that left chunk_off / frame_ok /
-     idx_ctr (a) written by the other pixel size, (b) by the split index where it runs unsplit, (c) the reverse, (d) for
-     more frames, (e) for fewer frames with both calls' 2n words inside one idx_ctr allocation (the earlier call's flag
-     words are this call's counters), (f) for another chunks_per_frame, (g) with a frame index rejected that is now
-     accepted, (h) the reverse; and every ordered pair of consumers is adjacent somewhere.  decode_frames16 never
-     splits its index (dbde16_hip_decode_frames passes 1), so (c) and (e) do not exist for it;
-  2. the same stale state with calls of other kinds in between, every intervener kind used;
+  1. index state: each of the 26 index consumers (sq.CONSUMERS: thirteen families, both pixel sizes) runs directly after
+     a call that left chunk_off / frame_ok / idx_ctr (a) written by the other pixel size, (b) by the split index where it
+     runs unsplit, (c) the reverse, (d) for more frames, (e) for fewer frames with both calls' 2n words inside one
+     idx_ctr allocation (the earlier call's flag words are this call's counters), (f) for another chunks_per_frame, (g)
+     with a frame index rejected that is now accepted, (h) the reverse; and every ordered pair of consumers, 676 of
+     them, is adjacent somewhere: the 256 pairs of the first sixteen in the de Bruijn walk, the 420 with one of the ten
+     newer consumers in them in an Euler circuit cut into two chains.  decode_frames16 never splits its index
+     (dbde16_hip_decode_frames passes 1), so (c) and (e) do not exist for it; all eight exist for every other consumer;
+  2. the same stale state with calls of other kinds in between, for every consumer, every intervener kind used (a call
+     without frames of every consumer and a call that fails after validation of every family that has one among them);
   3. every ordered pair of encoder forms adjacent; persistent -> an odd number of small launches -> persistent; a launch
      that makes the look-back block grow, and one with fewer chunks than the one before it;
   4. the fused decoder's records: growth, a smaller launch after it, another form in between, three of one shape;
   5. projection partials: segments > 1 -> 1 -> > 1, a change of the statistics between two segmented calls, traces and
-     projections after each other, traces at two label counts and two batch sizes;
-  6. continuations: project, project16, histogram and histogram16 totals in three accumulate=True parts each with at
-     least three other families between the parts;
+     projections after each other, traces at two label counts and two batch sizes; and for project_weighted, whose F32
+     partials lie in the same workspace, per pixel size: segments > 1 -> 1 -> > 1, two adjacent segmented calls with
+     another number of regressors and other workspace_bytes, a segmented project of all four statistics directly
+     before and directly after a segmented project_weighted of other workspace_bytes, traces directly before and after
+     it (project_groups has no workspace);
+  6. continuations: project, project16, histogram, histogram16, project_groups, project_groups16, project_weighted and
+     project_weighted16 over a whole pool in three accumulate=True parts each with at least three other families
+     between the parts (the weighted expectation is the header's defined value applied part by part, which may differ
+     from the one-call value in the last bits: chain_continuations_new);
   7. the stream walks in the order speculative, hop by hop, speculative cut by max_frames, garbage tail, truncated
      tail, speculative again;
   8. every step is accepted by its plan function, the pools have the plan properties they exist for, no chain is
@@ -69,6 +78,15 @@ def variant(op, v):
         "decode_binned": [dict(bin=4), dict(w=1, bin=8), dict(w=1, bin=2)],
         "decode_scaled": [dict(type="f32"), dict(w=1, type="bf16", org=True), dict(type="f16")],
         "crop_frames": [dict(w=1), dict(w=1, org=True, slots=True)],
+        "project_groups": [dict(g=4), dict(w=1, g=5, stats=("max", "sum"), sum16=b == 8),
+                           dict(w=1, starts=sq.GROUP_STARTS, stats=("min", "sum", "sumsq"))],
+        "decode_mask": [dict(band="mid"), dict(w=1, maps=True, outside=True, org=True, boxes=True),
+                        dict(w=1, band="tile", org=True, boxes=True)],
+        "decode_patches": [dict(edge="clamp"), dict(edge="fill", fill=0x1A5, counts=True)],
+        "project_weighted": [dict(R=1), dict(w=1, R=3, strided=True), dict(w=1, R=8, one=True)],
+        "patch_moments": [dict(edge="clamp", weight="above", band="tile", bbox=True),
+                          dict(edge="fill", weight="value", band="empty", counts=True, bbox=True),
+                          dict(edge="fill", weight="count", band="mid", counts=True)],
     }[f]
     return dict(table[v % len(table)])
 
@@ -101,6 +119,8 @@ def intervener_pool(op):
         return ("Esplit" if base == "decode_frames" else "A" + str(bits_of(op)))
     return {"decode_self": "Eself", "decode_fused": "Efused", "decode_mid": "Emid", "err:window": "A8",
             "err:crop_capacity": "A8", "err:project_no_statistic": "A8", "err:encode_capacity": "small",
+            "err:groups_u16_accumulate": "A8", "err:mask_no_output": "A8", "err:patches_edge_mode": "A8",
+            "err:weighted_nine_regressors": "A8", "err:moments_513_rows": "A8",
             "index_stream": "Fplain", "scan_ahead": "Fplain", "file": "window"}.get(
         op, op[7:] if op.startswith("encode:") else "host")
 
@@ -110,15 +130,17 @@ def intervener_step(op, **prm):
         prm = dict(variant(op[5:], 0), **prm)
     if op == "err:crop_capacity":
         prm = dict(w=1, **prm)
+    prm = dict({"err:groups_u16_accumulate": dict(g=4, stats=("sum",), sum16=True), "err:weighted_nine_regressors": dict(R=9),
+                "err:moments_513_rows": dict(bbox=True)}.get(op, {}), **prm)
     return (op, intervener_pool(op), prm)
 
 
 # ---- the chains --------------------------------------------------------------------------------------------------------
 
-def chain_relations():
+def chain_relations(consumers=sq.OLD_CONSUMERS):
     """For every consumer B, the pairs (stale-making call, B) that give each relation of condition 1."""
     steps = []
-    for k, B in enumerate(sq.CONSUMERS):
+    for k, B in enumerate(consumers):
         b = bits_of(B)
         o = 24 - b
         roi, roi_o = ("decode_roi", "decode_roi16") if b == 8 else ("decode_roi16", "decode_roi")
@@ -150,12 +172,15 @@ def chain_relations():
 def chain_walk():
     """A de Bruijn walk over the sixteen consumers (every ordered pair adjacent once: 257 steps), pools and parameter
     sets drawn with a seeded generator."""
-    rng = np.random.default_rng(257)
-    seq = de_bruijn(len(sq.CONSUMERS))
-    seq = seq + seq[:1]
+    seq = de_bruijn(len(sq.OLD_CONSUMERS))
+    return drawn_steps([sq.OLD_CONSUMERS[c] for c in seq + seq[:1]], seed=257)
+
+
+def drawn_steps(ops, seed):
+    """The consumers `ops` in order, pools and parameter sets drawn with a seeded generator."""
+    rng = np.random.default_rng(seed)
     steps = []
-    for c in seq:
-        op = sq.CONSUMERS[c]
+    for op in ops:
         b = bits_of(op)
         if op == "decode_frames":
             pool, more = [("Esplit", {}), ("Etable", {}), ("Esplit", dict(f0=4))][int(rng.integers(0, 3))]
@@ -166,6 +191,31 @@ def chain_walk():
                           (f"C{b}", dict(n=13))][int(rng.integers(0, 7))]
         steps.append(consumer_step(op, pool, int(rng.integers(0, 3)), **more))
     return steps
+
+
+def new_pairs_circuit():
+    """A closed walk over the 26 consumers in which every ordered pair with one of the ten newer consumers in it -- the
+    420 pairs the de Bruijn walk over the first sixteen does not have -- is adjacent exactly once: an Euler circuit of
+    the graph of those pairs (every newer consumer has 26 edges in and 26 out, every older one 10 and 10), by
+    Hierholzer's algorithm in a fixed order.  421 entries."""
+    new = set(sq.NEW_CONSUMERS)
+    todo = {a: [b for b in reversed(sq.CONSUMERS) if a in new or b in new] for a in sq.CONSUMERS}
+    stack, circuit = [sq.NEW_CONSUMERS[0]], []
+    while stack:
+        if todo[stack[-1]]:
+            stack.append(todo[stack[-1]].pop())
+        else:
+            circuit.append(stack.pop())
+    circuit.reverse()
+    assert len(circuit) == 421 and len(set(zip(circuit, circuit[1:]))) == 420
+    return circuit
+
+
+def chain_walk_new(half):
+    """One half of new_pairs_circuit (the halves share the step between them: 211 steps each), pools and parameter sets
+    drawn as the walk draws its own."""
+    ops = new_pairs_circuit()
+    return drawn_steps(ops[:211] if half == 0 else ops[210:], seed=421 + half)
 
 
 def intervener_kinds_in_order():
@@ -222,8 +272,16 @@ def chain_partials():
                   (P, C, dict(w=1, stats=("min", "sumsq"))), (T, C, dict(labels="few")), (P, C, {}),
                   (T, C, dict(labels="many", n=13)), (T, A, dict(labels="few")), (P, C, dict(stats=("sum",))),
                   (T, C, dict(labels="many"))]
-    return steps + [("project", "C8", {}), ("project16", "C16", {}), ("project", "C8", dict(stats=("sumsq",))),
-                    ("traces16", "C16", dict(labels="few")), ("traces", "C8", dict(labels="few"))]
+    steps += [("project", "C8", {}), ("project16", "C16", {}), ("project", "C8", dict(stats=("sumsq",))),
+              ("traces16", "C16", dict(labels="few")), ("traces", "C8", dict(labels="few"))]
+    # the weighted projections' F32 partials lie in the same workspace
+    for b in (8, 16):
+        s = "" if b == 8 else "16"
+        P, T, V, C = "project" + s, "traces" + s, "project_weighted" + s, f"C{b}"
+        steps += [(V, C, dict(R=3, strided=True)), (V, C, dict(R=8, one=True)), (V, C, dict(R=8)), (V, C, dict(R=1)),
+                  (V, C, dict(n=13, R=3)), (V, C, dict(w=1, R=3)), (P, C, {}), (V, C, dict(R=3, strided=True)), (P, C, {}),
+                  (T, C, dict(labels="few")), (V, C, dict(w=1, R=8)), (T, C, dict(labels="many"))]
+    return steps
 
 
 def chain_continuations():
@@ -245,6 +303,32 @@ def chain_continuations():
     return steps
 
 
+def chain_continuations_new():
+    """The grouped and the weighted projections over a whole pool in three accumulate=True parts each, calls of other
+    families between the parts.  The grouped planes are exact integers: the third part's value is the one-call
+    reference (sq._grp_expect asserts that the parts add up to it).  The weighted planes are F32 sums whose defined
+    value (include/dbde_hip.h) is ((prior + P_0) + P_1) + ... per call, each call cut into the segments of its own
+    plan: three parts round at other places than one call does, so their value may differ from the one-call value in
+    the last bits, and the expectation is the definition applied part by part (sq._wp_expect), not the one-call value."""
+    cuts = {"C": (0, 100, 200, 300), "A": (0, 4, 9, 13)}
+    conts = [("project_groups", "A8", "A", dict(starts=sq.GROUP_STARTS)), ("project_weighted", "C8", "C", dict(w=1, R=3)),
+             ("project_groups16", "A16", "A", dict(w=1, starts=sq.GROUP_STARTS, stats=("max", "sum"))),
+             ("project_weighted16", "C16", "C", dict(w=1, R=8, strided=True))]
+    between = [[consumer_step("decode_mask", "D8", 1), consumer_step("patch_moments16", "A16", 0),
+                consumer_step("decode_roi16", "B16", 1), consumer_step("decode_patches", "Ar8", 1)],
+               [consumer_step("patch_moments", "C8", 1, n=13), consumer_step("traces16", "A16", 0),
+                consumer_step("decode_patches16", "D16", 0), consumer_step("histogram", "A8", 0),
+                consumer_step("decode_mask16", "Ar16", 2)],
+               []]
+    steps = []
+    for part in range(3):
+        for op, pool, cut, prm in conts:
+            c = cuts[cut]
+            steps.append((op, pool, dict(prm, acc=op, acc_from=0, cuts=c, f0=c[part], n=c[part + 1] - c[part])))
+        steps += between[part]
+    return steps
+
+
 def chain_scan():
     w = lambda pool, **prm: ("index_stream", pool, prm)   # noqa: E731
     return [w("Fplain"), w("Fshort"), w("Fplain", max_frames=17), w("Fgarbage"), w("Ftruncated"), w("Fplain"),
@@ -253,7 +337,9 @@ def chain_scan():
 
 CHAINS = {"relations": chain_relations(), "walk": chain_walk(), "interveners": chain_interveners(),
           "encoders": chain_encoders(), "fused": chain_fused(), "partials": chain_partials(),
-          "continuations": chain_continuations(), "scan": chain_scan()}
+          "continuations": chain_continuations(), "scan": chain_scan(),
+          "relations_new": chain_relations(sq.NEW_CONSUMERS[4:5] + sq.NEW_CONSUMERS[:4] + sq.NEW_CONSUMERS[5:]),
+          "walk_new1": chain_walk_new(0), "walk_new2": chain_walk_new(1), "continuations_new": chain_continuations_new()}
 # the chains that make an encoder, fused or small-encode call: the ones the experiment contexts differ on
 EXPERIMENT_CHAINS = tuple(name for name, steps in CHAINS.items()
                           if any(op.startswith(("encode:", "decode_fused", "file", "host:pack_frame")) for op, _, _ in steps))
@@ -261,8 +347,20 @@ EXPERIMENT_CHAINS = tuple(name for name, steps in CHAINS.items()
 
 # ---- what the steps leave and meet ---------------------------------------------------------------------------------
 
+_plans = {}
+
+
+def plan_of(things, step):
+    """The step's plan (worked out once per distinct step: the tests below ask for it many times over)."""
+    k = sq.key_of(step)
+    if k not in _plans:
+        op, pool, prm = step
+        _plans[k] = sq.OPS[op].plan(things[pool], prm)
+    return _plans[k]
+
+
 def plans(things, steps):
-    return [sq.OPS[op].plan(things[pool], prm) for op, pool, prm in steps]
+    return [plan_of(things, step) for step in steps]
 
 
 def index_launches(things, steps):
@@ -441,6 +539,27 @@ def test_partials(things):
                 seen.add((b, "project after traces"))
             if (f0, f1) == ("project", "traces") and bits_of(op0) == b:
                 seen.add((b, "traces after project"))
+            if bits_of(op0) == b and "project_weighted" in (f0, f1):
+                s0, s1 = pls[i - 1].get("segments"), pls[i].get("segments")
+                w0, w1 = pls[i - 1].get("workspace_bytes"), pls[i].get("workspace_bytes")
+                if f0 == f1:
+                    if s0 > 1 and s1 == 1:
+                        seen.add((b, "weighted: segments > 1 then 1"))
+                    if s0 == 1 and s1 > 1:
+                        seen.add((b, "weighted: segments 1 then > 1"))
+                    if s0 > 1 and s1 == 1 and prm1.get("one") and pls[i]["index"]["n"] == pls[i - 1]["index"]["n"]:
+                        seen.add((b, "weighted: one_segment=True directly after a segmented call of as many frames"))
+                    if s0 == 1 and s1 > 1 and prm0.get("one") and pls[i]["index"]["n"] == pls[i - 1]["index"]["n"]:
+                        seen.add((b, "weighted: a segmented call directly after one_segment=True of as many frames"))
+                    if s0 > 1 and s1 > 1 and pls[i - 1]["regressors"] != pls[i]["regressors"] and w0 != w1:
+                        seen.add((b, "weighted: the regressors change between two segmented calls"))
+                elif "project" in (f0, f1):
+                    stats = (prm0 if f0 == "project" else prm1).get("stats", sq.ALL4)
+                    if s0 > 1 and s1 > 1 and w0 != w1 and set(stats) == set(sq.ALL4):
+                        seen.add((b, "weighted: segmented, directly after a segmented project of all four statistics"
+                                  if f0 == "project" else "weighted: segmented, directly before a segmented project of all four statistics"))
+                elif "traces" in (f0, f1):
+                    seen.add((b, "weighted: after traces" if f0 == "traces" else "weighted: before traces"))
         for (op, pool, prm), pl in zip(steps, pls):
             if family(op) == "traces":
                 seen.add((bits_of(op), "labels", pl["n_labels"]))
@@ -448,7 +567,13 @@ def test_partials(things):
     missing = []
     for b in (8, 16):
         for what in ("segments > 1 then 1", "segments 1 then > 1", "statistics change between two segmented calls",
-                     "project after traces", "traces after project"):
+                     "project after traces", "traces after project", "weighted: segments > 1 then 1",
+                     "weighted: segments 1 then > 1", "weighted: the regressors change between two segmented calls",
+                     "weighted: one_segment=True directly after a segmented call of as many frames",
+                     "weighted: a segmented call directly after one_segment=True of as many frames",
+                     "weighted: segmented, directly after a segmented project of all four statistics",
+                     "weighted: segmented, directly before a segmented project of all four statistics",
+                     "weighted: after traces", "weighted: before traces"):
             if (b, what) not in seen:
                 missing.append(f"{b}-bit: {what}")
         for what in ("labels", "frames"):
@@ -459,7 +584,8 @@ def test_partials(things):
 
 def test_continuations(things):
     missing = []
-    for want in ("project", "project16", "histogram", "histogram16"):
+    for want in ("project", "project16", "histogram", "histogram16", "project_groups", "project_groups16",
+                 "project_weighted", "project_weighted16"):
         found = False
         for name, steps in CHAINS.items():
             parts = [i for i, (op, _, prm) in enumerate(steps) if op == want and prm.get("acc") is not None]

@@ -50,23 +50,30 @@ def test_chain_on_one_context(dv, things, tmp_path, chain, ctx, mode):
 
 
 def test_the_runner_sees_one_wrong_element(dv, things):
-    """One element of one step's expectation changed: the chain fails at that step, in both modes, and the fresh
-    context -- which cannot match the wrong expectation either -- is reported as mismatching too."""
-    steps = CHAINS["relations"][:4]
-    codec = _codec(dv)
-    try:
-        sq.run_chain(codec, things, "pristine", steps, "stepwise")
-        want = sq.expected_dev(things, steps[3])
-        name = next(k for k in want if k != "results")
-        kept = want[name]
-        want[name] = kept.clone()
-        want[name].view(-1)[-1] += 1
+    """One element of one step's expectation changed: the chain fails at that step, in both modes with the same
+    message, and the fresh context -- which cannot match the wrong expectation either -- is reported as mismatching
+    too.  Two prefixes: the second ends in a patch_moments step, and the element is one of one moments entry."""
+    for chain, output in (("relations", None), ("relations_new", "moments")):
+        steps = CHAINS[chain][:4]
+        assert output is None or steps[3][0] == "patch_moments"
+        codec = _codec(dv)
         try:
-            for mode in ("stepwise", "queued"):
-                with pytest.raises(AssertionError, match=r"step 3 .* after .*first differing element.*ALSO mismatches"):
-                    sq.run_chain(codec, things, "one wrong element", steps, mode)
+            sq.run_chain(codec, things, "pristine", steps, "stepwise")
+            want = sq.expected_dev(things, steps[3])
+            name = output or next(k for k in want if k != "results")
+            kept = want[name]
+            want[name] = kept.clone()
+            want[name].view(-1)[-1] += 1
+            try:
+                said = []
+                for mode in ("stepwise", "queued"):
+                    with pytest.raises(AssertionError, match=r"step 3 .* after .*first differing element.*ALSO mismatches") as e:
+                        sq.run_chain(codec, things, "one wrong element", steps, mode)
+                    said.append(str(e.value).replace(f"({mode})", "(mode)"))
+                assert said[0] == said[1], said
+                assert output is None or f"{output}: first differing element" in said[0], said[0]
+            finally:
+                want[name] = kept
+            sq.run_chain(codec, things, "restored", steps, "queued")
         finally:
-            want[name] = kept
-        sq.run_chain(codec, things, "restored", steps, "queued")
-    finally:
-        codec.close()
+            codec.close()
