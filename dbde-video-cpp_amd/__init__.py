@@ -73,6 +73,8 @@ C_ABI_SYMBOLS = [
     "dbde16_hip_project_groups_plan",
     "dbde_hip_project_weighted", "dbde16_hip_project_weighted", "dbde_hip_project_weighted_plan",
     "dbde16_hip_project_weighted_plan",
+    "dbde_hip_project_counts", "dbde16_hip_project_counts", "dbde_hip_project_counts_plan",
+    "dbde16_hip_project_counts_plan",
 ]
 
 
@@ -207,6 +209,12 @@ def lib():
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_project_weighted_plan", "dbde16_hip_project_weighted_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, u64, i, u64, u64, u64, i, C.POINTER(WeightedProjectPlan)]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_project_counts", "dbde16_hip_project_counts"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, i, sz, i, i, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_project_counts_plan", "dbde16_hip_project_counts_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, u64, i, u64, u64, u64, i, C.POINTER(CountProjectPlan)]
         getattr(L, fn).restype = i
     L.dbde_hip_trace_map_summary.argtypes = [vp, i, i, i, C.POINTER(TraceMapInfo), vp]
     L.dbde_hip_trace_map_summary.restype = i
@@ -818,6 +826,78 @@ class WeightedProjection:
         ok = accepted_frames(results).to(w.device)
         w64 = w[:, :n].to(torch.float64)
         return torch.where(ok.view(1, -1), w64, torch.zeros_like(w64)).sum(1)
+
+
+COUNTS_MAX_LEVELS = 8
+COUNTS_MAPS = 1
+
+
+class CountProjectPlan(C.Structure):
+    """dbde_hip_project_counts_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32),
+                ("index_split", C.c_uint32), ("threads", C.c_uint32), ("pieces_x", C.c_uint32),
+                ("segments", C.c_uint32), ("frames_per_segment", C.c_uint32), ("max_frames_per_segment", C.c_uint32),
+                ("levels", C.c_uint32), ("grid", C.c_uint64), ("combine_grid", C.c_uint64),
+                ("workspace_bytes", C.c_uint64), ("lds_bytes", C.c_uint32), ("reserved_", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved_"}
+
+
+def _counts_plan(fn, W, H, n_frames, x, y, rw, rh, levels, n_cu, maps, level_stride, addresses):
+    """counts_plan / counts16_plan through the C function named fn."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    addr = {"thresholds": 4096, "out": 4096, "count": 4096}
+    addr.update(addresses or {})
+    flags = maps if isinstance(maps, int) and not isinstance(maps, bool) else (COUNTS_MAPS if maps else 0)
+    stride = max(rw, 0) * max(rh, 0) if level_stride is None else level_stride
+    pl = CountProjectPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, x, y, rw, rh, levels, stride, flags, addr["thresholds"], addr["out"],
+                            addr["count"], n_cu, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, K={levels}, stride={stride}, "
+                         f"flags={flags}) -> {rc}")
+    return pl.as_dict()
+
+
+def counts_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, levels=1, n_cu=256, maps=False, level_stride=None,
+                addresses=None):
+    """dbde_hip_project_counts_plan: the tile window, index geometry, launch, segments and workspace of a count
+    projection (host arithmetic only).  rw / rh default to the rest of the frame, level_stride to rw * rh.  maps: True /
+    False (or an int: the raw flags).  addresses: optional {"thresholds" | "out" | "count": address} standing for the
+    call's pointers (0 = NULL; aligned by default).  Raises ValueError where dbde_hip_project_counts would return
+    DBDE_HIP_ERR_ARG."""
+    return _counts_plan("dbde_hip_project_counts_plan", W, H, n_frames, x, y, rw, rh, levels, n_cu, maps, level_stride,
+                        addresses)
+
+
+def counts16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, levels=1, n_cu=256, maps=False, level_stride=None,
+                  addresses=None):
+    """dbde16_hip_project_counts_plan: counts_plan for DBDE16 streams (Codec.project_counts16)."""
+    return _counts_plan("dbde16_hip_project_counts_plan", W, H, n_frames, x, y, rw, rh, levels, n_cu, maps,
+                        level_stride, addresses)
+
+
+class CountProjection:
+    """Device tensors of a count projection (Codec.project_counts): out int32 (K, rh, rw), plane k holding the number of
+    accepted frames whose pixel is <= threshold k (U32 bits: exact below 2^31 frames); count int64 (1,), the frames that
+    contributed."""
+
+    def __init__(self, out=None, count=None):
+        self.out, self.count = out, count
+
+    @classmethod
+    def empty(cls, K, rh, rw, device):
+        """Uninitialised planes and a zero count."""
+        return cls(torch.empty((K, rh, rw), dtype=torch.int32, device=device),
+                   torch.zeros(1, dtype=torch.int64, device=device))
+
+    def fraction(self):
+        """out / count in float64 (K, rh, rw): the fraction of the accepted frames at or below each threshold (NaN where
+        no frame was accepted)."""
+        return self.out.to(torch.float64) / self.count.to(torch.float64)
 
 
 class TraceMapInfo(C.Structure):
@@ -1715,6 +1795,74 @@ class Codec:
         """project_weighted for DBDE16 streams (U16 pixels; every one is exact in float32)."""
         return self._project_weighted("dbde16_hip_project_weighted", stream, stream_offset, stream_bytes, offsets, W, H,
                                       n, weights, x, y, rw, rh, out, accumulate, one_segment, results)
+
+    def _project_counts(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, thresholds, x, y, rw, rh,
+                        out, accumulate, results):
+        """project_counts / project_counts16 through the C function named fn; pix: bytes per pixel and threshold."""
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        dtype = torch.uint8 if pix == 1 else torch.int16
+        if not torch.is_tensor(thresholds):
+            t = np.atleast_1d(np.asarray(thresholds, dtype=np.int64))
+            if t.ndim != 1 or t.size < 1 or t.min() < 0 or t.max() >= 1 << (8 * pix):
+                raise ValueError(f"scalar thresholds must be one or more ints in [0, {(1 << (8 * pix)) - 1}]")
+            t = t.astype(np.uint8) if pix == 1 else t.astype(np.uint16).view(np.int16)
+            thresholds = torch.as_tensor(t, device=self.device)
+        if thresholds.dtype != dtype or not thresholds.is_cuda or thresholds.dim() not in (1, 3):
+            raise ValueError(f"thresholds must be ints or a {dtype} device tensor (K,) or (K, rh, rw)")
+        maps = thresholds.dim() == 3
+        K = thresholds.shape[0]
+        if K < 1:
+            raise ValueError("thresholds need at least one level")
+        if maps:
+            if tuple(thresholds.shape[1:]) != (rh, rw) or not thresholds[0].is_contiguous() or (
+                    K > 1 and thresholds.stride(0) < rw * rh):
+                raise ValueError(f"threshold maps must be (K, {rh}, {rw}) with contiguous levels (a slice along the "
+                                 "level axis is fine)")
+        elif K > 1 and thresholds.stride(0) != 1:
+            raise ValueError("scalar thresholds must have unit stride")
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out= (the projection to continue)")
+            out = CountProjection.empty(K, rh, rw, self.device)
+        if tuple(out.out.shape) != (K, rh, rw) or out.out.dtype != torch.int32 or not out.out.is_contiguous():
+            raise ValueError(f"out.out must be a contiguous int32 tensor ({K}, {rh}, {rw})")
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        for k0 in range(0, K, COUNTS_MAX_LEVELS):   # more than 8 levels: successive calls (the index pass repeats)
+            lv = thresholds[k0: k0 + COUNTS_MAX_LEVELS]
+            stride = (lv.stride(0) if lv.shape[0] > 1 else rw * rh) if maps else 0
+            count = out.count
+            if k0 > 0:   # the frames are counted once: the later calls count into a spare that the output keeps alive
+                if getattr(out, "_spare_count", None) is None:
+                    out._spare_count = torch.zeros_like(out.count)
+                count = out._spare_count
+            rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                     W, H, n, x, y, rw, rh, lv.data_ptr(), lv.shape[0], stride,
+                                     1 if accumulate else 0, COUNTS_MAPS if maps else 0,
+                                     out.out[k0: k0 + lv.shape[0]].data_ptr(), count.data_ptr(),
+                                     results.data_ptr() if n > 0 else None)
+            self._check(rc, fn)
+        return out, results
+
+    def project_counts(self, stream, stream_offset, stream_bytes, offsets, W, H, n, thresholds, x=0, y=0, rw=None,
+                       rh=None, out=None, accumulate=False, results=None):
+        """Count projection of the rw x rh window at (x, y) over n frames: plane k is the number of accepted frames whose
+        pixel is <= threshold k (unsigned; include/dbde_hip.h).  thresholds: an int or a sequence of ints (uploaded as
+        scalars), a uint8 device tensor (K,) (scalars, nothing synchronises) or a uint8 device tensor (K, rh, rw) of
+        per-pixel maps in window coordinates; a map tensor may be a slice along the level axis of a wider one.  More than
+        8 levels are served by successive calls of at most 8 into slices of one output; the index pass then repeats once
+        per call and the frames are counted once.  out: a CountProjection to write into (accumulate=True adds to it: the
+        counts are exact integers, so any split of a run of frames gives the same planes).  Returns (CountProjection,
+        results (n, 4) int64)."""
+        return self._project_counts("dbde_hip_project_counts", 1, stream, stream_offset, stream_bytes, offsets, W, H, n,
+                                    thresholds, x, y, rw, rh, out, accumulate, results)
+
+    def project_counts16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, thresholds, x=0, y=0, rw=None,
+                         rh=None, out=None, accumulate=False, results=None):
+        """project_counts for DBDE16 streams: U16 pixels and thresholds, the tensors int16 holding the U16 bits."""
+        return self._project_counts("dbde16_hip_project_counts", 2, stream, stream_offset, stream_bytes, offsets, W, H,
+                                    n, thresholds, x, y, rw, rh, out, accumulate, results)
 
     def _project_groups(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, group_frames,
                         group_starts, stats, sum_dtype, accumulate, out, results):

@@ -16,6 +16,7 @@
 
 #include "dbde16_kernels.h"
 #include "dbde_binned_kernels.h"
+#include "dbde_counts_kernels.h"
 #include "dbde_crop_kernels.h"
 #include "dbde_gproject_kernels.h"
 #include "dbde_hist_kernels.h"
@@ -1256,6 +1257,147 @@ int dbde16_hip_project_weighted(dbde_hip_ctx *ctx, const uint8_t *d_stream, size
     return wproject_common(ctx, "project_weighted16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0,
                            y0, rw, rh, d_weights, n_regressors, weight_stride, accumulate, flags, d_out, d_count,
                            d_results);
+}
+
+// ---- count projections -------------------------------------------------------------------
+// The window, the index geometry and the segment rule are plan_project's (any statistics set gives the same segments).
+// The counts are integers, so the value does not depend on the segments.
+struct CountsPlan {
+    ProjectPlan proj;
+    uint32_t levels;
+};
+static const char *plan_counts(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int n_levels,
+                               uint64_t level_stride, int flags, uint64_t thresholds_address, uint64_t out_address,
+                               uint64_t count_address, int n_cu, uint32_t pix, CountsPlan &pl) {
+    if (const char *why = plan_project(W, H, n_frames, x0, y0, rw, rh, kProjSum, n_cu, pix, pl.proj)) return why;
+    if (n_levels < 1 || n_levels > (int)kCountsMaxLevels) return "n_levels outside 1..8";
+    if (flags & ~DBDE_HIP_COUNTS_MAPS) return "unknown flag bits";
+    if ((flags & DBDE_HIP_COUNTS_MAPS) && level_stride < (uint64_t)rw * (uint64_t)rh) return "level_stride < rw * rh";
+    if (!thresholds_address || !out_address || !count_address) return "null pointer";
+    if (thresholds_address & (pix - 1u)) return "U16 thresholds must be 2-byte aligned";
+    if (out_address & 3u) return "the U32 output must be 4-byte aligned";
+    if (count_address & 7u) return "the U64 count must be 8-byte aligned";
+    pl.levels = (uint32_t)n_levels;
+    pl.proj.workspace = counts_workspace_bytes(pl.levels, pl.proj.segments, (uint64_t)rw * (uint64_t)rh);
+    return nullptr;
+}
+
+static int counts_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int n_levels,
+                              uint64_t level_stride, int flags, uint64_t thresholds_address, uint64_t out_address,
+                              uint64_t count_address, int n_cu, uint32_t pix, dbde_hip_project_counts_plan_t *plan) {
+    CountsPlan pl;
+    if (!plan || plan_counts(W, H, n_frames, x0, y0, rw, rh, n_levels, level_stride, flags, thresholds_address,
+                             out_address, count_address, n_cu, pix, pl))
+        return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->tile_x = (int32_t)pl.proj.roi.tx0;
+    plan->tile_y = (int32_t)pl.proj.roi.ty0;
+    plan->tiles_x = (int32_t)pl.proj.roi.ntx;
+    plan->tiles_y = (int32_t)pl.proj.roi.nty;
+    plan->chunks_per_frame = pl.proj.roi.dg.cpf;
+    plan->chunk_tiles = pl.proj.roi.dg.ct;
+    plan->chunk_pieces = pl.proj.roi.dg.ct == pl.proj.roi.g.w || pl.proj.roi.dg.pieces > 1u ? pl.proj.roi.dg.pieces : 0u;
+    plan->index_split = pl.proj.roi.split;
+    plan->threads = kProjThreads;
+    plan->pieces_x = pl.proj.pieces;
+    plan->segments = pl.proj.segments;
+    plan->frames_per_segment = pl.proj.fps;
+    plan->max_frames_per_segment = kProjMaxFramesPerSegment;
+    plan->levels = pl.levels;
+    plan->grid = pl.proj.grid;
+    plan->combine_grid = pl.proj.combine_grid;
+    plan->workspace_bytes = pl.proj.workspace;
+    plan->lds_bytes = kCountsLdsBytes;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_project_counts_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int n_levels,
+                                 uint64_t level_stride, int flags, uint64_t thresholds_address, uint64_t out_address,
+                                 uint64_t count_address, int n_cu, dbde_hip_project_counts_plan_t *plan) {
+    return counts_plan_common(W, H, n_frames, x0, y0, rw, rh, n_levels, level_stride, flags, thresholds_address,
+                              out_address, count_address, n_cu, 1u, plan);
+}
+
+int dbde16_hip_project_counts_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int n_levels,
+                                   uint64_t level_stride, int flags, uint64_t thresholds_address, uint64_t out_address,
+                                   uint64_t count_address, int n_cu, dbde_hip_project_counts_plan_t *plan) {
+    return counts_plan_common(W, H, n_frames, x0, y0, rw, rh, n_levels, level_stride, flags, thresholds_address,
+                              out_address, count_address, n_cu, 2u, plan);
+}
+
+// Both count projections: the index (pix: 1 = DBDE, 2 = DBDE16) in timing slot 1, the projection kernels in slot 2.
+static int counts_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream, size_t stream_bytes,
+                         const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                         const void *d_thresholds, int n_levels, size_t level_stride, int accumulate, int flags,
+                         uint32_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    CountsPlan pl;
+    if (const char *why = plan_counts(W, H, n_frames, x0, y0, rw, rh, n_levels, (uint64_t)level_stride, flags,
+                                      reinterpret_cast<uintptr_t>(d_thresholds), reinterpret_cast<uintptr_t>(d_out),
+                                      reinterpret_cast<uintptr_t>(d_count), ctx->n_cu, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d, K=%d)", name, why, W, H,
+                    n_frames, rw, rh, x0, y0, n_levels);
+    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n_frames > 0) {
+        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.proj.roi.dg, pix,
+                           pl.proj.roi.split);
+        if (rc) return rc;
+    }
+    CountsParams p;
+    memset(&p, 0, sizeof p);
+    if (pl.proj.workspace) {   // the U32 partials [segments][K][rh * rw]
+        int rc = grow(ctx, ctx->proj_ws, ctx->proj_ws_bytes, (size_t)pl.proj.workspace, 1);
+        if (rc) return rc;
+        p.ws = reinterpret_cast<uint32_t *>(ctx->proj_ws);
+    }
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.n_frames = (uint32_t)n_frames;
+    p.x0 = x0;
+    p.y0 = y0;
+    p.rw = rw;
+    p.rh = rh;
+    p.T = pl.proj.roi.g.T;
+    p.w = pl.proj.roi.g.w;
+    p.geom = pl.proj.roi.dg;
+    p.tx0 = pl.proj.roi.tx0;
+    p.ty0 = pl.proj.roi.ty0;
+    p.rows = pl.proj.rows;
+    p.pieces = pl.proj.pieces;
+    p.segments = pl.proj.segments;
+    p.fps = pl.proj.fps;
+    p.accumulate = accumulate ? 1 : 0;
+    p.levels = pl.levels;
+    p.maps = (flags & DBDE_HIP_COUNTS_MAPS) ? 1 : 0;
+    p.thresholds = d_thresholds;
+    p.level_stride = (uint64_t)level_stride;
+    p.out = d_out;
+    p.out_count = d_count;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_counts(p, pl.levels, pix, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_project_counts(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                            const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                            const uint8_t *d_thresholds, int n_levels, size_t level_stride, int accumulate, int flags,
+                            uint32_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results) {
+    return counts_common(ctx, "project_counts", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
+                         rh, d_thresholds, n_levels, level_stride, accumulate, flags, d_out, d_count, d_results);
+}
+
+int dbde16_hip_project_counts(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                              const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw,
+                              int rh, const uint16_t *d_thresholds, int n_levels, size_t level_stride, int accumulate,
+                              int flags, uint32_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results) {
+    return counts_common(ctx, "project_counts16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0,
+                         rw, rh, d_thresholds, n_levels, level_stride, accumulate, flags, d_out, d_count, d_results);
 }
 
 // ---- grouped temporal projections --------------------------------------------------------

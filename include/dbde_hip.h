@@ -428,6 +428,47 @@ int dbde16_hip_project_weighted(dbde_hip_ctx *ctx, const uint8_t *d_stream, size
                                 int accumulate, int flags,
                                 float *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results);
 
+/* Count projection: K = n_levels U32 planes of the rw x rh window,
+ *   out[k][y][x] = number of accepted frames f with p_f[y0 + y][x0 + x] <= thr_k(y, x),   k = 0 .. K - 1,
+ * reduced straight from the compressed bytes (no image is written).  The compare is unsigned in the pixel type.  One
+ * primitive for exact per-pixel order statistics over time (a radix refinement on the counts: temporal median,
+ * percentile baselines) and for dwell and occupancy maps.
+ * Inputs and outputs:
+ *   The stream, the window and its argument rules, the validation, d_results, the stream_bytes rule and the timing
+ *   slots (index 1, projection kernels 2) are dbde_hip_project's; there are no per-frame origins.
+ *   Thresholds always live on the device (U8 elements), so the call stays asynchronous.  Without DBDE_HIP_COUNTS_MAPS
+ *   thr_k = d_thresholds[k]: K values, level_stride ignored.  With it thr_k(y, x) = d_thresholds[k * level_stride +
+ *   y * rw + x]: K maps in window coordinates, level_stride >= rw * rh (in elements); only elements of window pixels
+ *   are read.  The levels are independent: no ordering of the thresholds is required.  1 <= n_levels <=
+ *   DBDE_HIP_COUNTS_MAX_LEVELS.
+ *   d_out is [n_levels][rh][rw] U32, row-major, 4-byte aligned, indexed in 64 bits.  d_count (one U64, 8-byte aligned,
+ *   required) receives the number of frames that contributed, as in dbde_hip_project.
+ * The value.  Counts are exact integers modulo 2^32 (a pixel wraps only after 2^32 accepted frames at or below its
+ *   threshold).  A rejected frame adds nothing.  accumulate = 1 adds this call's counts to what the planes hold and
+ *   the accepted frames to *d_count, so a run of frames may be split into calls, batches or segments in any way with
+ *   the same result; accumulate = 1 with n_frames == 0 changes nothing.  accumulate = 0 with no accepted frame
+ *   (n_frames == 0 included) writes zero planes and count 0.  The result does not depend on the plan's segments.
+ * Errors: DBDE_HIP_ERR_ARG for everything dbde_hip_project rejects of its sizes, window and pointers, n_levels
+ *   outside 1..8, NULL d_thresholds / d_out / d_count, a misaligned d_out (4 bytes) or d_count (8 bytes), MAPS with
+ *   level_stride < rw * rh, and unknown flag bits.
+ * Asynchronous on the context's stream; workspace as dbde_hip_project, with the U32 partials the plan reports. */
+enum { DBDE_HIP_COUNTS_MAX_LEVELS = 8 };
+enum { DBDE_HIP_COUNTS_MAPS = 1 };   /* flags: thresholds are per-pixel maps; otherwise K scalars */
+int dbde_hip_project_counts(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                            const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                            int x0, int y0, int rw, int rh,
+                            const uint8_t *d_thresholds, int n_levels, size_t level_stride,
+                            int accumulate, int flags,
+                            uint32_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results);
+/* The same for DBDE16 frames: dbde_hip_project_counts' contract with U16 pixels and U16 thresholds (2-byte aligned),
+ * validated as dbde16_hip_project validates. */
+int dbde16_hip_project_counts(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                              const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                              int x0, int y0, int rw, int rh,
+                              const uint16_t *d_thresholds, int n_levels, size_t level_stride,
+                              int accumulate, int flags,
+                              uint32_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results);
+
 /* ---- multi-GPU: variable-length gather of the compressed stream to a root (RCCL over xGMI) ------------------- */
 /* Frames are independent, so the path shards by contiguous frame blocks (rank g of G owns frames
  * [g*N/G, (g+1)*N/G)): every rank encodes its block with dbde_hip_encode_frames (slot_stride 0) and its output is
@@ -731,6 +772,42 @@ int dbde16_hip_project_weighted_plan(int W, int H, int n_frames, int x0, int y0,
                                      int n_regressors, uint64_t weight_stride, int flags,
                                      uint64_t weights_address, uint64_t out_address, uint64_t count_address,
                                      int n_cu, dbde_hip_project_weighted_plan_t *plan);
+
+/* What dbde_hip_project_counts runs (pure host arithmetic, like dbde_hip_project_plan): validates exactly what the
+ * call validates of its sizes, window, n_levels, level_stride, flags and addresses (DBDE_HIP_ERR_ARG otherwise) and
+ * reports the tile window, the index geometry, the launch and its workspace.  The fields are
+ * dbde_hip_project_weighted_plan_t's, with levels in place of regressors; segments and frames_per_segment follow
+ * dbde_hip_project_plan's rule for the same window, n_frames and compute units (the counts do not depend on them).
+ * All 8 level counts have a kernel instance of their own for both pixel sizes, so levels is also the instance used.
+ * thresholds_address, out_address and count_address stand for the call's pointers (0 = NULL, rejected); n_cu: compute
+ * units of the device (the call uses its context's). */
+typedef struct dbde_hip_project_counts_plan_t {
+    int32_t tile_x, tile_y;           /* first tile column / row of the window */
+    int32_t tiles_x, tiles_y;         /* tiles across / down the window covers */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t threads;                 /* projection kernel: workgroup size */
+    uint32_t pieces_x;                /* projection kernel: workgroups across a window tile row */
+    uint32_t segments;                /* S: frame segments, each counted by its own workgroups */
+    uint32_t frames_per_segment;      /* fps: frames of every segment but the last (which may hold fewer) */
+    uint32_t max_frames_per_segment;  /* dbde_hip_project's bound, kept so that the two plans agree */
+    uint32_t levels;                  /* K */
+    uint64_t grid;                    /* projection kernel: pieces_x * tiles_y * segments workgroups */
+    uint64_t combine_grid;            /* combine kernel: workgroups (0 = one segment, no combine) */
+    uint64_t workspace_bytes;         /* U32 partials: 4 * S * K * rw * rh rounded up to 16 (0 for one segment) */
+    uint32_t lds_bytes;               /* projection kernel: LDS per workgroup */
+    uint32_t reserved_;
+} dbde_hip_project_counts_plan_t;
+int dbde_hip_project_counts_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                                 int n_levels, uint64_t level_stride, int flags,
+                                 uint64_t thresholds_address, uint64_t out_address, uint64_t count_address,
+                                 int n_cu, dbde_hip_project_counts_plan_t *plan);
+int dbde16_hip_project_counts_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                                   int n_levels, uint64_t level_stride, int flags,
+                                   uint64_t thresholds_address, uint64_t out_address, uint64_t count_address,
+                                   int n_cu, dbde_hip_project_counts_plan_t *plan);
 
 /* ---- region traces: per frame and per labelled region, max / min / sum / sum of squares ---------- */
 /* A trace map is a label image (H x W int32, row-major, pitch W: 0 = no region, 1..n_labels = region id) classified
