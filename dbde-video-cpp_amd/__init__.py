@@ -75,6 +75,7 @@ C_ABI_SYMBOLS = [
     "dbde16_hip_project_weighted_plan",
     "dbde_hip_project_counts", "dbde16_hip_project_counts", "dbde_hip_project_counts_plan",
     "dbde16_hip_project_counts_plan",
+    "dbde_hip_project_pairs", "dbde16_hip_project_pairs", "dbde_hip_project_pairs_plan", "dbde16_hip_project_pairs_plan",
 ]
 
 
@@ -215,6 +216,12 @@ def lib():
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_project_counts_plan", "dbde16_hip_project_counts_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, u64, i, u64, u64, u64, i, C.POINTER(CountProjectPlan)]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_project_pairs", "dbde16_hip_project_pairs"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, i, i, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_project_pairs_plan", "dbde16_hip_project_pairs_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, u64, u64, i, C.POINTER(PairProjectPlan)]
         getattr(L, fn).restype = i
     L.dbde_hip_trace_map_summary.argtypes = [vp, i, i, i, C.POINTER(TraceMapInfo), vp]
     L.dbde_hip_trace_map_summary.restype = i
@@ -898,6 +905,95 @@ class CountProjection:
         """out / count in float64 (K, rh, rw): the fraction of the accepted frames at or below each threshold (NaN where
         no frame was accepted)."""
         return self.out.to(torch.float64) / self.count.to(torch.float64)
+
+
+PAIR_RIGHT, PAIR_DOWN, PAIR_DOWN_RIGHT, PAIR_DOWN_LEFT = 1, 2, 4, 8
+PAIR_OFFSETS = ((1, 0), (0, 1), (1, 1), (-1, 1))   # (dx, dy) of bits 0..3
+
+
+def pairs_mask(pairs):
+    """4 (the 4-neighbourhood: RIGHT | DOWN), 8 (the 8-neighbourhood: all four), any other int in 1..15 (a mask of
+    PAIR_* bits), or an iterable of (dx, dy) from PAIR_OFFSETS -> dbde_hip_project_pairs' mask.  The ints 4 and 8 always
+    mean the neighbourhoods: DOWN_RIGHT or DOWN_LEFT alone are asked for as [(1, 1)] / [(-1, 1)]."""
+    if isinstance(pairs, (int, np.integer)) and not isinstance(pairs, bool):
+        mask = {4: 3, 8: 15}.get(int(pairs), int(pairs))
+    else:
+        mask = 0
+        for off in pairs:
+            off = tuple(int(v) for v in off)
+            if off not in PAIR_OFFSETS:
+                raise ValueError(f"offset {off} is not one of {PAIR_OFFSETS}")
+            mask |= 1 << PAIR_OFFSETS.index(off)
+    if not 1 <= mask <= 15:
+        raise ValueError(f"pairs must be 4, 8, a mask in 1..15 or offsets from {PAIR_OFFSETS}, not {pairs!r}")
+    return mask
+
+
+def pair_offsets(mask):
+    """The (dx, dy) of each plane of mask, in plane order."""
+    return tuple(PAIR_OFFSETS[b] for b in range(4) if (mask >> b) & 1)
+
+
+class PairProjectPlan(C.Structure):
+    """dbde_hip_project_pairs_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32),
+                ("index_split", C.c_uint32), ("threads", C.c_uint32), ("pieces_x", C.c_uint32),
+                ("segments", C.c_uint32), ("frames_per_segment", C.c_uint32), ("max_frames_per_segment", C.c_uint32),
+                ("planes", C.c_uint32), ("grid", C.c_uint64), ("combine_grid", C.c_uint64),
+                ("workspace_bytes", C.c_uint64), ("lds_bytes", C.c_uint32), ("instance", C.c_uint32),
+                ("piece_tiles", C.c_uint32), ("piece_stride", C.c_uint32), ("halo_left", C.c_uint32),
+                ("halo_right", C.c_uint32), ("rows_below", C.c_uint32), ("reserved_", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved_"}
+
+
+def _pairs_plan(fn, W, H, n_frames, x, y, rw, rh, pairs, n_cu, addresses):
+    """pairs_plan / pairs16_plan through the C function named fn."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    addr = {"out": 4096, "count": 4096}
+    addr.update(addresses or {})
+    pl = PairProjectPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, x, y, rw, rh, pairs, addr["out"], addr["count"], n_cu, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, pairs={pairs}) -> {rc}")
+    return pl.as_dict()
+
+
+def pairs_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, pairs=15, n_cu=256, addresses=None):
+    """dbde_hip_project_pairs_plan: the tile window, index geometry, launch, halo, segments and workspace of a pair
+    projection (host arithmetic only).  rw / rh default to the rest of the frame.  pairs: the raw mask (anything outside
+    1..15 is rejected).  addresses: optional {"out" | "count": address} standing for the call's pointers (0 = NULL;
+    aligned by default).  Raises ValueError where dbde_hip_project_pairs would return DBDE_HIP_ERR_ARG."""
+    return _pairs_plan("dbde_hip_project_pairs_plan", W, H, n_frames, x, y, rw, rh, pairs, n_cu, addresses)
+
+
+def pairs16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, pairs=15, n_cu=256, addresses=None):
+    """dbde16_hip_project_pairs_plan: pairs_plan for DBDE16 streams (Codec.project_pairs16)."""
+    return _pairs_plan("dbde16_hip_project_pairs_plan", W, H, n_frames, x, y, rw, rh, pairs, n_cu, addresses)
+
+
+class PairProjection:
+    """Device tensors of a pair projection (Codec.project_pairs): out int64 (P, rh, rw) holding the U64 bits (the sums
+    stay below 2^63, see include/dbde_hip.h), plane j the sum over the accepted frames of p[y][x] * p[y + dy][x + dx]
+    for (dx, dy) = offsets[j], zero where the partner lies outside the window; count int64 (1,), the frames that
+    contributed; offsets, the (dx, dy) of each plane."""
+
+    def __init__(self, out=None, count=None, offsets=None):
+        self.out, self.count, self.offsets = out, count, tuple(offsets) if offsets is not None else None
+
+    @property
+    def mask(self):
+        return pairs_mask(self.offsets)
+
+    @classmethod
+    def empty(cls, pairs, rh, rw, device):
+        """Uninitialised planes and a zero count for `pairs` (what Codec.project_pairs takes)."""
+        offsets = pair_offsets(pairs_mask(pairs))
+        return cls(torch.empty((len(offsets), rh, rw), dtype=torch.int64, device=device),
+                   torch.zeros(1, dtype=torch.int64, device=device), offsets)
 
 
 class TraceMapInfo(C.Structure):
@@ -1863,6 +1959,47 @@ class Codec:
         """project_counts for DBDE16 streams: U16 pixels and thresholds, the tensors int16 holding the U16 bits."""
         return self._project_counts("dbde16_hip_project_counts", 2, stream, stream_offset, stream_bytes, offsets, W, H,
                                     n, thresholds, x, y, rw, rh, out, accumulate, results)
+
+    def _project_pairs(self, fn, stream, stream_offset, stream_bytes, offsets, W, H, n, pairs, x, y, rw, rh, out,
+                       accumulate, results):
+        """project_pairs / project_pairs16 through the C function named fn."""
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        mask = pairs_mask(pairs)
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out= (the projection to continue)")
+            out = PairProjection.empty(pair_offsets(mask), rh, rw, self.device)
+        if out.offsets != pair_offsets(mask):
+            raise ValueError(f"out holds the offsets {out.offsets}, the call asks for {pair_offsets(mask)}")
+        if (tuple(out.out.shape) != (len(out.offsets), rh, rw) or out.out.dtype != torch.int64
+                or not out.out.is_contiguous()):
+            raise ValueError(f"out.out must be a contiguous int64 tensor ({len(out.offsets)}, {rh}, {rw})")
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(), W, H, n,
+                                 x, y, rw, rh, mask, 1 if accumulate else 0, out.out.data_ptr(), out.count.data_ptr(),
+                                 results.data_ptr() if n > 0 else None)
+        self._check(rc, fn)
+        return out, results
+
+    def project_pairs(self, stream, stream_offset, stream_bytes, offsets, W, H, n, pairs=8, x=0, y=0, rw=None, rh=None,
+                      out=None, accumulate=False, results=None):
+        """Neighbour-product projection of the rw x rh window at (x, y) over n frames: per requested forward offset
+        (dx, dy) one plane of sums of p[y][x] * p[y + dy][x + dx] over the accepted frames, both pixels inside the
+        window (include/dbde_hip.h).  pairs: 4 (RIGHT and DOWN), 8 (all four offsets), a mask, or an iterable of (dx, dy)
+        (pairs_mask).  out: a PairProjection to write into (accumulate=True adds to it: the sums are exact integers, so
+        any split of a run of frames gives the same planes).  With project's sum, sumsq and count of the same frames
+        and window, correlation.local_correlation turns it into the local correlation image.  Returns (PairProjection,
+        results (n, 4) int64)."""
+        return self._project_pairs("dbde_hip_project_pairs", stream, stream_offset, stream_bytes, offsets, W, H, n, pairs,
+                                   x, y, rw, rh, out, accumulate, results)
+
+    def project_pairs16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, pairs=8, x=0, y=0, rw=None,
+                        rh=None, out=None, accumulate=False, results=None):
+        """project_pairs for DBDE16 streams (U16 pixels; a product stays below 2^32)."""
+        return self._project_pairs("dbde16_hip_project_pairs", stream, stream_offset, stream_bytes, offsets, W, H, n,
+                                   pairs, x, y, rw, rh, out, accumulate, results)
 
     def _project_groups(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, group_frames,
                         group_starts, stats, sum_dtype, accumulate, out, results):

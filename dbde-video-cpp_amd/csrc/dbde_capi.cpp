@@ -17,6 +17,7 @@
 #include "dbde16_kernels.h"
 #include "dbde_binned_kernels.h"
 #include "dbde_counts_kernels.h"
+#include "dbde_pairs_kernels.h"
 #include "dbde_crop_kernels.h"
 #include "dbde_gproject_kernels.h"
 #include "dbde_hist_kernels.h"
@@ -961,6 +962,7 @@ struct ProjectPlan {
 // pix: 1 = DBDE (dbde_hip_project), 2 = DBDE16 (dbde16_hip_project: kProjTilesOf(2) tiles per workgroup, U16 / U64
 // partials); the segment rule is the same for both.
 static constexpr uint32_t kProjMinFramesPerSegment = 32;
+static const char *plan_project_segments(int n_frames, int rw, int rh, int n_cu, uint32_t pix, ProjectPlan &pl);
 static const char *plan_project(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
                                 uint32_t pix, ProjectPlan &pl) {
     if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, pix == 2u ? kRoi16WideThreads : kRoiWideThreads))
@@ -969,6 +971,10 @@ static const char *plan_project(int W, int H, int n_frames, int x0, int y0, int 
     pl.stats = stats;
     const uint32_t tiles = kProjTilesOf(pix);
     pl.pieces = (pl.roi.ntx + tiles - 1u) / tiles;
+    return plan_project_segments(n_frames, rw, rh, n_cu, pix, pl);
+}
+// The rows, segments, grids and workspace of a projection whose pieces across a window tile row are set (pl.pieces).
+static const char *plan_project_segments(int n_frames, int rw, int rh, int n_cu, uint32_t pix, ProjectPlan &pl) {
     pl.rows = pl.roi.nty;
     const uint64_t base = (uint64_t)pl.pieces * pl.rows, n = (uint64_t)n_frames;
     const uint64_t target = 4ull * (uint64_t)(n_cu > 0 ? n_cu : 1);
@@ -988,7 +994,7 @@ static const char *plan_project(int W, int H, int n_frames, int x0, int y0, int 
     const uint64_t pixels = (uint64_t)rw * (uint64_t)rh;
     pl.combine_grid = seg > 1u ? (pixels + kProjCombineThreads - 1u) / kProjCombineThreads : 0u;
     if (pl.combine_grid >= (1ull << 31)) return "too many workgroups in one call";
-    pl.workspace = project_workspace_bytes(stats, pl.segments, pixels, pix);
+    pl.workspace = project_workspace_bytes(pl.stats, pl.segments, pixels, pix);
     return nullptr;
 }
 
@@ -1398,6 +1404,145 @@ int dbde16_hip_project_counts(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t
                               int flags, uint32_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results) {
     return counts_common(ctx, "project_counts16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0,
                          rw, rh, d_thresholds, n_levels, level_stride, accumulate, flags, d_out, d_count, d_results);
+}
+
+// ---- neighbour-product projections -------------------------------------------------------
+// The window and the index geometry are plan_project's.  The pieces across a window tile row overlap by the halo tiles
+// of the instance that serves the mask (kPairsPiecesOf), and the segment rule is plan_project's applied to that grid.
+// The sums are integers, so the value does not depend on the segments.
+struct PairsPlan {
+    ProjectPlan proj;
+    uint32_t pairs, planes, instance;
+};
+static const char *plan_pairs(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int pairs, uint64_t out_address,
+                              uint64_t count_address, int n_cu, uint32_t pix, PairsPlan &pl) {
+    if (const char *why = plan_project(W, H, n_frames, x0, y0, rw, rh, kProjSum, n_cu, pix, pl.proj)) return why;
+    if (pairs < 1 || pairs > (int)kPairAll) return "pairs outside 1..15";
+    if (!out_address || !count_address) return "null pointer";
+    if ((out_address | count_address) & 7u) return "the U64 output and count must be 8-byte aligned";
+    pl.pairs = (uint32_t)pairs;
+    pl.planes = (uint32_t)__builtin_popcount(pl.pairs);
+    pl.instance = kPairsInstanceOf(pl.pairs);
+    pl.proj.pieces = kPairsPiecesOf(pl.proj.roi.ntx, pl.instance, pix);
+    if (const char *why = plan_project_segments(n_frames, rw, rh, n_cu, pix, pl.proj)) return why;
+    pl.proj.workspace = pairs_workspace_bytes(pl.planes, pl.proj.segments, (uint64_t)rw * (uint64_t)rh, pix);
+    return nullptr;
+}
+
+static int pairs_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int pairs, uint64_t out_address,
+                             uint64_t count_address, int n_cu, uint32_t pix, dbde_hip_project_pairs_plan_t *plan) {
+    PairsPlan pl;
+    if (!plan || plan_pairs(W, H, n_frames, x0, y0, rw, rh, pairs, out_address, count_address, n_cu, pix, pl))
+        return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->tile_x = (int32_t)pl.proj.roi.tx0;
+    plan->tile_y = (int32_t)pl.proj.roi.ty0;
+    plan->tiles_x = (int32_t)pl.proj.roi.ntx;
+    plan->tiles_y = (int32_t)pl.proj.roi.nty;
+    plan->chunks_per_frame = pl.proj.roi.dg.cpf;
+    plan->chunk_tiles = pl.proj.roi.dg.ct;
+    plan->chunk_pieces = pl.proj.roi.dg.ct == pl.proj.roi.g.w || pl.proj.roi.dg.pieces > 1u ? pl.proj.roi.dg.pieces : 0u;
+    plan->index_split = pl.proj.roi.split;
+    plan->threads = kProjThreads;
+    plan->pieces_x = pl.proj.pieces;
+    plan->segments = pl.proj.segments;
+    plan->frames_per_segment = pl.proj.fps;
+    plan->max_frames_per_segment = kProjMaxFramesPerSegment;
+    plan->planes = pl.planes;
+    plan->grid = pl.proj.grid;
+    plan->combine_grid = pl.proj.combine_grid;
+    plan->workspace_bytes = pl.proj.workspace;
+    plan->lds_bytes = kPairsLdsBytesOf(pl.instance);
+    plan->instance = pl.instance;
+    plan->piece_tiles = kProjTilesOf(pix);
+    plan->piece_stride = kPairsStrideOf(pl.instance, pix);
+    plan->halo_left = kPairsHaloLeft(pl.instance);
+    plan->halo_right = kPairsHaloRight(pl.instance);
+    plan->rows_below = pl.instance != kPairRight ? pl.proj.roi.nty - 1u : 0u;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_project_pairs_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int pairs,
+                                uint64_t out_address, uint64_t count_address, int n_cu,
+                                dbde_hip_project_pairs_plan_t *plan) {
+    return pairs_plan_common(W, H, n_frames, x0, y0, rw, rh, pairs, out_address, count_address, n_cu, 1u, plan);
+}
+
+int dbde16_hip_project_pairs_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int pairs,
+                                  uint64_t out_address, uint64_t count_address, int n_cu,
+                                  dbde_hip_project_pairs_plan_t *plan) {
+    return pairs_plan_common(W, H, n_frames, x0, y0, rw, rh, pairs, out_address, count_address, n_cu, 2u, plan);
+}
+
+// Both pair projections: the index (pix: 1 = DBDE, 2 = DBDE16) in timing slot 1, the projection kernels in slot 2.
+static int pairs_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream, size_t stream_bytes,
+                        const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                        int pairs, int accumulate, uint64_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    PairsPlan pl;
+    if (const char *why = plan_pairs(W, H, n_frames, x0, y0, rw, rh, pairs, reinterpret_cast<uintptr_t>(d_out),
+                                     reinterpret_cast<uintptr_t>(d_count), ctx->n_cu, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d, pairs=%d)", name, why, W, H,
+                    n_frames, rw, rh, x0, y0, pairs);
+    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n_frames > 0) {
+        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.proj.roi.dg, pix,
+                           pl.proj.roi.split);
+        if (rc) return rc;
+    }
+    PairsParams p;
+    memset(&p, 0, sizeof p);
+    if (pl.proj.workspace) {   // the partials [segments][planes][rh * rw], U32 (pix 1) or U64 (pix 2)
+        int rc = grow(ctx, ctx->proj_ws, ctx->proj_ws_bytes, (size_t)pl.proj.workspace, 1);
+        if (rc) return rc;
+        p.ws = ctx->proj_ws;
+    }
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.n_frames = (uint32_t)n_frames;
+    p.x0 = x0;
+    p.y0 = y0;
+    p.rw = rw;
+    p.rh = rh;
+    p.T = pl.proj.roi.g.T;
+    p.w = pl.proj.roi.g.w;
+    p.geom = pl.proj.roi.dg;
+    p.tx0 = pl.proj.roi.tx0;
+    p.ty0 = pl.proj.roi.ty0;
+    p.rows = pl.proj.rows;
+    p.pieces = pl.proj.pieces;
+    p.segments = pl.proj.segments;
+    p.fps = pl.proj.fps;
+    p.accumulate = accumulate ? 1 : 0;
+    p.pairs = pl.pairs;
+    p.planes = pl.planes;
+    p.out = d_out;
+    p.out_count = d_count;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_pairs(p, pix, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_project_pairs(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                           int pairs, int accumulate, uint64_t *d_out, uint64_t *d_count,
+                           dbde_hip_frame_result *d_results) {
+    return pairs_common(ctx, "project_pairs", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh,
+                        pairs, accumulate, d_out, d_count, d_results);
+}
+
+int dbde16_hip_project_pairs(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                             const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                             int pairs, int accumulate, uint64_t *d_out, uint64_t *d_count,
+                             dbde_hip_frame_result *d_results) {
+    return pairs_common(ctx, "project_pairs16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
+                        rh, pairs, accumulate, d_out, d_count, d_results);
 }
 
 // ---- grouped temporal projections --------------------------------------------------------

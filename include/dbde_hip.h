@@ -469,6 +469,43 @@ int dbde16_hip_project_counts(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t
                               int accumulate, int flags,
                               uint32_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results);
 
+/* Neighbour-product projection: one U64 plane of the rw x rh window per requested forward offset,
+ *   out[j][y][x] = sum over the accepted frames f of p_f[y0 + y][x0 + x] * p_f[y0 + y + dy][x0 + x + dx]
+ *                  where 0 <= x + dx < rw and y + dy < rh (both pixels inside the window),
+ * reduced straight from the compressed bytes (no image is written).  With dbde_hip_project's sum, sumsq and count it
+ * gives the Pearson correlation of every pixel with its neighbours exactly: the local correlation image.
+ * The offsets, one bit each: RIGHT (+1, 0), DOWN (0, +1), DOWN_RIGHT (+1, +1), DOWN_LEFT (-1, +1).  The four cover
+ *   every unordered pair of an 8-neighbourhood once; mask 3 is the 4-neighbourhood, mask 15 the 8-neighbourhood.
+ *   `pairs` is a mask in 1..15; plane j belongs to its j-th set bit in ascending bit order.
+ * Inputs and outputs:
+ *   The stream, the window and its argument rules, the validation, d_results, the stream_bytes rule and the timing
+ *   slots (index 1, projection kernels 2) are dbde_hip_project's; there are no per-frame origins.
+ *   d_out is [popcount(pairs)][rh][rw] U64, row-major, 8-byte aligned, indexed in 64 bits.  d_count (one U64, 8-byte
+ *   aligned, required) receives the number of frames that contributed, as in dbde_hip_project.
+ * The value.  The sums are exact integers, so a run of frames may be split into calls, batches or segments in any way
+ *   with the same bits.  A product is at most 255^2 (DBDE) or 65,535^2 < 2^32 (DBDE16), so an element stays below 2^63
+ *   while the accepted frames accumulated into it number fewer than 2^63 / 255^2 > 1.4e14 (DBDE) or 2^31 (DBDE16):
+ *   more than one call's n_frames (an int) can hold, and the bound that matters only for accumulate = 1 over many calls.
+ *   A rejected frame adds nothing.  Pixels outside the window never contribute, even where the frame has them.  An
+ *   element whose partner lies outside the window holds 0 after accumulate = 0 and is left unchanged by accumulate = 1.
+ *   accumulate = 1 adds this call's sums to what the planes hold and the accepted frames to *d_count; with
+ *   n_frames == 0 it changes nothing.  accumulate = 0 with no accepted frame (n_frames == 0 included) writes zero
+ *   planes and count 0.  The result does not depend on the plan's segments.
+ * Errors: DBDE_HIP_ERR_ARG for everything dbde_hip_project rejects of its sizes, window and pointers, pairs outside
+ *   1..15, NULL d_out / d_count, and a d_out or d_count that is not 8-byte aligned.
+ * Asynchronous on the context's stream; workspace as dbde_hip_project, with the partials the plan reports. */
+enum { DBDE_HIP_PAIR_RIGHT = 1, DBDE_HIP_PAIR_DOWN = 2, DBDE_HIP_PAIR_DOWN_RIGHT = 4, DBDE_HIP_PAIR_DOWN_LEFT = 8 };
+int dbde_hip_project_pairs(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                           int x0, int y0, int rw, int rh, int pairs, int accumulate,
+                           uint64_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results);
+/* The same for DBDE16 frames: dbde_hip_project_pairs' contract with U16 pixels, validated as dbde16_hip_project
+ * validates. */
+int dbde16_hip_project_pairs(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                             const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                             int x0, int y0, int rw, int rh, int pairs, int accumulate,
+                             uint64_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results);
+
 /* ---- multi-GPU: variable-length gather of the compressed stream to a root (RCCL over xGMI) ------------------- */
 /* Frames are independent, so the path shards by contiguous frame blocks (rank g of G owns frames
  * [g*N/G, (g+1)*N/G)): every rank encodes its block with dbde_hip_encode_frames (slot_stride 0) and its output is
@@ -808,6 +845,57 @@ int dbde16_hip_project_counts_plan(int W, int H, int n_frames, int x0, int y0, i
                                    int n_levels, uint64_t level_stride, int flags,
                                    uint64_t thresholds_address, uint64_t out_address, uint64_t count_address,
                                    int n_cu, dbde_hip_project_counts_plan_t *plan);
+
+/* What dbde_hip_project_pairs runs (pure host arithmetic, like dbde_hip_project_plan): validates exactly what the call
+ * validates of its sizes, window, pairs and addresses (DBDE_HIP_ERR_ARG otherwise) and reports the tile window, the
+ * index geometry, the launch and its workspace.  out_address and count_address stand for the call's pointers (0 =
+ * NULL, rejected); n_cu: compute units of the device (the call uses its context's).  The formulas:
+ *   instance     1 for pairs == 1, 3 for pairs 2 and 3, 15 for every mask with a diagonal: the kernel instance that
+ *                runs.  It accumulates all of its offsets and stores the requested planes.
+ *   piece_tiles  P = threads / 8 (DBDE: 32) or threads / 16 (DBDE16: 16): tiles one workgroup decodes.
+ *   halo_left    1 where the instance has DOWN_LEFT, halo_right 1 where it has RIGHT or DOWN_RIGHT, else 0: tiles at
+ *                either end of a piece that are decoded as partners only.  The window's first piece owns its first
+ *                tile and its last piece its last: their partners beyond lie outside the window.
+ *   piece_stride s = P - halo_left - halo_right: tiles from one piece's first tile to the next one's.
+ *   pieces_x     1 while tiles_x <= P, else 1 + ceil((tiles_x - P) / s): more than one from 264 pixels (DBDE) or 136
+ *                pixels (DBDE16) of an aligned window.
+ *   rows_below   tiles_y - 1 for instances 3 and 15 (every window tile row but the last also decodes row 0 of the tile
+ *                row under it, through a second offset prefix), 0 for instance 1.
+ *   segments, frames_per_segment: dbde_hip_project_plan's rule applied to pieces_x * tiles_y workgroups.
+ *   grid         pieces_x * tiles_y * segments; combine_grid = ceil(rw * rh / 256) with more than one segment, else 0.
+ *   workspace_bytes  (4 DBDE, 8 DBDE16) * segments * planes * rw * rh rounded up to 16; 0 for one segment.
+ *   lds_bytes    2 * 4 * R * 288 + 2 * 4 * (R - 7) * 32 + 16 with R = 8 band rows for instance 1 and 9 otherwise: the
+ *                double-buffered band of a group of 4 frames, the wave totals of the prefixes, the count's. */
+typedef struct dbde_hip_project_pairs_plan_t {
+    int32_t tile_x, tile_y;           /* first tile column / row of the window */
+    int32_t tiles_x, tiles_y;         /* tiles across / down the window covers */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t threads;                 /* projection kernel: workgroup size */
+    uint32_t pieces_x;                /* projection kernel: workgroups across a window tile row */
+    uint32_t segments;                /* S: frame segments, each summed by its own workgroups */
+    uint32_t frames_per_segment;      /* fps: frames of every segment but the last (which may hold fewer) */
+    uint32_t max_frames_per_segment;  /* 65,536: keeps the DBDE kernel's U32 partials exact (65,536 * 255^2 < 2^32) */
+    uint32_t planes;                  /* popcount(pairs) */
+    uint64_t grid;                    /* projection kernel: pieces_x * tiles_y * segments workgroups */
+    uint64_t combine_grid;            /* combine kernel: workgroups (0 = one segment, no combine) */
+    uint64_t workspace_bytes;         /* per-segment partials (0 for one segment) */
+    uint32_t lds_bytes;               /* projection kernel: LDS per workgroup */
+    uint32_t instance;                /* mask of the kernel instance that runs: 1, 3 or 15 */
+    uint32_t piece_tiles;             /* tiles a workgroup decodes */
+    uint32_t piece_stride;            /* tiles between the first tiles of neighbouring pieces */
+    uint32_t halo_left, halo_right;   /* partner-only tiles at the ends of an inner piece */
+    uint32_t rows_below;              /* window tile rows that also decode row 0 of the tile row under them */
+    uint32_t reserved_;
+} dbde_hip_project_pairs_plan_t;
+int dbde_hip_project_pairs_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int pairs,
+                                uint64_t out_address, uint64_t count_address, int n_cu,
+                                dbde_hip_project_pairs_plan_t *plan);
+int dbde16_hip_project_pairs_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int pairs,
+                                  uint64_t out_address, uint64_t count_address, int n_cu,
+                                  dbde_hip_project_pairs_plan_t *plan);
 
 /* ---- region traces: per frame and per labelled region, max / min / sum / sum of squares ---------- */
 /* A trace map is a label image (H x W int32, row-major, pitch W: 0 = no region, 1..n_labels = region id) classified
