@@ -76,6 +76,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_project_counts", "dbde16_hip_project_counts", "dbde_hip_project_counts_plan",
     "dbde16_hip_project_counts_plan",
     "dbde_hip_project_pairs", "dbde16_hip_project_pairs", "dbde_hip_project_pairs_plan", "dbde16_hip_project_pairs_plan",
+    "dbde_hip_project_lag", "dbde16_hip_project_lag", "dbde_hip_project_lag_plan", "dbde16_hip_project_lag_plan",
 ]
 
 
@@ -222,6 +223,12 @@ def lib():
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_project_pairs_plan", "dbde16_hip_project_pairs_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, u64, u64, i, C.POINTER(PairProjectPlan)]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_project_lag", "dbde16_hip_project_lag"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_project_lag_plan", "dbde16_hip_project_lag_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, i, C.c_uint, u64, u64, u64, u64, i, C.POINTER(LagProjectPlan)]
         getattr(L, fn).restype = i
     L.dbde_hip_trace_map_summary.argtypes = [vp, i, i, i, C.POINTER(TraceMapInfo), vp]
     L.dbde_hip_trace_map_summary.restype = i
@@ -994,6 +1001,99 @@ class PairProjection:
         offsets = pair_offsets(pairs_mask(pairs))
         return cls(torch.empty((len(offsets), rh, rw), dtype=torch.int64, device=device),
                    torch.zeros(1, dtype=torch.int64, device=device), offsets)
+
+
+LAG_STATS = ("product", "pairsum", "absdiff", "sqdiff", "maxdiff")   # bits 0..4 of dbde_hip_project_lag_plan's stats
+LAG_MAX = 8
+
+
+def lag_mask(stats):
+    """An iterable of names from LAG_STATS (or one name, or a mask in 1..31) -> the DBDE_HIP_LAG_* mask."""
+    if isinstance(stats, (int, np.integer)) and not isinstance(stats, bool):
+        mask = int(stats)
+    else:
+        mask = 0
+        for name in ((stats,) if isinstance(stats, str) else stats):
+            if name not in LAG_STATS:
+                raise ValueError(f"statistic {name!r} is not one of {LAG_STATS}")
+            mask |= 1 << LAG_STATS.index(name)
+    if not 1 <= mask <= 31:
+        raise ValueError(f"stats must name at least one of {LAG_STATS}, not {stats!r}")
+    return mask
+
+
+def lag_stats(mask):
+    """The names of the statistics of mask, in bit order."""
+    return tuple(LAG_STATS[b] for b in range(5) if (mask >> b) & 1)
+
+
+class LagProjectPlan(C.Structure):
+    """dbde_hip_project_lag_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32),
+                ("index_split", C.c_uint32), ("threads", C.c_uint32), ("pieces_x", C.c_uint32),
+                ("segments", C.c_uint32), ("frames_per_segment", C.c_uint32), ("max_frames_per_segment", C.c_uint32),
+                ("planes", C.c_uint32), ("grid", C.c_uint64), ("combine_grid", C.c_uint64),
+                ("workspace_bytes", C.c_uint64), ("lds_bytes", C.c_uint32), ("instance", C.c_uint32),
+                ("first_frame", C.c_uint32), ("history_frames", C.c_uint32), ("first_pair", C.c_uint32),
+                ("reserved_", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved_"}
+
+
+def _lag_plan(fn, W, H, n_frames, x, y, rw, rh, lag, lead, stats, n_cu, addresses):
+    """lag_plan / lag16_plan through the C function named fn."""
+    rw = W - x if rw is None else rw
+    rh = H - y if rh is None else rh
+    addr = {"sums": 4096, "maxdiff": 4096, "pairs": 4096, "count": 4096}
+    addr.update(addresses or {})
+    pl = LagProjectPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, x, y, rw, rh, lag, lead, stats, addr["sums"], addr["maxdiff"], addr["pairs"],
+                            addr["count"], n_cu, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {x}, {y}, {rw}, {rh}, lag={lag}, lead={lead}, stats={stats}) -> {rc}")
+    return pl.as_dict()
+
+
+def lag_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, lag=1, lead=0, stats=31, n_cu=256, addresses=None):
+    """dbde_hip_project_lag_plan: the tile window, index geometry, launch, segments, history frames, instance and
+    workspace of a lag projection (host arithmetic only).  rw / rh default to the rest of the frame.  stats: the raw
+    mask of DBDE_HIP_LAG_* bits (anything outside 1..31 is rejected).  addresses: optional {"sums" | "maxdiff" | "pairs"
+    | "count": address} standing for the call's pointers (aligned by default; pairs / count 0 = NULL).  Raises
+    ValueError where dbde_hip_project_lag would return DBDE_HIP_ERR_ARG."""
+    return _lag_plan("dbde_hip_project_lag_plan", W, H, n_frames, x, y, rw, rh, lag, lead, stats, n_cu, addresses)
+
+
+def lag16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, lag=1, lead=0, stats=31, n_cu=256, addresses=None):
+    """dbde16_hip_project_lag_plan: lag_plan for DBDE16 streams (Codec.project_lag16)."""
+    return _lag_plan("dbde16_hip_project_lag_plan", W, H, n_frames, x, y, rw, rh, lag, lead, stats, n_cu, addresses)
+
+
+class LagProjection:
+    """Device tensors of a lag projection (Codec.project_lag): product, pairsum, absdiff, sqdiff int64 (rh, rw) holding
+    the U64 bits (the sums stay below 2^63, see include/dbde_hip.h), maxdiff uint8 (rh, rw) (project_lag16: int16
+    holding the U16 bits), each None where not requested; pairs int64 (1,), the counted pairs; count int64 (1,), the
+    accepted frames past the lead; lag, the distance of the two frames of a pair."""
+
+    def __init__(self, product=None, pairsum=None, absdiff=None, sqdiff=None, maxdiff=None, pairs=None, count=None,
+                 lag=None):
+        self.product, self.pairsum, self.absdiff, self.sqdiff, self.maxdiff = product, pairsum, absdiff, sqdiff, maxdiff
+        self.pairs, self.count, self.lag = pairs, count, lag
+
+    @property
+    def stats(self):
+        return tuple(k for k in LAG_STATS if getattr(self, k) is not None)
+
+    @classmethod
+    def empty(cls, stats, rh, rw, device, lag=1, bits=8):
+        """Uninitialised planes and zero scalars for `stats` (what Codec.project_lag takes)."""
+        names = lag_stats(lag_mask(stats))
+        planes = {k: torch.empty((rh, rw), dtype=(torch.int64 if k != "maxdiff" else
+                                                  torch.uint8 if bits == 8 else torch.int16), device=device)
+                  for k in names}
+        return cls(pairs=torch.zeros(1, dtype=torch.int64, device=device),
+                   count=torch.zeros(1, dtype=torch.int64, device=device), lag=lag, **planes)
 
 
 class TraceMapInfo(C.Structure):
@@ -2000,6 +2100,54 @@ class Codec:
         """project_pairs for DBDE16 streams (U16 pixels; a product stays below 2^32)."""
         return self._project_pairs("dbde16_hip_project_pairs", stream, stream_offset, stream_bytes, offsets, W, H, n,
                                    pairs, x, y, rw, rh, out, accumulate, results)
+
+    def _project_lag(self, fn, bits, stream, stream_offset, stream_bytes, offsets, W, H, n, lag, stats, lead, x, y, rw,
+                     rh, out, accumulate, results):
+        """project_lag / project_lag16 through the C function named fn; bits: of a pixel (the maxdiff plane's)."""
+        rw = W - x if rw is None else rw
+        rh = H - y if rh is None else rh
+        names = lag_stats(lag_mask(stats))
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out= (the projection to continue)")
+            out = LagProjection.empty(names, rh, rw, self.device, lag=lag, bits=bits)
+        if out.lag != lag:
+            raise ValueError(f"out holds lag {out.lag}, the call asks for {lag}")
+        ptr = {}
+        for k in LAG_STATS:
+            t = getattr(out, k) if k in names else None
+            if k in names:
+                want = torch.int64 if k != "maxdiff" else torch.uint8 if bits == 8 else torch.int16
+                if t is None or tuple(t.shape) != (rh, rw) or t.dtype != want or not t.is_contiguous():
+                    raise ValueError(f"out.{k} must be a contiguous {want} tensor ({rh}, {rw})")
+            ptr[k] = t.data_ptr() if t is not None else None
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(), W, H, n,
+                                 x, y, rw, rh, lag, lead, 1 if accumulate else 0, ptr["product"], ptr["pairsum"],
+                                 ptr["absdiff"], ptr["sqdiff"], ptr["maxdiff"], out.pairs.data_ptr(),
+                                 out.count.data_ptr(), results.data_ptr() if n > 0 else None)
+        self._check(rc, fn)
+        return out, results
+
+    def project_lag(self, stream, stream_offset, stream_bytes, offsets, W, H, n, lag=1, stats=("sqdiff",), lead=0, x=0,
+                    y=0, rw=None, rh=None, out=None, accumulate=False, results=None):
+        """Lag projection of the rw x rh window at (x, y) over n frames: per pixel, over the pairs
+        (a, b) = (p[f - lag], p[f]) with f >= max(lead, lag) and both frames accepted, the requested ones of
+        product = sum a b, pairsum = sum (a + b), absdiff = sum |b - a|, sqdiff = sum (b - a)^2 and
+        maxdiff = max |b - a| (include/dbde_hip.h).  stats: names from LAG_STATS.  lead: leading frames that are history
+        only (the frames carried over from the call before).  out: a LagProjection to write into; planes of out that
+        stats does not name are left alone (accumulate=True adds to it: the values are exact integers, so a run of
+        frames split by the header's rule gives the same planes).  lagged.py turns the planes into the noise image, the
+        mean absolute difference and the autocorrelation.  Returns (LagProjection, results (n, 4) int64)."""
+        return self._project_lag("dbde_hip_project_lag", 8, stream, stream_offset, stream_bytes, offsets, W, H, n, lag,
+                                 stats, lead, x, y, rw, rh, out, accumulate, results)
+
+    def project_lag16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, lag=1, stats=("sqdiff",), lead=0,
+                      x=0, y=0, rw=None, rh=None, out=None, accumulate=False, results=None):
+        """project_lag for DBDE16 streams (U16 pixels; maxdiff int16 holding the U16 bits)."""
+        return self._project_lag("dbde16_hip_project_lag", 16, stream, stream_offset, stream_bytes, offsets, W, H, n,
+                                 lag, stats, lead, x, y, rw, rh, out, accumulate, results)
 
     def _project_groups(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, group_frames,
                         group_starts, stats, sum_dtype, accumulate, out, results):

@@ -17,6 +17,7 @@
 #include "dbde16_kernels.h"
 #include "dbde_binned_kernels.h"
 #include "dbde_counts_kernels.h"
+#include "dbde_lag_kernels.h"
 #include "dbde_pairs_kernels.h"
 #include "dbde_crop_kernels.h"
 #include "dbde_gproject_kernels.h"
@@ -1543,6 +1544,175 @@ int dbde16_hip_project_pairs(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t 
                              dbde_hip_frame_result *d_results) {
     return pairs_common(ctx, "project_pairs16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
                         rh, pairs, accumulate, d_out, d_count, d_results);
+}
+
+// ---- lag projections ---------------------------------------------------------------------
+// The window, the index geometry, the pieces and the segment rule are plan_project's (any statistics set gives the same
+// segments).  The values are integers, so they do not depend on the segments.
+struct LagPlan {
+    ProjectPlan proj;
+    uint32_t stats, instance, lag, lead, first_pair, history;
+};
+static const char *plan_lag(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int lag, int lead, unsigned stats,
+                            uint64_t sums_address, uint64_t maxdiff_address, uint64_t pairs_address,
+                            uint64_t count_address, int n_cu, uint32_t pix, LagPlan &pl) {
+    if (const char *why = plan_project(W, H, n_frames, x0, y0, rw, rh, kProjSum, n_cu, pix, pl.proj)) return why;
+    if (lag < 1 || lag > (int)kLagMax) return "lag outside 1..8";
+    if (lead < 0 || lead > n_frames) return "lead outside 0..n_frames";
+    if (stats < 1u || stats > kLagAll) return "no statistic (or an unknown one) requested";
+    if (!pairs_address || !count_address) return "null pointer";
+    if ((sums_address | pairs_address | count_address) & 7u) return "U64 outputs must be 8-byte aligned";
+    if (maxdiff_address & (pix - 1u)) return "the U16 maxdiff plane must be 2-byte aligned";
+    pl.stats = stats;
+    pl.instance = kLagInstanceOf(stats);
+    pl.lag = (uint32_t)lag;
+    pl.lead = (uint32_t)lead;
+    pl.first_pair = pl.lead > pl.lag ? pl.lead : pl.lag;
+    // segments that count a pair: those reaching past first_pair; each but the first decodes lag history frames again
+    const uint32_t active = pl.first_pair < (uint32_t)n_frames ? pl.proj.segments - pl.first_pair / pl.proj.fps : 0u;
+    pl.history = active > 1u ? (active - 1u) * pl.lag : 0u;
+    pl.proj.workspace = lag_workspace_bytes(stats, pl.proj.segments, (uint64_t)rw * (uint64_t)rh, pix);
+    return nullptr;
+}
+
+static int lag_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int lag, int lead, unsigned stats,
+                           uint64_t sums_address, uint64_t maxdiff_address, uint64_t pairs_address,
+                           uint64_t count_address, int n_cu, uint32_t pix, dbde_hip_project_lag_plan_t *plan) {
+    LagPlan pl;
+    if (!plan || plan_lag(W, H, n_frames, x0, y0, rw, rh, lag, lead, stats, sums_address, maxdiff_address, pairs_address,
+                          count_address, n_cu, pix, pl))
+        return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->tile_x = (int32_t)pl.proj.roi.tx0;
+    plan->tile_y = (int32_t)pl.proj.roi.ty0;
+    plan->tiles_x = (int32_t)pl.proj.roi.ntx;
+    plan->tiles_y = (int32_t)pl.proj.roi.nty;
+    plan->chunks_per_frame = pl.proj.roi.dg.cpf;
+    plan->chunk_tiles = pl.proj.roi.dg.ct;
+    plan->chunk_pieces = pl.proj.roi.dg.ct == pl.proj.roi.g.w || pl.proj.roi.dg.pieces > 1u ? pl.proj.roi.dg.pieces : 0u;
+    plan->index_split = pl.proj.roi.split;
+    plan->threads = kProjThreads;
+    plan->pieces_x = pl.proj.pieces;
+    plan->segments = pl.proj.segments;
+    plan->frames_per_segment = pl.proj.fps;
+    plan->max_frames_per_segment = kProjMaxFramesPerSegment;
+    plan->planes = (uint32_t)__builtin_popcount(pl.stats);
+    plan->grid = pl.proj.grid;
+    plan->combine_grid = pl.proj.combine_grid;
+    plan->workspace_bytes = pl.proj.workspace;
+    plan->lds_bytes = kLagLdsBytes;
+    plan->instance = pl.instance;
+    plan->first_frame = pl.first_pair - pl.lag;
+    plan->history_frames = pl.history;
+    plan->first_pair = pl.first_pair;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_project_lag_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int lag, int lead,
+                              unsigned stats, uint64_t sums_address, uint64_t maxdiff_address, uint64_t pairs_address,
+                              uint64_t count_address, int n_cu, dbde_hip_project_lag_plan_t *plan) {
+    return lag_plan_common(W, H, n_frames, x0, y0, rw, rh, lag, lead, stats, sums_address, maxdiff_address,
+                           pairs_address, count_address, n_cu, 1u, plan);
+}
+
+int dbde16_hip_project_lag_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int lag, int lead,
+                                unsigned stats, uint64_t sums_address, uint64_t maxdiff_address, uint64_t pairs_address,
+                                uint64_t count_address, int n_cu, dbde_hip_project_lag_plan_t *plan) {
+    return lag_plan_common(W, H, n_frames, x0, y0, rw, rh, lag, lead, stats, sums_address, maxdiff_address,
+                           pairs_address, count_address, n_cu, 2u, plan);
+}
+
+// Both lag projections: the index (pix: 1 = DBDE, 2 = DBDE16) in timing slot 1, the projection kernels in slot 2.
+// d_maxdiff holds U8 (pix 1) or U16 (pix 2) pixels.
+static int lag_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream, size_t stream_bytes,
+                      const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                      int lag, int lead, int accumulate, uint64_t *d_product, uint64_t *d_pairsum, uint64_t *d_absdiff,
+                      uint64_t *d_sqdiff, void *d_maxdiff, uint64_t *d_pairs, uint64_t *d_count,
+                      dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    const unsigned stats = (d_product ? kLagProduct : 0u) | (d_pairsum ? kLagPairSum : 0u) | (d_absdiff ? kLagAbsDiff : 0u) |
+                           (d_sqdiff ? kLagSqDiff : 0u) | (d_maxdiff ? kLagMaxDiff : 0u);
+    const uint64_t sums = reinterpret_cast<uintptr_t>(d_product) | reinterpret_cast<uintptr_t>(d_pairsum) |
+                          reinterpret_cast<uintptr_t>(d_absdiff) | reinterpret_cast<uintptr_t>(d_sqdiff);
+    LagPlan pl;
+    if (const char *why = plan_lag(W, H, n_frames, x0, y0, rw, rh, lag, lead, stats, sums,
+                                   reinterpret_cast<uintptr_t>(d_maxdiff), reinterpret_cast<uintptr_t>(d_pairs),
+                                   reinterpret_cast<uintptr_t>(d_count), ctx->n_cu, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d, lag=%d lead=%d)", name, why, W,
+                    H, n_frames, rw, rh, x0, y0, lag, lead);
+    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n_frames > 0) {
+        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.proj.roi.dg, pix,
+                           pl.proj.roi.split);
+        if (rc) return rc;
+    }
+    LagParams p;
+    memset(&p, 0, sizeof p);
+    if (pl.proj.workspace) {   // the partials in lag_workspace_bytes' order, each 16-byte aligned
+        int rc = grow(ctx, ctx->proj_ws, ctx->proj_ws_bytes, (size_t)pl.proj.workspace, 1);
+        if (rc) return rc;
+        const uint64_t pixels = (uint64_t)rw * (uint64_t)rh;
+        uint8_t *w = ctx->proj_ws;
+        if (d_product) { p.ws_product = w; w += lag_partial_bytes(kLagProduct, pl.proj.segments, pixels, pix); }
+        if (d_pairsum) { p.ws_pairsum = w; w += lag_partial_bytes(kLagPairSum, pl.proj.segments, pixels, pix); }
+        if (d_absdiff) { p.ws_absdiff = reinterpret_cast<uint32_t *>(w); w += lag_partial_bytes(kLagAbsDiff, pl.proj.segments, pixels, pix); }
+        if (d_sqdiff) { p.ws_sqdiff = w; w += lag_partial_bytes(kLagSqDiff, pl.proj.segments, pixels, pix); }
+        if (d_maxdiff) { p.ws_maxdiff = w; w += lag_partial_bytes(kLagMaxDiff, pl.proj.segments, pixels, pix); }
+    }
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.n_frames = (uint32_t)n_frames;
+    p.x0 = x0;
+    p.y0 = y0;
+    p.rw = rw;
+    p.rh = rh;
+    p.T = pl.proj.roi.g.T;
+    p.w = pl.proj.roi.g.w;
+    p.geom = pl.proj.roi.dg;
+    p.tx0 = pl.proj.roi.tx0;
+    p.ty0 = pl.proj.roi.ty0;
+    p.rows = pl.proj.rows;
+    p.pieces = pl.proj.pieces;
+    p.segments = pl.proj.segments;
+    p.fps = pl.proj.fps;
+    p.accumulate = accumulate ? 1 : 0;
+    p.lag = pl.lag;
+    p.lead = pl.lead;
+    p.out_product = d_product;
+    p.out_pairsum = d_pairsum;
+    p.out_absdiff = d_absdiff;
+    p.out_sqdiff = d_sqdiff;
+    p.out_maxdiff = d_maxdiff;
+    p.out_pairs = d_pairs;
+    p.out_count = d_count;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_lag(p, stats, pix, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_project_lag(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                         const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                         int lag, int lead, int accumulate, uint64_t *d_product, uint64_t *d_pairsum,
+                         uint64_t *d_absdiff, uint64_t *d_sqdiff, uint8_t *d_maxdiff, uint64_t *d_pairs,
+                         uint64_t *d_count, dbde_hip_frame_result *d_results) {
+    return lag_common(ctx, "project_lag", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh, lag,
+                      lead, accumulate, d_product, d_pairsum, d_absdiff, d_sqdiff, d_maxdiff, d_pairs, d_count, d_results);
+}
+
+int dbde16_hip_project_lag(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
+                           int lag, int lead, int accumulate, uint64_t *d_product, uint64_t *d_pairsum,
+                           uint64_t *d_absdiff, uint64_t *d_sqdiff, uint16_t *d_maxdiff, uint64_t *d_pairs,
+                           uint64_t *d_count, dbde_hip_frame_result *d_results) {
+    return lag_common(ctx, "project_lag16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh,
+                      lag, lead, accumulate, d_product, d_pairsum, d_absdiff, d_sqdiff, d_maxdiff, d_pairs, d_count,
+                      d_results);
 }
 
 // ---- grouped temporal projections --------------------------------------------------------

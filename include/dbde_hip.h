@@ -506,6 +506,56 @@ int dbde16_hip_project_pairs(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t 
                              int x0, int y0, int rw, int rh, int pairs, int accumulate,
                              uint64_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results);
 
+/* Lag projection: per pixel of the rw x rh window, statistics over the pairs of frames `lag` apart,
+ * with the order of the frames kept.  A pair is (a, b) = (p_{f - lag}[y0 + y][x0 + x], p_f[y0 + y][x0 + x]); over the
+ * counted pairs the planes hold
+ *   product = sum a * b        pairsum = sum (a + b)        absdiff = sum |b - a|        sqdiff = sum (b - a)^2
+ *   maxdiff = max |b - a| in the pixel type, 0 where no pair was counted,
+ * reduced straight from the compressed bytes (no image is written).  sqdiff gives the noise level from successive
+ * differences, sqrt(sqdiff / (2 pairs)); absdiff and maxdiff are motion maps; product and pairsum, with
+ * dbde_hip_project's sum, sumsq and count, give the autocorrelation at the lag.
+ * Which pairs count.  Positions are frame indices within the call.  Pair f is counted iff f >= max(lead, lag) and
+ *   frames f and f - lag are both accepted.  A rejected frame is not skipped over: it only voids the up to two pairs it
+ *   is a member of.  `lag` is a runtime value in 1..DBDE_HIP_LAG_MAX.  `lead`, 0..n_frames, is the number of leading
+ *   frames of the call that serve as history only: they are partners a, never b.
+ * Inputs and outputs:
+ *   The stream, the window and its argument rules, the validation, d_results, the stream_bytes rule and the timing
+ *   slots (index 1, projection kernels 2) are dbde_hip_project's; there are no per-frame origins.
+ *   Each plane is [rh][rw], row-major, indexed in 64 bits: the four sums U64 and 8-byte aligned, d_maxdiff U8 (DBDE) or
+ *   U16 and 2-byte aligned (DBDE16).  A NULL plane is not computed; at least one of the five must be given.
+ *   *d_pairs (one U64, 8-byte aligned, required) receives the number of counted pairs, the same for every pixel;
+ *   *d_count (likewise) the number of accepted frames with index >= lead.
+ * The value.  All values are exact integers, so the result depends neither on the plan's segments nor on how a run of
+ *   frames is split into calls.  The split rule: frames [0, N) in one call (lead 0, accumulate 0) equal, bit for bit,
+ *   the calls on [0, B) with lead = 0, then accumulating on [B - lag, 2B) with lead = lag, on [2B - lag, 3B) with
+ *   lead = lag and so on (B >= lag), maxdiff and *d_pairs included, and *d_count sums to the accepted frames of
+ *   [0, N).  `lead` exists for this rule.
+ *   Overflow: a product is at most 255^2 (DBDE) or 65,535^2 < 2^32 (DBDE16), a squared difference likewise, a + b at
+ *   most 510 or 131,070, so an element stays below 2^63 while the pairs accumulated into it number fewer than
+ *   2^63 / 255^2 > 1.4e14 (DBDE) or 2^31 (DBDE16): more than one call's n_frames (an int) can hold, and the bound
+ *   that matters only for accumulate = 1 over many calls.
+ *   accumulate = 1 adds to the sums, to *d_pairs and to *d_count and takes the maximum into maxdiff; with no counted
+ *   pair it leaves the planes as they are.  accumulate = 0 with no counted pair (n_frames <= lag and lead == n_frames
+ *   included) writes zero planes and *d_pairs = 0.
+ * Errors: DBDE_HIP_ERR_ARG for everything dbde_hip_project rejects of its sizes, window and pointers, lag outside
+ *   1..8, lead outside 0..n_frames, no plane requested, NULL d_pairs / d_count, and misaligned pointers.
+ * Asynchronous on the context's stream; workspace as dbde_hip_project, with the partials the plan reports. */
+enum { DBDE_HIP_LAG_MAX = 8 };
+enum { DBDE_HIP_LAG_PRODUCT = 1, DBDE_HIP_LAG_PAIRSUM = 2, DBDE_HIP_LAG_ABSDIFF = 4, DBDE_HIP_LAG_SQDIFF = 8,
+       DBDE_HIP_LAG_MAXDIFF = 16 };   /* the statistics as the plans name them */
+int dbde_hip_project_lag(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                         const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                         int x0, int y0, int rw, int rh, int lag, int lead, int accumulate,
+                         uint64_t *d_product, uint64_t *d_pairsum, uint64_t *d_absdiff, uint64_t *d_sqdiff,
+                         uint8_t *d_maxdiff, uint64_t *d_pairs, uint64_t *d_count, dbde_hip_frame_result *d_results);
+/* The same for DBDE16 frames: dbde_hip_project_lag's contract with U16 pixels and a U16 maxdiff plane, validated as
+ * dbde16_hip_project validates. */
+int dbde16_hip_project_lag(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                           int x0, int y0, int rw, int rh, int lag, int lead, int accumulate,
+                           uint64_t *d_product, uint64_t *d_pairsum, uint64_t *d_absdiff, uint64_t *d_sqdiff,
+                           uint16_t *d_maxdiff, uint64_t *d_pairs, uint64_t *d_count, dbde_hip_frame_result *d_results);
+
 /* ---- multi-GPU: variable-length gather of the compressed stream to a root (RCCL over xGMI) ------------------- */
 /* Frames are independent, so the path shards by contiguous frame blocks (rank g of G owns frames
  * [g*N/G, (g+1)*N/G)): every rank encodes its block with dbde_hip_encode_frames (slot_stride 0) and its output is
@@ -896,6 +946,52 @@ int dbde_hip_project_pairs_plan(int W, int H, int n_frames, int x0, int y0, int 
 int dbde16_hip_project_pairs_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int pairs,
                                   uint64_t out_address, uint64_t count_address, int n_cu,
                                   dbde_hip_project_pairs_plan_t *plan);
+
+/* What dbde_hip_project_lag runs (pure host arithmetic, like dbde_hip_project_plan): validates exactly what the call
+ * validates of its sizes, window, lag, lead, statistics and addresses (DBDE_HIP_ERR_ARG otherwise) and reports the tile
+ * window, the index geometry, the launch and its workspace.  `stats` is the mask of DBDE_HIP_LAG_* bits standing for
+ * the non-NULL planes.  sums_address (the OR of the addresses of the requested U64 planes: only its alignment is
+ * looked at), maxdiff_address, pairs_address and count_address stand for the call's pointers (pairs / count 0 = NULL,
+ * rejected); n_cu: compute units of the device (the call uses its context's).  The formulas:
+ *   instance     3 where stats has only product / pairsum, 28 where it has only absdiff / sqdiff / maxdiff, else 31:
+ *                the kernel instance that runs.  It accumulates all of its statistics and stores the requested planes.
+ *   pieces_x, segments, frames_per_segment: dbde_hip_project_plan's for the same window, n_frames and n_cu.
+ *   first_frame  max(lead - lag, 0): the first frame any workgroup decodes (the index still validates every frame).
+ *   history_frames  frames decoded a second time as history only: lag per segment that counts a pair, less the first
+ *                of them (a segment counts one iff it reaches past max(lead, lag)); 0 where no pair is counted.
+ *   grid         pieces_x * tiles_y * segments; combine_grid = ceil(rw * rh / 256) with more than one segment, else 0.
+ *   workspace_bytes  per requested statistic segments * rw * rh elements rounded up to 16 bytes: product, pairsum and
+ *                sqdiff 4 bytes (DBDE) or 8 (DBDE16), absdiff 4, maxdiff 1 or 2; 0 for one segment.
+ *   lds_bytes    8 * 256 * 8 (the history ring) + 2 * 4 * 2 * 16 (the wave totals of a group) + 32 (the scalars'). */
+typedef struct dbde_hip_project_lag_plan_t {
+    int32_t tile_x, tile_y;           /* first tile column / row of the window */
+    int32_t tiles_x, tiles_y;         /* tiles across / down the window covers */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t threads;                 /* projection kernel: workgroup size */
+    uint32_t pieces_x;                /* projection kernel: workgroups across a window tile row */
+    uint32_t segments;                /* S: frame segments, each summed by its own workgroups */
+    uint32_t frames_per_segment;      /* fps: frames of every segment but the last (which may hold fewer) */
+    uint32_t max_frames_per_segment;  /* 65,536: keeps the kernel's per-lane sums exact */
+    uint32_t planes;                  /* popcount(stats) */
+    uint64_t grid;                    /* projection kernel: pieces_x * tiles_y * segments workgroups */
+    uint64_t combine_grid;            /* combine kernel: workgroups (0 = one segment, no combine) */
+    uint64_t workspace_bytes;         /* per-segment partials (0 for one segment) */
+    uint32_t lds_bytes;               /* projection kernel: LDS per workgroup */
+    uint32_t instance;                /* statistics of the kernel instance that runs: 3, 28 or 31 */
+    uint32_t first_frame;             /* first frame decoded: max(lead - lag, 0) */
+    uint32_t history_frames;          /* frames decoded twice (history of the segments after the first) */
+    uint32_t first_pair;              /* max(lead, lag): the first frame that can be the later member of a pair */
+    uint32_t reserved_;
+} dbde_hip_project_lag_plan_t;
+int dbde_hip_project_lag_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int lag, int lead,
+                              unsigned stats, uint64_t sums_address, uint64_t maxdiff_address, uint64_t pairs_address,
+                              uint64_t count_address, int n_cu, dbde_hip_project_lag_plan_t *plan);
+int dbde16_hip_project_lag_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int lag, int lead,
+                                unsigned stats, uint64_t sums_address, uint64_t maxdiff_address, uint64_t pairs_address,
+                                uint64_t count_address, int n_cu, dbde_hip_project_lag_plan_t *plan);
 
 /* ---- region traces: per frame and per labelled region, max / min / sum / sum of squares ---------- */
 /* A trace map is a label image (H x W int32, row-major, pitch W: 0 = no region, 1..n_labels = region id) classified
