@@ -77,6 +77,8 @@ C_ABI_SYMBOLS = [
     "dbde16_hip_project_counts_plan",
     "dbde_hip_project_pairs", "dbde16_hip_project_pairs", "dbde_hip_project_pairs_plan", "dbde16_hip_project_pairs_plan",
     "dbde_hip_project_lag", "dbde16_hip_project_lag", "dbde_hip_project_lag_plan", "dbde16_hip_project_lag_plan",
+    "dbde_hip_project_registered", "dbde16_hip_project_registered", "dbde_hip_project_registered_plan",
+    "dbde16_hip_project_registered_plan",
 ]
 
 
@@ -230,7 +232,13 @@ def lib():
     for fn in ("dbde_hip_project_lag_plan", "dbde16_hip_project_lag_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, i, C.c_uint, u64, u64, u64, u64, i, C.POINTER(LagProjectPlan)]
         getattr(L, fn).restype = i
-    L.dbde_hip_trace_map_summary.argtypes = [vp, i, i, i, C.POINTER(TraceMapInfo), vp]
+    for fn in ("dbde_hip_project_registered", "dbde16_hip_project_registered"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_project_registered_plan", "dbde16_hip_project_registered_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, C.c_uint, i, C.POINTER(RegisteredProjectPlan)]
+        getattr(L, fn).restype = i
+    L.dbde_hip_trace_map_summary.argtypes =[vp, i, i, i, C.POINTER(TraceMapInfo), vp]
     L.dbde_hip_trace_map_summary.restype = i
     L.dbde_hip_trace_map_create.argtypes = [vp, vp, i, i, i, C.POINTER(vp)]
     L.dbde_hip_trace_map_create.restype = i
@@ -1068,6 +1076,40 @@ def lag_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, lag=1, lead=0, stats=31
 def lag16_plan(W, H, n_frames, x=0, y=0, rw=None, rh=None, lag=1, lead=0, stats=31, n_cu=256, addresses=None):
     """dbde16_hip_project_lag_plan: lag_plan for DBDE16 streams (Codec.project_lag16)."""
     return _lag_plan("dbde16_hip_project_lag_plan", W, H, n_frames, x, y, rw, rh, lag, lead, stats, n_cu, addresses)
+
+
+class RegisteredProjectPlan(C.Structure):
+    """dbde_hip_project_registered_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32),
+                ("index_split", C.c_uint32), ("threads", C.c_uint32), ("piece_cols", C.c_uint32),
+                ("pieces_x", C.c_uint32), ("band_rows", C.c_uint32), ("bands", C.c_uint32), ("segments", C.c_uint32),
+                ("frames_per_segment", C.c_uint32), ("max_frames_per_segment", C.c_uint32), ("grid", C.c_uint64),
+                ("combine_grid", C.c_uint64), ("workspace_bytes", C.c_uint64), ("lds_bytes", C.c_uint32),
+                ("instance", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def _registered_plan(fn, W, H, n_frames, rw, rh, stats, n_cu):
+    """registered_plan / registered16_plan through the C function named fn."""
+    pl = RegisteredProjectPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, rw, rh, stats_mask(stats), n_cu, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{fn}({W}, {H}, {n_frames}, {rw}, {rh}, {stats}) -> {rc}")
+    return pl.as_dict()
+
+
+def registered_plan(W, H, n_frames, rw, rh, stats=("max", "min", "sum", "sumsq"), n_cu=256):
+    """dbde_hip_project_registered_plan: the index geometry, pieces, bands, segments, instance, LDS and workspace of a
+    registered projection (host arithmetic only).  Raises ValueError where dbde_hip_project_registered would return
+    DBDE_HIP_ERR_ARG for its sizes or statistics."""
+    return _registered_plan("dbde_hip_project_registered_plan", W, H, n_frames, rw, rh, stats, n_cu)
+
+
+def registered16_plan(W, H, n_frames, rw, rh, stats=("max", "min", "sum", "sumsq"), n_cu=256):
+    """dbde16_hip_project_registered_plan: registered_plan for DBDE16 streams (Codec.project_registered16)."""
+    return _registered_plan("dbde16_hip_project_registered_plan", W, H, n_frames, rw, rh, stats, n_cu)
 
 
 class LagProjection:
@@ -1936,6 +1978,52 @@ class Codec:
         its statistics are the ones computed.  Returns (Projection, results (n, 4) int64) like decode_frames."""
         return self._project("dbde_hip_project", 1, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh,
                              stats, out, accumulate, results)
+
+    def _project_registered(self, fn, pix, stream, stream_offset, stream_bytes, offsets, W, H, n, rw, rh, origins, stats,
+                            out, accumulate, origins_used, results):
+        """project_registered / project_registered16 through the C function named fn; pix: bytes per pixel."""
+        for name, t in (("origins", origins), ("origins_used", origins_used)):
+            if t is None and name == "origins_used":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+                raise ValueError(f"{name} must be an int32 tensor")
+            if t.device != self.device:
+                raise ValueError(f"{name} must be on {self.device}, not {t.device}")
+            if t.dim() != 2 or t.shape[1] != 2 or t.shape[0] < n:
+                raise ValueError(f"{name} must have shape (>= {n}, 2), not {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs out= (the projection to continue)")
+            out = Projection.empty(rh, rw, stats, self.device, pix=pix)
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(),
+                                 W, H, n, rw, rh, origins.data_ptr(), 1 if accumulate else 0, ptr(out.max),
+                                 ptr(out.min), ptr(out.sum), ptr(out.sumsq), ptr(out.count), ptr(origins_used),
+                                 ptr(results) if n > 0 else None)
+        self._check(rc, fn)
+        return out, results
+
+    def project_registered(self, stream, stream_offset, stream_bytes, offsets, W, H, n, rw, rh, origins,
+                           stats=("max", "min", "sum", "sumsq"), out=None, accumulate=False, origins_used=None,
+                           results=None):
+        """Registered temporal projection: project's statistics of an rw x rh window whose origin moves with the
+        frames.  origins: int32 device tensor (>= n, 2) of per-frame (x, y), clamped into the frame as decode_roi
+        clamps (registration.origins_from_shifts builds it from a registration's shifts).  origins_used: optional
+        int32 device tensor (>= n, 2) that receives the clamped origin of every accepted frame.  out / accumulate /
+        results as in project.  Returns (Projection, results (n, 4) int64); the Projection is in window coordinates."""
+        return self._project_registered("dbde_hip_project_registered", 1, stream, stream_offset, stream_bytes, offsets,
+                                        W, H, n, rw, rh, origins, stats, out, accumulate, origins_used, results)
+
+    def project_registered16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, rw, rh, origins,
+                             stats=("max", "min", "sum", "sumsq"), out=None, accumulate=False, origins_used=None,
+                             results=None):
+        """project_registered for DBDE16 streams: max / min as int16 tensors holding the U16 bits, as project16."""
+        return self._project_registered("dbde16_hip_project_registered", 2, stream, stream_offset, stream_bytes,
+                                        offsets, W, H, n, rw, rh, origins, stats, out, accumulate, origins_used, results)
 
     def _project_weighted(self, fn, stream, stream_offset, stream_bytes, offsets, W, H, n, weights, x, y, rw, rh, out,
                           accumulate, one_segment, results):

@@ -28,6 +28,7 @@
 #include "dbde_patch_kernels.h"
 #include "dbde_project_kernels.h"
 #include "dbde_roi_kernels.h"
+#include "dbde_rproject_kernels.h"
 #include "dbde_scaled_kernels.h"
 #include "dbde_trace_kernels.h"
 #include "dbde_wenc_kernels.h"
@@ -1713,6 +1714,146 @@ int dbde16_hip_project_lag(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t st
     return lag_common(ctx, "project_lag16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh,
                       lag, lead, accumulate, d_product, d_pairsum, d_absdiff, d_sqdiff, d_maxdiff, d_pairs, d_count,
                       d_results);
+}
+
+// ---- registered projections --------------------------------------------------------------
+// The sizes and the index geometry are plan_roi's for the window at (0, 0), whose tile rows are the bands of 8 output
+// rows; the pieces own kRProjColsOf(pix) output columns, and the segment rule is plan_project's applied to that grid.
+static const char *plan_rproject(int W, int H, int n_frames, int rw, int rh, unsigned stats, int n_cu, uint32_t pix,
+                                 ProjectPlan &pl) {
+    if (const char *why = plan_roi(W, H, n_frames, 0, 0, rw, rh, pl.roi, pix == 2u ? kRoi16WideThreads : kRoiWideThreads))
+        return why;
+    if (stats < 1u || stats > kProjAll) return "no statistic (or an unknown one) requested";
+    pl.stats = stats;
+    pl.pieces = ((uint32_t)rw + kRProjColsOf(pix) - 1u) / kRProjColsOf(pix);
+    return plan_project_segments(n_frames, rw, rh, n_cu, pix, pl);
+}
+
+static int rproject_plan_common(int W, int H, int n_frames, int rw, int rh, unsigned stats, int n_cu, uint32_t pix,
+                                dbde_hip_project_registered_plan_t *plan) {
+    ProjectPlan pl;
+    if (!plan || plan_rproject(W, H, n_frames, rw, rh, stats, n_cu, pix, pl)) return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->chunks_per_frame = pl.roi.dg.cpf;
+    plan->chunk_tiles = pl.roi.dg.ct;
+    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
+    plan->index_split = pl.roi.split;
+    plan->threads = kProjThreads;
+    plan->piece_cols = kRProjColsOf(pix);
+    plan->pieces_x = pl.pieces;
+    plan->band_rows = kRProjBandRows;
+    plan->bands = pl.rows;
+    plan->segments = pl.segments;
+    plan->frames_per_segment = pl.fps;
+    plan->max_frames_per_segment = kProjMaxFramesPerSegment;
+    plan->grid = pl.grid;
+    plan->combine_grid = pl.combine_grid;
+    plan->workspace_bytes = pl.workspace;
+    plan->lds_bytes = kRProjLdsBytes;
+    plan->instance = kRProjInstanceOf(stats);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_project_registered_plan(int W, int H, int n_frames, int rw, int rh, unsigned stats, int n_cu,
+                                     dbde_hip_project_registered_plan_t *plan) {
+    return rproject_plan_common(W, H, n_frames, rw, rh, stats, n_cu, 1u, plan);
+}
+
+int dbde16_hip_project_registered_plan(int W, int H, int n_frames, int rw, int rh, unsigned stats, int n_cu,
+                                       dbde_hip_project_registered_plan_t *plan) {
+    return rproject_plan_common(W, H, n_frames, rw, rh, stats, n_cu, 2u, plan);
+}
+
+// Both registered projections: the index (pix: 1 = DBDE, 2 = DBDE16) in timing slot 1, the projection kernels in slot
+// 2.  d_max / d_min hold U8 (pix 1) or U16 (pix 2) pixels.
+static int rproject_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
+                           size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int rw,
+                           int rh, const int32_t *d_origins, int accumulate, void *d_max, void *d_min, uint64_t *d_sum,
+                           uint64_t *d_sumsq, uint64_t *d_count, int32_t *d_origins_used,
+                           dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    const unsigned stats = (d_max ? kProjMax : 0u) | (d_min ? kProjMin : 0u) | (d_sum ? kProjSum : 0u) |
+                           (d_sumsq ? kProjSumSq : 0u);
+    ProjectPlan pl;
+    if (const char *why = plan_rproject(W, H, n_frames, rw, rh, stats, ctx->n_cu, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d)", name, why, W, H, n_frames, rw, rh);
+    if (!d_stream || !d_frame_offsets || !d_count || !d_origins)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if ((reinterpret_cast<uintptr_t>(d_sum) | reinterpret_cast<uintptr_t>(d_sumsq) |
+         reinterpret_cast<uintptr_t>(d_count)) & 7u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U64 outputs must be 8-byte aligned", name);
+    if ((reinterpret_cast<uintptr_t>(d_max) | reinterpret_cast<uintptr_t>(d_min)) & (pix - 1u))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U16 outputs must be 2-byte aligned", name);
+    if ((reinterpret_cast<uintptr_t>(d_origins) | reinterpret_cast<uintptr_t>(d_origins_used)) & 3u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: origins must be 4-byte aligned", name);
+    if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n_frames > 0) {
+        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
+        if (rc) return rc;
+    }
+    RProjParams rp;
+    memset(&rp, 0, sizeof rp);
+    ProjParams &p = rp.pj;
+    if (pl.workspace) {   // the partials in project_workspace_bytes' order: max, min, sum, sumsq, each 16-byte aligned
+        int rc = grow(ctx, ctx->proj_ws, ctx->proj_ws_bytes, (size_t)pl.workspace, 1);
+        if (rc) return rc;
+        const uint64_t n = (uint64_t)pl.segments * (uint64_t)rw * (uint64_t)rh;
+        const uint64_t mm = (pix * n + 15u) & ~(uint64_t)15, u32 = (4u * n + 15u) & ~(uint64_t)15;
+        const uint64_t sq = pix == 1u ? u32 : (8u * n + 15u) & ~(uint64_t)15;
+        uint8_t *w = ctx->proj_ws;
+        if (d_max) { p.ws_max = w; w += mm; }
+        if (d_min) { p.ws_min = w; w += mm; }
+        if (d_sum) { p.ws_sum = reinterpret_cast<uint32_t *>(w); w += u32; }
+        if (d_sumsq) { p.ws_sumsq = reinterpret_cast<uint32_t *>(w); w += sq; }
+    }
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.n_frames = (uint32_t)n_frames;
+    p.rw = rw;
+    p.rh = rh;
+    p.T = pl.roi.g.T;
+    p.w = pl.roi.g.w;
+    p.geom = pl.roi.dg;
+    p.rows = pl.rows;
+    p.pieces = pl.pieces;
+    p.segments = pl.segments;
+    p.fps = pl.fps;
+    p.accumulate = accumulate ? 1 : 0;
+    p.out_max = static_cast<uint8_t *>(d_max);
+    p.out_min = static_cast<uint8_t *>(d_min);
+    p.out_sum = d_sum;
+    p.out_sumsq = d_sumsq;
+    p.out_count = d_count;
+    rp.origins = d_origins;
+    rp.origins_used = d_origins_used;
+    rp.W = W;
+    rp.H = H;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_rproject(rp, stats, pix, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_project_registered(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                                const uint64_t *d_frame_offsets, int W, int H, int n_frames, int rw, int rh,
+                                const int32_t *d_origins, int accumulate, uint8_t *d_max, uint8_t *d_min,
+                                uint64_t *d_sum, uint64_t *d_sumsq, uint64_t *d_count, int32_t *d_origins_used,
+                                dbde_hip_frame_result *d_results) {
+    return rproject_common(ctx, "project_registered", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, rw, rh,
+                           d_origins, accumulate, d_max, d_min, d_sum, d_sumsq, d_count, d_origins_used, d_results);
+}
+
+int dbde16_hip_project_registered(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                                  const uint64_t *d_frame_offsets, int W, int H, int n_frames, int rw, int rh,
+                                  const int32_t *d_origins, int accumulate, uint16_t *d_max, uint16_t *d_min,
+                                  uint64_t *d_sum, uint64_t *d_sumsq, uint64_t *d_count, int32_t *d_origins_used,
+                                  dbde_hip_frame_result *d_results) {
+    return rproject_common(ctx, "project_registered16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, rw,
+                           rh, d_origins, accumulate, d_max, d_min, d_sum, d_sumsq, d_count, d_origins_used, d_results);
 }
 
 // ---- grouped temporal projections --------------------------------------------------------

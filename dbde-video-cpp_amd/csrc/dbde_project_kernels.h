@@ -54,6 +54,9 @@ struct ProjParams {
 // 2 = DBDE16): grid = pieces * rows * segments workgroups of kProjThreads; with segments > 1 the combine kernel follows
 // on the same stream.
 hipError_t launch_project(const ProjParams &p, uint32_t stats, uint32_t pix, hipStream_t s);
+// The combine kernel alone, for a projection kernel of another family that writes project's partials (segments > 1):
+// the partials of the planes of p that are not NULL -> the outputs, and the accepted frames -> *p.out_count.
+hipError_t launch_project_combine(const ProjParams &p, uint32_t pix, hipStream_t s);
 // Bytes of the per-segment partials of a window of `pixels` pixels (0 for one segment), laid out in the order max, min,
 // sum, sumsq, each 16-byte aligned.  pix: 1 = DBDE (U8 max / min, U32 sums), 2 = DBDE16 (U16 max / min, U32 sums, U64
 // sums of squares).

@@ -407,6 +407,11 @@ hipError_t launch_project(const ProjParams &p, uint32_t stats, uint32_t pix, hip
     hipLaunchKernelGGL(tables[pix - 1u].k[stats], dim3(grid), dim3(kProjThreads), 0, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || p.segments == 1u) return e;
+    return launch_project_combine(p, pix, s);
+}
+
+hipError_t launch_project_combine(const ProjParams &p, uint32_t pix, hipStream_t s) {
+    if (pix != 1u && pix != 2u) return hipErrorInvalidValue;
     const uint64_t P = (uint64_t)p.rw * (uint64_t)p.rh;
     const uint32_t cgrid = (uint32_t)((P + kProjCombineThreads - 1u) / kProjCombineThreads);
     const ProjKernel combine = pix == 1u ? project_combine_kernel<1> : project_combine_kernel<2>;

@@ -556,6 +556,45 @@ int dbde16_hip_project_lag(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t st
                            uint64_t *d_product, uint64_t *d_pairsum, uint64_t *d_absdiff, uint64_t *d_sqdiff,
                            uint16_t *d_maxdiff, uint64_t *d_pairs, uint64_t *d_count, dbde_hip_frame_result *d_results);
 
+/* Registered projection: dbde_hip_project's reduction of an rw x rh window whose origin moves from
+ * frame to frame, for recordings that drift under the sensor.  Frame f contributes the window at d_origins[f]; the
+ * planes are indexed in window coordinates, so a feature that a registration tool or a tracker follows stays on one
+ * output pixel.  Straight from the compressed bytes (no image is written).
+ * Origins.  d_origins is a device int32 [n_frames][2] of (x, y), required (NULL is DBDE_HIP_ERR_ARG).  Each origin is
+ *   clamped into [0, W - rw] x [0, H - rh], exactly as dbde_hip_decode_roi clamps its d_origins.  The array is never
+ *   trusted: any int32 value, INT32_MIN and INT32_MAX included, is legal and causes no read outside the frame.  The
+ *   origin of a rejected frame is never used.
+ * The value.  The outputs equal what dbde_hip_project's reduction gives over the windows dbde_hip_decode_roi writes
+ *   for the same stream, rw, rh and d_origins, taken over the accepted frames: bit for bit, every value an exact
+ *   integer, wrapped minima included as dbde_hip_project includes them.  With all origins equal to (x0, y0) the
+ *   result is dbde_hip_project's at that window.
+ * Inputs and outputs:
+ *   The stream, the validation, d_results, the planes (d_max / d_min U8 [rh][rw], d_sum / d_sumsq U64 and 8-byte
+ *   aligned, a NULL plane neither computed nor touched, at least one given), *d_count (required), the empty
+ *   projection, n_frames == 0, the stream_bytes rule (nothing is read at or beyond it) and the timing slots (index 1,
+ *   projection kernels 2) are dbde_hip_project's.  1 <= rw <= W, 1 <= rh <= H.
+ *   accumulate follows dbde_hip_project's rules; any split of the frames, with their origin rows, into consecutive
+ *   accumulating calls gives the one-call result bit for bit.
+ *   d_origins_used: optional device int32 [n_frames][2] that receives the clamped origin of every accepted frame; the
+ *   row of a rejected frame stays untouched.  It shows that clamping happened instead of silently reducing a
+ *   misregistered frame.
+ * Errors: DBDE_HIP_ERR_ARG for everything dbde_hip_project rejects of its sizes and pointers, NULL d_origins, and
+ *   d_origins / d_origins_used that are not 4-byte aligned.
+ * Asynchronous on the context's stream; workspace as dbde_hip_project, with the partials the plan reports.  At most
+ * 65,536 frames per segment, as dbde_hip_project. */
+int dbde_hip_project_registered(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                                const uint64_t *d_frame_offsets, int W, int H, int n_frames, int rw, int rh,
+                                const int32_t *d_origins, int accumulate, uint8_t *d_max, uint8_t *d_min,
+                                uint64_t *d_sum, uint64_t *d_sumsq, uint64_t *d_count, int32_t *d_origins_used,
+                                dbde_hip_frame_result *d_results);
+/* The same for DBDE16 frames: dbde_hip_project_registered's contract with U16 pixels (d_max / d_min U16 and 2-byte
+ * aligned), validated as dbde16_hip_project validates. */
+int dbde16_hip_project_registered(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                                  const uint64_t *d_frame_offsets, int W, int H, int n_frames, int rw, int rh,
+                                  const int32_t *d_origins, int accumulate, uint16_t *d_max, uint16_t *d_min,
+                                  uint64_t *d_sum, uint64_t *d_sumsq, uint64_t *d_count, int32_t *d_origins_used,
+                                  dbde_hip_frame_result *d_results);
+
 /* ---- multi-GPU: variable-length gather of the compressed stream to a root (RCCL over xGMI) ------------------- */
 /* Frames are independent, so the path shards by contiguous frame blocks (rank g of G owns frames
  * [g*N/G, (g+1)*N/G)): every rank encodes its block with dbde_hip_encode_frames (slot_stride 0) and its output is
@@ -992,6 +1031,43 @@ int dbde_hip_project_lag_plan(int W, int H, int n_frames, int x0, int y0, int rw
 int dbde16_hip_project_lag_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int lag, int lead,
                                 unsigned stats, uint64_t sums_address, uint64_t maxdiff_address, uint64_t pairs_address,
                                 uint64_t count_address, int n_cu, dbde_hip_project_lag_plan_t *plan);
+
+/* What dbde_hip_project_registered runs (pure host arithmetic, like dbde_hip_project_plan): validates what the call
+ * validates of its sizes and statistics (DBDE_HIP_ERR_ARG otherwise; `stats` is the mask of the non-NULL planes, max 1,
+ * min 2, sum 4, sumsq 8) and reports the index geometry, the launch and its workspace.  n_cu: compute units of the
+ * device (the call uses its context's).  The formulas:
+ *   piece_cols   output columns one workgroup owns: 8 * (256 / 8 - 1) = 248 (DBDE), 8 * (256 / 16 - 1) = 120 (DBDE16).
+ *   pieces_x     ceil(rw / piece_cols); band_rows = 8; bands = ceil(rh / 8).
+ *   segments, frames_per_segment: dbde_hip_project_plan's rule applied to pieces_x * bands workgroups.
+ *   instance     3 where stats has only max / min, 12 where it has only sum / sumsq, else 15: the kernel instance that
+ *                runs.  It accumulates all of its statistics and stores the requested planes.
+ *   grid         pieces_x * bands * segments; combine_grid = ceil(rw * rh / 256) with more than one segment, else 0.
+ *   workspace_bytes  dbde_hip_project_plan's for the requested statistics; 0 for one segment.
+ *   lds_bytes    2 * 4 * 8 * 68 * 4 (the band: two groups of four frames, 8 rows of 68 dwords) + 2 * 4 * 2 * 32 (the wave
+ *                totals of a group, two tile rows) + 16 (the count's). */
+typedef struct dbde_hip_project_registered_plan_t {
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t threads;                 /* projection kernel: workgroup size */
+    uint32_t piece_cols;              /* output columns per workgroup */
+    uint32_t pieces_x;                /* workgroups across the window */
+    uint32_t band_rows;               /* output rows per workgroup: 8 */
+    uint32_t bands;                   /* workgroups down the window */
+    uint32_t segments;                /* S: frame segments, each reduced by its own workgroups */
+    uint32_t frames_per_segment;      /* fps: frames of every segment but the last (which may hold fewer) */
+    uint32_t max_frames_per_segment;  /* 65,536: keeps the kernel's per-lane sums exact */
+    uint64_t grid;                    /* projection kernel: pieces_x * bands * segments workgroups */
+    uint64_t combine_grid;            /* combine kernel: workgroups (0 = one segment, no combine) */
+    uint64_t workspace_bytes;         /* per-segment partials (0 for one segment) */
+    uint32_t lds_bytes;               /* projection kernel: LDS per workgroup */
+    uint32_t instance;                /* statistics of the kernel instance that runs: 3, 12 or 15 */
+} dbde_hip_project_registered_plan_t;
+int dbde_hip_project_registered_plan(int W, int H, int n_frames, int rw, int rh, unsigned stats, int n_cu,
+                                     dbde_hip_project_registered_plan_t *plan);
+int dbde16_hip_project_registered_plan(int W, int H, int n_frames, int rw, int rh, unsigned stats, int n_cu,
+                                       dbde_hip_project_registered_plan_t *plan);
 
 /* ---- region traces: per frame and per labelled region, max / min / sum / sum of squares ---------- */
 /* A trace map is a label image (H x W int32, row-major, pitch W: 0 = no region, 1..n_labels = region id) classified
