@@ -66,6 +66,7 @@ C_ABI_SYMBOLS = [
     "dbde_hip_decode_mask", "dbde16_hip_decode_mask", "dbde_hip_mask_plan", "dbde16_hip_mask_plan",
     "dbde_hip_decode_patches", "dbde16_hip_decode_patches", "dbde_hip_patches_plan", "dbde16_hip_patches_plan",
     "dbde_hip_patch_moments", "dbde16_hip_patch_moments", "dbde_hip_patch_moments_plan", "dbde16_hip_patch_moments_plan",
+    "dbde_hip_match_patches", "dbde16_hip_match_patches", "dbde_hip_match_plan", "dbde16_hip_match_plan",
     "dbde_hip_crop_frames", "dbde16_hip_crop_frames", "dbde_hip_crop_plan", "dbde16_hip_crop_plan",
     "dbde_hip_encode_window", "dbde16_hip_encode_window", "dbde_hip_window_encode_plan", "dbde16_hip_window_encode_plan",
     "dbde_hip_writer_put_window",
@@ -289,6 +290,13 @@ def lib():
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_patch_moments_plan", "dbde16_hip_patch_moments_plan"):
         getattr(L, fn).argtypes = [i, i, i, i, i, i, i, C.POINTER(PatchMomentsPlan)]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_match_patches", "dbde16_hip_match_patches"):
+        getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, vp, i, C.c_uint32, vp, i, C.c_uint, vp, vp, vp,
+                                   vp, vp]
+        getattr(L, fn).restype = i
+    for fn in ("dbde_hip_match_plan", "dbde16_hip_match_plan"):
+        getattr(L, fn).argtypes = [i, i, i, i, i, i, i, i, i, C.c_uint32, C.c_uint, C.POINTER(MatchPlan)]
         getattr(L, fn).restype = i
     for fn in ("dbde_hip_crop_frames", "dbde16_hip_crop_frames"):
         getattr(L, fn).argtypes = [vp, vp, sz, vp, i, i, i, i, i, i, i, vp, vp, sz, u64, vp, vp, vp, vp]
@@ -1628,6 +1636,164 @@ class PatchMoments:
         return angle, 2 * torch.sqrt(half + root), 2 * torch.sqrt(torch.clamp(half - root, min=0))
 
 
+MATCH_PROD, MATCH_SUM, MATCH_SQ = 1, 2, 4   # DBDE_HIP_MATCH_* (include/dbde_hip.h)
+MATCH_STATS = {"prod": MATCH_PROD, "sum": MATCH_SUM, "sq": MATCH_SQ}
+MATCH_MAX_TEMPLATE, MATCH_MAX_RADIUS = 128, 16
+
+
+def match_mask(stats):
+    """("prod", "sum", "sq") names (or a DBDE_HIP_MATCH_* mask as an int) -> the C-ABI's mask of surfaces."""
+    if isinstance(stats, int):
+        return stats
+    m = 0
+    for s in stats:
+        if s not in MATCH_STATS:
+            raise ValueError(f"stats must be among {sorted(MATCH_STATS)}, not {s!r}")
+        m |= MATCH_STATS[s]
+    return m
+
+
+class MatchPlan(C.Structure):
+    """dbde_hip_match_plan_t (include/dbde_hip.h)."""
+    _fields_ = [("pw", C.c_int32), ("ph", C.c_int32), ("D", C.c_int32), ("max_tiles_x", C.c_int32),
+                ("max_tiles_y", C.c_int32), ("rows_per_wave", C.c_uint32), ("decode_waves", C.c_uint32),
+                ("steps_per_patch", C.c_uint32), ("row_slices", C.c_uint32), ("threads", C.c_uint32),
+                ("chunks_per_frame", C.c_uint32), ("chunk_tiles", C.c_uint32), ("chunk_pieces", C.c_uint32),
+                ("index_split", C.c_uint32), ("lds_bytes", C.c_uint32), ("grid", C.c_uint64), ("surface_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def _match_plan(fn, W, H, n_frames, tw, th, S, n_patches, n_templates, edge, fill, stats):
+    """match_plan / match16_plan through the C function named fn.  What ctypes would take modulo 2^32 is refused here."""
+    mask = match_mask(stats)
+    what = f"{fn}({W}, {H}, {n_frames}, {tw}x{th}, S={S}, {n_patches}, {n_templates}, {edge}, fill={fill}, stats={stats})"
+    if not (0 <= int(fill) < 2 ** 32 and 0 <= mask < 2 ** 32):
+        raise ValueError(f"{what}: fill or stats out of range")
+    pl = MatchPlan()
+    rc = getattr(lib(), fn)(W, H, n_frames, tw, th, S, n_patches, n_templates if n_templates is not None else n_patches,
+                            patch_edge_mode(edge), int(fill), mask, C.byref(pl))
+    if rc != OK:
+        raise ValueError(f"{what} -> {rc}")
+    return pl.as_dict()
+
+
+def match_plan(W, H, n_frames, tw, th, S, n_patches, n_templates=None, edge="clamp", fill=0, stats=("prod", "sum", "sq")):
+    """dbde_hip_match_plan: the search patch and surface sizes, the tiles a search patch can span, the decoding waves and
+    steps, the row slices, the index geometry, LDS, grid and the bytes of one surface of Codec.match_patches (host
+    arithmetic only).  n_templates: 1 or n_patches (the default).  Raises ValueError where dbde_hip_match_patches would
+    return DBDE_HIP_ERR_ARG for these arguments."""
+    return _match_plan("dbde_hip_match_plan", W, H, n_frames, tw, th, S, n_patches, n_templates, edge, fill, stats)
+
+
+def match16_plan(W, H, n_frames, tw, th, S, n_patches, n_templates=None, edge="clamp", fill=0, stats=("prod", "sum", "sq")):
+    """dbde16_hip_match_plan: match_plan for DBDE16 frames (Codec.match_patches16)."""
+    return _match_plan("dbde16_hip_match_plan", W, H, n_frames, tw, th, S, n_patches, n_templates, edge, fill, stats)
+
+
+def best_shift(score, S, maximize=True):
+    """The best entry of score surfaces (..., D, D), D = 2S + 1, row dy + S, column dx + S: the arg-max (maximize=False:
+    the arg-min), NaN never winning; ties go to the smallest |dx| + |dy|, then the smallest dy, then the smallest dx.
+    Returns (shifts int64 (..., 2) as (dx, dy), the score there); an all-NaN surface gives (0, 0) and NaN."""
+    D = 2 * S + 1
+    if score.shape[-2:] != (D, D):
+        raise ValueError(f"score surfaces must end in ({D}, {D})")
+    flat = score.reshape(*score.shape[:-2], D * D)
+    off = torch.arange(D, device=score.device, dtype=torch.int64) - S
+    dy, dx = off[:, None].expand(D, D).reshape(-1), off[None, :].expand(D, D).reshape(-1)
+    rank = ((dx.abs() + dy.abs()) * D + (dy + S)) * D + (dx + S)
+    if flat.is_floating_point():
+        valid = ~torch.isnan(flat)
+        worst = float("-inf") if maximize else float("inf")
+        s = torch.where(valid, flat, torch.full_like(flat, worst))
+    else:
+        valid = torch.ones_like(flat, dtype=torch.bool)
+        s = flat
+    top = (s.max(-1, keepdim=True).values if maximize else s.min(-1, keepdim=True).values)
+    cand = (s == top) & valid
+    pick = torch.where(cand, rank, torch.full_like(rank, 4 * D * D * D)).argmin(-1)
+    none = ~cand.any(-1)
+    pick = torch.where(none, torch.full_like(pick, S * D + S), pick)
+    shifts = torch.stack((dx[pick], dy[pick]), dim=-1)
+    value = flat.gather(-1, pick[..., None])[..., 0]
+    if flat.is_floating_point():
+        value = torch.where(none, torch.full_like(value, float("nan")), value)
+    return shifts, value
+
+
+class PatchMatch:
+    """What Codec.match_patches returns: per frame and patch the D x D surfaces over the shifts -S..S (row dy + S, column
+    dx + S) as int64 (n, K, D, D): prod = sum T P, sum = sum P, sq = sum P^2 over the template's footprint at that shift
+    (None where not requested); used int32 (n, K, 2), the search patches' used origins; t_sum and t_sq int64 (Kt,), the
+    templates' own sum T and sum T^2 (Kt = 1 or K).  Entries of rejected frames and of patches beyond a frame's count
+    hold whatever the tensors held before the call.  The derived quantities are torch tensors on the surfaces' device."""
+
+    def __init__(self, prod, sum, sq, used, t_sum, t_sq, tw, th, S):
+        self.prod, self.sum, self.sq, self.used, self.t_sum, self.t_sq = prod, sum, sq, used, t_sum, t_sq
+        self.tw, self.th, self.S = int(tw), int(th), int(S)
+
+    def _need(self, *names):
+        for nm in names:
+            if getattr(self, nm) is None:
+                raise ValueError(f"the surface {nm!r} was not requested")
+
+    def ssd(self):
+        """sum (T - P)^2 = sum T^2 - 2 prod + sq, int64 (n, K, D, D), exact."""
+        self._need("prod", "sq")
+        return self.t_sq.view(1, -1, 1, 1) - 2 * self.prod + self.sq
+
+    def zncc(self):
+        """The zero-mean normalised cross-correlation, float64 (n, K, D, D), from the exact integers: with N = tw th,
+        (N prod - sum T sum) / sqrt((N sum T^2 - (sum T)^2) (N sq - sum^2)); NaN where the denominator is 0 (a flat
+        template or a flat footprint)."""
+        self._need("prod", "sum", "sq")
+        N = self.tw * self.th
+        ts, tq = self.t_sum.view(1, -1, 1, 1), self.t_sq.view(1, -1, 1, 1)
+        num = (N * self.prod - ts * self.sum).to(torch.float64)        # below 2^61: exact in int64
+        var_t = (N * tq - ts * ts).to(torch.float64)
+        var_p = (N * self.sq - self.sum * self.sum).to(torch.float64)
+        den = torch.sqrt(var_t * var_p)
+        return torch.where(den == 0, torch.full_like(den, float("nan")), num / den)
+
+    def _score(self, score):
+        if score == "zncc":
+            return self.zncc(), True
+        if score == "ssd":
+            return self.ssd(), False
+        raise ValueError("score must be 'zncc' or 'ssd'")
+
+    def best(self, score="zncc"):
+        """(shifts int64 (n, K, 2) as (dx, dy), score (n, K)): the arg-max of zncc (NaN never wins) or the arg-min of
+        ssd; ties go to the smallest |dx| + |dy|, then the smallest dy, then the smallest dx; an all-NaN surface gives
+        (0, 0) and NaN."""
+        s, up = self._score(score)
+        return best_shift(s, self.S, maximize=up)
+
+    def refine(self, score="zncc"):
+        """best's shifts plus the three-point parabolic sub-pixel offset per axis around the best entry, float64
+        (n, K, 2): with l, c, r the scores left of, at and right of the best, 0.5 (l - r) / (l - 2 c + r); 0 on the
+        border of the surface, and where a neighbour is NaN or the three lie on a line."""
+        s, up = self._score(score)
+        shifts, _ = best_shift(s, self.S, maximize=up)
+        s = s.to(torch.float64)
+        D = 2 * self.S + 1
+        col, row = shifts[..., 0] + self.S, shifts[..., 1] + self.S
+
+        def at(r, c):
+            idx = (r.clamp(0, D - 1) * D + c.clamp(0, D - 1))[..., None]
+            return s.reshape(*s.shape[:-2], D * D).gather(-1, idx)[..., 0]
+
+        out = []
+        for lo, hi, pos in ((at(row, col - 1), at(row, col + 1), col), (at(row - 1, col), at(row + 1, col), row)):
+            c = at(row, col)
+            den = lo - 2 * c + hi
+            off = 0.5 * (lo - hi) / den
+            ok = (pos > 0) & (pos < D - 1) & torch.isfinite(off)
+            out.append(torch.where(ok, off, torch.zeros_like(off)))
+        return shifts.to(torch.float64) + torch.stack(out, dim=-1)
+
+
 class CropPlan(C.Structure):
     """dbde_hip_crop_plan_t (include/dbde_hip.h)."""
     _fields_ = [("tile_x", C.c_int32), ("tile_y", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
@@ -2610,6 +2776,83 @@ class Codec:
         """DBDE16 patch moments: patch_moments' arguments and results over U16 pixels (lo, hi up to 65535)."""
         return self._patch_moments("dbde16_hip_patch_moments", stream, stream_offset, stream_bytes, offsets, W, H, n,
                                    pw, ph, origins, lo, hi, weight, counts, edge, out, bbox, used, results)
+
+    def _match_patches(self, fn, dtype, stream, stream_offset, stream_bytes, offsets, W, H, n, templates, S, origins,
+                       counts, edge, fill, stats, out, used, results):
+        """match_patches / match_patches16 through the C function named fn; dtype: the templates' tensor type."""
+        if (not torch.is_tensor(origins) or origins.dtype != torch.int32 or origins.dim() != 3 or origins.shape[0] != n
+                or origins.shape[2] != 2 or not origins.is_contiguous()):
+            raise ValueError("origins must be a contiguous int32 device tensor of shape (n, K, 2)")
+        K = int(origins.shape[1])
+        if (not torch.is_tensor(templates) or templates.dtype != dtype or templates.dim() != 3
+                or not templates.is_contiguous() or templates.shape[0] not in (1, K)):
+            raise ValueError(f"templates must be a contiguous {dtype} device tensor of shape (K, th, tw) or (1, th, tw)")
+        Kt, th, tw = (int(v) for v in templates.shape)
+        if counts is not None and (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 1
+                                   or counts.numel() != n or not counts.is_contiguous()):
+            raise ValueError("counts must be a contiguous 1-D int32 tensor of n entries (the U32 bits)")
+        # what the C call refuses of the scalars, checked here as well: the call is not made when n == 0, and ctypes would
+        # take them modulo 2^32 before the C range check sees them
+        S, fill, mask = int(S), int(fill), match_mask(stats)
+        try:
+            pl = _match_plan(fn.replace("match_patches", "match_plan"), W, H, max(n, 0), tw, th, S, max(K, 1),
+                             Kt if K > 0 else 1, edge, fill, mask)
+        except ValueError as e:
+            raise DbdeError(f"{fn}: {e}") from None
+        D = pl["D"]
+        if used is None:
+            used = torch.empty((n, K, 2), dtype=torch.int32, device=self.device)
+        elif not torch.is_tensor(used) or used.dtype != torch.int32 or not used.is_contiguous() or used.numel() < 2 * n * K:
+            raise ValueError("used must be a contiguous int32 device tensor of at least n * K * 2 entries")
+        names = ("prod", "sum", "sq")
+        if out is None:
+            out = {}
+        elif not isinstance(out, dict) or any(k not in names for k in out):
+            raise ValueError("out must be a dict of int64 tensors under 'prod', 'sum', 'sq'")
+        surf = []
+        for bit, nm in enumerate(names):
+            t = out.get(nm)
+            if not mask >> bit & 1:
+                t = None
+            elif t is None:
+                t = torch.empty((n, K, D, D), dtype=torch.int64, device=self.device)
+            elif not torch.is_tensor(t) or t.dtype != torch.int64 or not t.is_contiguous() or t.numel() < n * K * D * D:
+                raise ValueError(f"out[{nm!r}] must be a contiguous int64 device tensor of at least n * K * D * D entries")
+            surf.append(t)
+        t64 = templates.to(torch.int64)
+        if dtype == torch.int16:
+            t64 = t64 & 0xFFFF
+        pm = PatchMatch(surf[0], surf[1], surf[2], used, t64.sum((1, 2)), (t64 * t64).sum((1, 2)), tw, th, S)
+        if results is None:
+            results = torch.empty((max(n, 0), 4), dtype=torch.int64, device=self.device)
+        if n == 0 or K == 0:   # nothing to do (empty tensors have no address to pass): the sizes are checked above
+            return pm, results
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        rc = getattr(self.L, fn)(self.h, stream.data_ptr() + stream_offset, stream_bytes, offsets.data_ptr(), W, H, n,
+                                 tw, th, S, K, origins.data_ptr(), ptr(counts), patch_edge_mode(edge), fill,
+                                 templates.data_ptr(), Kt, mask, ptr(surf[0]), ptr(surf[1]), ptr(surf[2]),
+                                 used.data_ptr(), ptr(results))
+        self._check(rc, fn)
+        return pm, results
+
+    def match_patches(self, stream, stream_offset, stream_bytes, offsets, W, H, n, templates, S, origins, counts=None,
+                      edge="clamp", fill=0, stats=("prod", "sum", "sq"), out=None, used=None, results=None):
+        """Correlation surfaces of K templates over the shifts -S..S in x and y, per frame of n frames (frame f at
+        stream.data_ptr()+stream_offset+offsets[f]), straight from the stream: no pixel is written.  templates: uint8
+        device tensor (K, th, tw), or (1, th, tw) for one template shared by all patches.  origins: int32 (n, K, 2), the
+        (x, y) of the SEARCH patches of (tw + 2S) x (th + 2S) pixels (registration.search_origins makes them from the
+        templates' positions); counts, edge and fill as in decode_patches, a fill pixel counting like any other.
+        stats: the surfaces wanted among "prod", "sum", "sq"; out: optional dict of int64 tensors to write them into;
+        used: optional int32 (n, K, 2).  Returns (PatchMatch, results (n, 4) int64) like decode_frames."""
+        return self._match_patches("dbde_hip_match_patches", torch.uint8, stream, stream_offset, stream_bytes, offsets, W,
+                                   H, n, templates, S, origins, counts, edge, fill, stats, out, used, results)
+
+    def match_patches16(self, stream, stream_offset, stream_bytes, offsets, W, H, n, templates, S, origins, counts=None,
+                        edge="clamp", fill=0, stats=("prod", "sum", "sq"), out=None, used=None, results=None):
+        """DBDE16 patch match: match_patches' arguments and results over U16 pixels; templates are int16 tensors holding
+        the U16 bits (as decode_frames16 returns its images), fill up to 65535."""
+        return self._match_patches("dbde16_hip_match_patches", torch.int16, stream, stream_offset, stream_bytes, offsets,
+                                   W, H, n, templates, S, origins, counts, edge, fill, stats, out, used, results)
 
     def _crop_frames(self, fn, stream, stream_offset, stream_bytes, offsets, W, H, n, x, y, rw, rh, out, out_offset,
                      capacity, origins, slot_stride, out_offsets, out_bytes, origins_used, results):

@@ -24,6 +24,7 @@
 #include "dbde_hist_kernels.h"
 #include "dbde_kernels.h"
 #include "dbde_mask_kernels.h"
+#include "dbde_match_kernels.h"
 #include "dbde_moment_kernels.h"
 #include "dbde_patch_kernels.h"
 #include "dbde_project_kernels.h"
@@ -3217,6 +3218,178 @@ int dbde16_hip_patch_moments(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t 
     return patch_moments_common(ctx, "patch_moments16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, pw,
                                 ph, n_patches, d_origins, d_counts, edge_mode, lo, hi, weight_mode, d_moments, d_bbox,
                                 d_used, d_results);
+}
+
+// ---- patch match --------------------------------------------------------------------------------------------
+// The search patch's size and the edge mode go through the patch decoder's plan (plan_patches); what is added are the
+// template and radius limits that keep an 8-bit entry inside 32 bits, the split of a shift's rows over lanes, and the LDS.
+struct MatchPlan {
+    PatchPlan pp;
+    int pw, ph;
+    uint32_t D, dwaves, steps, slices;
+    MatchLayout lds;
+    uint64_t surface_bytes;
+};
+static const char *plan_match(int W, int H, int n_frames, int tw, int th, int S, int n_patches, int n_templates,
+                              int edge_mode, uint32_t fill, unsigned stats, uint32_t pix, MatchPlan &pl) {
+    if (tw < 1 || th < 1 || tw > kMatchMaxTemplate || th > kMatchMaxTemplate) return "template size outside [1, 128]";
+    if (S < 0 || S > kMatchMaxRadius) return "search radius outside [0, 16]";
+    pl.pw = tw + 2 * S;
+    pl.ph = th + 2 * S;
+    if (const char *why = plan_patches(W, H, n_frames, pl.pw, pl.ph, n_patches, edge_mode, pix, pl.pp)) return why;
+    if (fill > (pix == 1u ? 0xFFu : 0xFFFFu)) return "fill above the pixel type";
+    if (n_templates != 1 && n_templates != n_patches) return "n_templates is neither 1 nor n_patches";
+    if (stats == 0u || (stats & ~7u)) return "stats empty or with unknown bits";
+    static_assert(kMatchClamp == DBDE_HIP_PATCH_CLAMP && kMatchFill == DBDE_HIP_PATCH_FILL, "edge modes");
+    static_assert(kMatchProd == DBDE_HIP_MATCH_PROD && kMatchSum == DBDE_HIP_MATCH_SUM && kMatchSq == DBDE_HIP_MATCH_SQ, "surfaces");
+    static_assert(kPatchThreads == 64u, "plan_patches' G is tile rows per wave");
+    pl.D = 2u * (uint32_t)S + 1u;
+    pl.dwaves = pl.pp.groups < kMatchWaves ? pl.pp.groups : kMatchWaves;
+    pl.steps = (pl.pp.groups + pl.dwaves - 1u) / pl.dwaves;
+    // the row slices: a lane's cost is its passes over the items times an item's cost, the batches of kMatchBatch dwords
+    // in the rows of its slice plus a fixed part: ceil(nsh r / 256) * (ceil(th / r) * batches + kMatchItemCost).  The count
+    // up to 16 (and th) with the least cost, the smallest on a tie
+    const uint32_t nsh = pl.D * pl.D, rmax = (uint32_t)th < kMatchMaxSlices ? (uint32_t)th : kMatchMaxSlices;
+    const uint32_t batches = (((uint32_t)tw * pix + 3u) / 4u + kMatchBatch - 1u) / kMatchBatch;
+    uint32_t best = 0xFFFFFFFFu;
+    pl.slices = 1u;
+    for (uint32_t r = 1; r <= rmax; r++) {
+        const uint32_t passes = (nsh * r + kMatchThreads - 1u) / kMatchThreads;
+        const uint32_t cost = passes * ((((uint32_t)th + r - 1u) / r) * batches + kMatchItemCost);
+        if (cost < best) {
+            best = cost;
+            pl.slices = r;
+        }
+    }
+    pl.lds = match_layout(pix, (uint32_t)tw, (uint32_t)th, (uint32_t)S, pl.pp.mtx, pl.pp.mty, pl.pp.G, pl.dwaves, pl.slices);
+    pl.surface_bytes = (uint64_t)n_frames * (uint64_t)n_patches * nsh * 8u;   // (below 2^31 * 1089 * 8)
+    return nullptr;
+}
+
+static int match_plan_common(int W, int H, int n_frames, int tw, int th, int S, int n_patches, int n_templates,
+                             int edge_mode, uint32_t fill, unsigned stats, uint32_t pix, dbde_hip_match_plan_t *plan) {
+    MatchPlan pl;
+    memset(&pl, 0, sizeof pl);
+    if (!plan || plan_match(W, H, n_frames, tw, th, S, n_patches, n_templates, edge_mode, fill, stats, pix, pl))
+        return DBDE_HIP_ERR_ARG;
+    memset(plan, 0, sizeof *plan);
+    plan->pw = pl.pw;
+    plan->ph = pl.ph;
+    plan->D = (int32_t)pl.D;
+    plan->max_tiles_x = (int32_t)pl.pp.mtx;
+    plan->max_tiles_y = (int32_t)pl.pp.mty;
+    plan->rows_per_wave = pl.pp.G;
+    plan->decode_waves = pl.dwaves;
+    plan->steps_per_patch = pl.steps;
+    plan->row_slices = pl.slices;
+    plan->threads = kMatchThreads;
+    plan->chunks_per_frame = pl.pp.dg.cpf;
+    plan->chunk_tiles = pl.pp.dg.ct;
+    plan->chunk_pieces = pl.pp.dg.ct == pl.pp.g.w || pl.pp.dg.pieces > 1u ? pl.pp.dg.pieces : 0u;
+    plan->index_split = pl.pp.split;
+    plan->lds_bytes = pl.lds.bytes;
+    plan->grid = (uint64_t)n_frames * (uint64_t)n_patches;
+    plan->surface_bytes = pl.surface_bytes;
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_match_plan(int W, int H, int n_frames, int tw, int th, int S, int n_patches, int n_templates,
+                        int edge_mode, uint32_t fill, unsigned stats, dbde_hip_match_plan_t *plan) {
+    return match_plan_common(W, H, n_frames, tw, th, S, n_patches, n_templates, edge_mode, fill, stats, 1u, plan);
+}
+
+int dbde16_hip_match_plan(int W, int H, int n_frames, int tw, int th, int S, int n_patches, int n_templates,
+                          int edge_mode, uint32_t fill, unsigned stats, dbde_hip_match_plan_t *plan) {
+    return match_plan_common(W, H, n_frames, tw, th, S, n_patches, n_templates, edge_mode, fill, stats, 2u, plan);
+}
+
+// Both calls: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the match kernel in slot 2.
+static int match_patches_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
+                                size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int tw,
+                                int th, int S, int n_patches, const int32_t *d_origins, const uint32_t *d_counts,
+                                int edge_mode, uint32_t fill, const void *d_templates, int n_templates, unsigned stats,
+                                uint64_t *d_prod, uint64_t *d_sum, uint64_t *d_sq, int32_t *d_used,
+                                dbde_hip_frame_result *d_results) {
+    if (!ctx) return DBDE_HIP_ERR_ARG;
+    MatchPlan pl;
+    memset(&pl, 0, sizeof pl);
+    if (const char *why = plan_match(W, H, n_frames, tw, th, S, n_patches, n_templates, edge_mode, fill, stats, pix, pl))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d, %d patches, %d templates of %dx%d, radius %d, edge mode %d, "
+                    "fill %u, stats %u)", name, why, W, H, n_frames, n_patches, n_templates, tw, th, S, edge_mode, fill, stats);
+    if (!d_stream || !d_frame_offsets || !d_origins || !d_templates) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
+    if (reinterpret_cast<uintptr_t>(d_templates) & (pix - 1u))
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the templates must be %u-byte aligned", name, pix);
+    uint64_t *const surf[3] = {d_prod, d_sum, d_sq};
+    for (int i = 0; i < 3; i++)
+        if ((stats >> i & 1u) && (!surf[i] || (reinterpret_cast<uintptr_t>(surf[i]) & 7u)))
+            return fail(ctx, DBDE_HIP_ERR_ARG, "%s: a requested surface is null or not 8-byte aligned", name);
+    if ((reinterpret_cast<uintptr_t>(d_origins) | reinterpret_cast<uintptr_t>(d_counts) | reinterpret_cast<uintptr_t>(d_used)) & 3u)
+        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: origins, counts and used origins must be 4-byte aligned", name);
+    if (n_frames == 0) return DBDE_HIP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.pp.dg, pix, pl.pp.split);
+    if (rc) return rc;
+
+    MatchParams p;
+    memset(&p, 0, sizeof p);
+    p.stream = d_stream;
+    p.frame_offsets = d_frame_offsets;
+    p.stream_bytes = stream_bytes;
+    p.chunk_off = ctx->chunk_off;
+    p.frame_ok = ctx->frame_ok;
+    p.origins = d_origins;
+    p.counts = d_counts;
+    p.templates = static_cast<const uint8_t *>(d_templates);
+    p.prod = (stats & DBDE_HIP_MATCH_PROD) ? d_prod : nullptr;
+    p.sum = (stats & DBDE_HIP_MATCH_SUM) ? d_sum : nullptr;
+    p.sq = (stats & DBDE_HIP_MATCH_SQ) ? d_sq : nullptr;
+    p.used = d_used;
+    p.W = W;
+    p.H = H;
+    p.pw = pl.pw;
+    p.ph = pl.ph;
+    p.tw = (uint32_t)tw;
+    p.th = (uint32_t)th;
+    p.D = pl.D;
+    p.n_patches = (uint32_t)n_patches;
+    p.per_patch = n_templates == 1 ? 0u : 1u;
+    p.w = pl.pp.g.w;
+    p.h = pl.pp.g.h;
+    p.T = pl.pp.g.T;
+    p.geom = pl.pp.dg;
+    p.mtx = pl.pp.mtx;
+    p.G = pl.pp.G;
+    p.dwaves = pl.dwaves;
+    p.steps = pl.steps;
+    p.slices = pl.slices;
+    p.mode = edge_mode == DBDE_HIP_PATCH_FILL ? kMatchFill : kMatchClamp;
+    p.fill = fill;
+    p.stats = stats;
+    p.lds = pl.lds;
+    span_begin(ctx, 2);
+    HIP_TRY(ctx, launch_match_patches(p, (uint32_t)n_frames, pix, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int dbde_hip_match_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int tw, int th, int S,
+                           int n_patches, const int32_t *d_origins, const uint32_t *d_counts, int edge_mode, uint32_t fill,
+                           const uint8_t *d_templates, int n_templates, unsigned stats, uint64_t *d_prod, uint64_t *d_sum,
+                           uint64_t *d_sq, int32_t *d_used, dbde_hip_frame_result *d_results) {
+    return match_patches_common(ctx, "match_patches", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, tw, th, S,
+                                n_patches, d_origins, d_counts, edge_mode, fill, d_templates, n_templates, stats, d_prod,
+                                d_sum, d_sq, d_used, d_results);
+}
+
+int dbde16_hip_match_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                             const uint64_t *d_frame_offsets, int W, int H, int n_frames, int tw, int th, int S,
+                             int n_patches, const int32_t *d_origins, const uint32_t *d_counts, int edge_mode, uint32_t fill,
+                             const uint16_t *d_templates, int n_templates, unsigned stats, uint64_t *d_prod, uint64_t *d_sum,
+                             uint64_t *d_sq, int32_t *d_used, dbde_hip_frame_result *d_results) {
+    return match_patches_common(ctx, "match_patches16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, tw, th,
+                                S, n_patches, d_origins, d_counts, edge_mode, fill, d_templates, n_templates, stats, d_prod,
+                                d_sum, d_sq, d_used, d_results);
 }
 
 // ---- compressed-domain crop ---------------------------------------------------------------------------------

@@ -1,16 +1,19 @@
 """Registered summary images from Codec.project_registered: rigid integer shifts -> per-frame window
 origins -> max / min / sum / sumsq images in the template's coordinates, straight from the compressed stream.
 
-The shifts come from elsewhere: a registration tool's one integer (dx, dy) per frame, or tracking.follow's fiducial
-centres (shifts_from_centres).  The convention is
+The shifts come from a registration tool's one integer (dx, dy) per frame, from tracking.follow's fiducial centres
+(shifts_from_centres), or from estimate_shifts / estimate_file below: block matching of a few templates of a reference
+image over a search radius (Codec.match_patches).  The convention is
 
     registered[Y][X] = frame_f[Y + dy_f][X + dx_f]
 
 so (dx_f, dy_f) is where the template's pixel (0, 0) lies in frame f.  origins_from_shifts turns the shifts into the
 window every frame can serve and its per-frame origins; registered_image and registered_file reduce over it.
 
-Out of scope here: estimating the shifts by correlation, sub-pixel and piecewise-rigid registration, and a fill mode
-for pixels that leave the frame (the common window holds only pixels every frame has).
+Out of scope here: applying sub-pixel or piecewise-rigid shifts (estimate_shifts reports the per-patch field and
+PatchMatch.refine the sub-pixel offsets, project_registered takes one integer origin per frame), FFT correlation of
+whole frames, rotation and scale, and a fill mode for pixels that leave the frame (the common window holds only pixels
+every frame has).
 """
 import numpy as np
 import torch
@@ -151,3 +154,110 @@ def registered_file(codec, path, shifts, stats=("max", "min", "sum", "sumsq"), b
             if plane is not None:
                 plane.fill_(fill)
     return pr, at, results
+
+
+def _as_positions(positions, device=None):
+    p = torch.as_tensor(positions, device=device)
+    if p.dim() != 2 or p.shape[1] != 2 or p.shape[0] < 1:
+        raise ValueError("positions must have shape (K, 2) with K >= 1")
+    if p.dtype.is_floating_point or p.dtype == torch.bool or p.dtype.is_complex:
+        raise ValueError("positions must be integers")
+    return p.to(torch.int64)
+
+
+def templates_from_image(image, positions, tw, th):
+    """(K, th, tw) slices of a reference image (H, W) at the (x, y) `positions` (K, 2), on the image's device and in its
+    type: a decoded frame, or project's rounded mean.  A slice must lie inside the image."""
+    if not torch.is_tensor(image) or image.dim() != 2:
+        raise ValueError("image must be a 2-D tensor")
+    H, W = image.shape
+    pos = _as_positions(positions).tolist()
+    for x, y in pos:
+        if not (0 <= x <= W - tw and 0 <= y <= H - th):
+            raise ValueError(f"a {tw} x {th} template at ({x}, {y}) leaves the {W} x {H} image")
+    return torch.stack([image[y:y + th, x:x + tw] for x, y in pos]).contiguous()
+
+
+def search_origins(positions, S, n, device=None):
+    """The search patches' origins for Codec.match_patches: positions (K, 2) - S, for each of n frames, int32 (n, K, 2)
+    on the positions' device (or `device`)."""
+    p = _as_positions(positions, device)
+    return (p - int(S)).clamp(-2 ** 31, 2 ** 31 - 1).to(torch.int32)[None].expand(int(n), -1, -1).contiguous()
+
+
+def _shifts_of(pm, results):
+    """PatchMatch of a batch -> (shifts int32 (n, 2), score (n,), per-patch shifts int32 (n, K, 2))."""
+    from . import accepted_frames, best_shift
+    z = pm.zncc()
+    ok = accepted_frames(results).to(torch.bool)
+    z = torch.where(ok.view(-1, 1, 1, 1), z, torch.full_like(z, float("nan")))   # a rejected frame's surfaces are not written
+    per_patch, _ = best_shift(z, pm.S)
+    mean = torch.nanmean(z, dim=1)   # over the patches; NaN where every patch is NaN
+    shifts, score = best_shift(mean, pm.S)
+    return shifts.to(torch.int32), score, per_patch.to(torch.int32)
+
+
+def _match(codec, bits):
+    if bits not in (8, 16):
+        raise ValueError("bits must be 8 or 16")
+    return codec.match_patches if bits == 8 else codec.match_patches16
+
+
+def estimate_shifts(codec, stream, stream_offset, stream_bytes, offsets, W, H, n, reference, positions, tw, th, S, bits=8,
+                    edge="clamp"):
+    """Rigid integer shifts of n frames against a reference image, by block matching straight from the compressed
+    stream: K templates of tw x th are cut out of `reference` (H, W; uint8, or int16 holding U16 bits for bits=16) at
+    `positions` (K, 2) and searched over -S..S in x and y in every frame (Codec.match_patches).
+    Returns (shifts int32 (n, 2), score (n,), per-patch shifts int32 (n, K, 2)).  The per-frame shift is the arg-max,
+    under PatchMatch.best's tie rule, of the mean over the patches of zncc(), NaNs ignored; a frame whose every entry
+    is NaN gets (0, 0) and score NaN, as does a rejected frame.  The per-patch shifts are each patch's own best: the
+    piecewise-rigid field.  Sign: a template cut at (X, Y) of the reference and found at (X + dx, Y + dy) of frame f
+    means registered[Y][X] = frame[Y + dy][X + dx], so the shifts feed origins_from_shifts unchanged."""
+    templates = templates_from_image(reference, positions, tw, th)
+    origins = search_origins(positions, S, n, codec.device)
+    pm, results = _match(codec, bits)(stream, stream_offset, stream_bytes, offsets, W, H, n, templates, S, origins, edge=edge)
+    return _shifts_of(pm, results)
+
+
+def estimate_file(codec, path, reference, positions, tw, th, S, batch=64, edge="clamp"):
+    """estimate_shifts of a .dbde file that need not fit in device memory: the file is read once in pieces that hold
+    `batch` frames (registered_file's reading loop), each piece is indexed on the device and matched.  Every frame is
+    matched on its own, so the result equals the one-call result.  .dbde files hold 8-bit frames.
+    Returns (shifts int32 (N, 2), score (N,), per-patch shifts (N, K, 2)) over the N frames of the file."""
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    parts = []
+    K = _as_positions(positions).shape[0]
+    with open(path, "rb") as src:
+        _, (_, H, W, _) = unpack_video_header(np.frombuffer(src.read(28), np.uint8))
+        W, H = int(W), int(H)
+        templates = templates_from_image(reference, positions, tw, th)
+        T = tiles(W, H)
+        piece = batch * max_frame_bytes(W, H)          # always holds `batch` whole frames, unless the file ends
+        carry = b""
+        while True:
+            data = carry + src.read(max(piece - len(carry), 0))
+            if len(data) < 32 + 2 * T:
+                break   # the end, or a cut frame behind the last whole one
+            buf = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(codec.device)
+            offs, n = codec.index_stream(buf, 0, len(data), W, H, batch + 1)
+            m = min(n, batch)
+            if m == 0:
+                break
+            pm, res = codec.match_patches(buf, 0, len(data), offs, W, H, m, templates, S,
+                                          search_origins(positions, S, m, codec.device), edge=edge)
+            parts.append(_shifts_of(pm, res))
+            if m < n:
+                end = int(offs[m].item())
+            else:
+                last = int(offs[m - 1].item())
+                n64 = int.from_bytes(data[last + 28 + 2 * T: last + 32 + 2 * T], "little")
+                end = last + 32 + 2 * T + 8 * n64
+            codec.sync()   # the piece's buffer is released below
+            carry = data[end:]
+    if not parts:
+        dev = codec.device
+        return (torch.empty((0, 2), dtype=torch.int32, device=dev), torch.empty((0,), dtype=torch.float64, device=dev),
+                torch.empty((0, K, 2), dtype=torch.int32, device=dev))
+    return tuple(torch.cat([p[i] for p in parts]) for i in range(3))

@@ -1557,6 +1557,76 @@ int dbde_hip_patch_moments_plan(int W, int H, int n_frames, int pw, int ph, int 
 int dbde16_hip_patch_moments_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
                                   dbde_hip_patch_moments_plan_t *plan);
 
+/* ---- patch match: correlation surfaces of templates over a shift search ------------------------- */
+/* Patch match: for each of n_patches search patches per frame, each with its own origin per frame (as in
+ * dbde_hip_decode_patches), the correlation surfaces of a tw x th template over every integer shift of a search radius
+ * S, straight from the compressed stream by ONE index pass and one kernel; no pixel is written.  The search patch is
+ * pw = tw + 2S wide and ph = th + 2S high; d_origins are the SEARCH PATCH's origins, so a template at zero shift sits at
+ * origin + (S, S).  Stream, offsets, d_origins, d_counts, edge_mode, fill, d_used (the search patch's used origin),
+ * d_results and validation are dbde_hip_decode_patches' own.
+ *   d_templates: device pixels [n_templates][th][tw], contiguous, aligned to the pixel size, required; n_templates is 1
+ *     (every patch uses template 0) or n_patches (patch k uses template k).
+ *   stats: a mask of DBDE_HIP_MATCH_PROD, _SUM, _SQ: the surfaces to write.
+ *   d_prod, d_sum, d_sq: device uint64 [n_frames][n_patches][D][D], D = 2S + 1, 8-byte aligned; a surface not in stats
+ *     may be NULL and is not written.  With P the ph x pw patch dbde_hip_decode_patches writes for the same stream,
+ *     origins, edge mode, fill, pw and ph, the entry at row dy + S, column dx + S (-S <= dy, dx <= S) is, over
+ *     0 <= i < th, 0 <= j < tw:
+ *         prod = sum T[i][j] * P[i + dy + S][j + dx + S]
+ *         sum  = sum           P[i + dy + S][j + dx + S]
+ *         sq   = sum           P[i + dy + S][j + dx + S]^2
+ *     In FILL mode the pixels outside the frame are `fill` and take part like any other pixel (decode_patches' rule, not
+ *     patch_moments').  All values are exact integers: an 8-bit entry is at most 128^2 * 255^2 < 2^32, a 16-bit entry
+ *     at most 128^2 * 65535^2 < 2^46.
+ * A rejected frame, and a patch k >= min(d_counts[f], n_patches), leave their surfaces and used entries untouched; the
+ * caller zeroes nothing beforehand, every live entry is written once by plain stores.  No byte at or beyond
+ * stream_bytes is read; nothing outside the requested surfaces and d_used is written.  n_frames == 0 does nothing.
+ * DBDE_HIP_ERR_ARG: tw or th outside [1, 128]; S outside [0, 16]; whatever dbde_hip_decode_patches refuses for that pw,
+ * ph, edge mode and fill; n_templates neither 1 nor n_patches; stats empty or with unknown bits; a requested surface
+ * that is NULL or not 8-byte aligned; a null stream, offsets, origins or templates; templates not aligned to the pixel
+ * size.  Asynchronous on the context's stream; timing hook: the index kernel in slot 1, the match kernel in slot 2. */
+enum { DBDE_HIP_MATCH_PROD = 1, DBDE_HIP_MATCH_SUM = 2, DBDE_HIP_MATCH_SQ = 4 };
+int dbde_hip_match_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                           const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                           int tw, int th, int S, int n_patches, const int32_t *d_origins, const uint32_t *d_counts,
+                           int edge_mode, uint32_t fill, const uint8_t *d_templates, int n_templates, unsigned stats,
+                           uint64_t *d_prod, uint64_t *d_sum, uint64_t *d_sq, int32_t *d_used,
+                           dbde_hip_frame_result *d_results);
+/* Patch match of DBDE16 frames: the same contract over U16 pixels (templates U16, 2-byte aligned; fill up to 65535).
+ * Validation is dbde16_hip_decode_frames' own. */
+int dbde16_hip_match_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
+                             const uint64_t *d_frame_offsets, int W, int H, int n_frames,
+                             int tw, int th, int S, int n_patches, const int32_t *d_origins, const uint32_t *d_counts,
+                             int edge_mode, uint32_t fill, const uint16_t *d_templates, int n_templates, unsigned stats,
+                             uint64_t *d_prod, uint64_t *d_sum, uint64_t *d_sq, int32_t *d_used,
+                             dbde_hip_frame_result *d_results);
+/* What dbde_hip_match_patches runs (pure host arithmetic, shared with the call): refuses exactly the arguments the call
+ * refuses, pointers aside (DBDE_HIP_ERR_ARG), and reports the launch.  ONE 256-lane workgroup takes a whole search
+ * patch: up to four of its waves decode a group of rows_per_wave = max(1, 64 / max_tiles_x) tile rows each per step,
+ * one tile per lane, into LDS; then lane t takes the items t, t + 256, ... of the D * D * row_slices (shift, slice)
+ * pairs, a slice being every row_slices-th template row. */
+typedef struct dbde_hip_match_plan_t {
+    int32_t pw, ph;                   /* the search patch: tw + 2S, th + 2S */
+    int32_t D;                        /* 2S + 1: a surface is D x D */
+    int32_t max_tiles_x, max_tiles_y; /* the most tiles any origin makes the search patch span, as dbde_hip_patches_plan */
+    uint32_t rows_per_wave;           /* tile rows a decoding wave takes per step */
+    uint32_t decode_waves;            /* waves that decode: min(4, ceil(max_tiles_y / rows_per_wave)) */
+    uint32_t steps_per_patch;         /* steps of the decode loop */
+    uint32_t row_slices;              /* lanes that share a shift (1: a lane owns its shift, no LDS accumulators) */
+    uint32_t threads;                 /* workgroup size: 256 */
+    uint32_t chunks_per_frame;        /* index: chunks per frame (dbde_hip_roi_plan's geometry) */
+    uint32_t chunk_tiles;             /* index: tiles per chunk */
+    uint32_t chunk_pieces;            /* index: chunks per tile row, 0 = plain 512-tile chunks */
+    uint32_t index_split;             /* index: workgroups per frame */
+    uint32_t lds_bytes;               /* LDS per workgroup: the band, the template, the payload ranges / accumulators */
+    uint64_t grid;                    /* workgroups: n_frames * n_patches */
+    uint64_t surface_bytes;           /* n_frames * n_patches * D * D * 8, of ONE surface */
+} dbde_hip_match_plan_t;
+int dbde_hip_match_plan(int W, int H, int n_frames, int tw, int th, int S, int n_patches, int n_templates,
+                        int edge_mode, uint32_t fill, unsigned stats, dbde_hip_match_plan_t *plan);
+/* The same for dbde16_hip_match_patches: its index, LDS and fill limit. */
+int dbde16_hip_match_plan(int W, int H, int n_frames, int tw, int th, int S, int n_patches, int n_templates,
+                          int edge_mode, uint32_t fill, unsigned stats, dbde_hip_match_plan_t *plan);
+
 /* ---- compressed-domain crop: a window of each frame as a new stream ------------------------------ */
 /* Crops the rw x rh window at (x0, y0) out of each of n_frames DBDE frames and writes it as a complete DBDE frame of an
  * rw x rh image, without decoding the window: tiles whose valid pixels are unchanged are COPIED (depth byte, minimum,
