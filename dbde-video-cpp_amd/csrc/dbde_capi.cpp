@@ -1,130 +1,22 @@
-// dbde_capi.cpp -- implementation of include/dbde_hip.h (the C-ABI of libdbde_hip.so).
+// dbde_capi.cpp -- implementation of include/dbde_hip.h (the C-ABI of libdbde_hip.so): the context, the whole-frame
+// encoders and decoders, the stream scan and the host-pointer entry points, and the plumbing of dbde_host.h.  The
+// window families are in dbde_capi_window.cpp, dbde_capi_project.cpp and dbde_capi_patch.cpp.
 //
 // Host side only: argument checking, workspace, launches, and the byte marshalling the
 // host-pointer entry points need.  All tile arithmetic is in dbde_kernels.hip; nothing here
 // (or anywhere in this library) computes DBDE on the CPU.
-#include "../../include/dbde_hip.h"
-
-#include <hip/hip_runtime.h>
+#include "dbde_host.h"
 
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
 #include "dbde16_kernels.h"
-#include "dbde_binned_kernels.h"
-#include "dbde_counts_kernels.h"
-#include "dbde_lag_kernels.h"
-#include "dbde_pairs_kernels.h"
-#include "dbde_crop_kernels.h"
-#include "dbde_gproject_kernels.h"
-#include "dbde_hist_kernels.h"
-#include "dbde_kernels.h"
-#include "dbde_mask_kernels.h"
-#include "dbde_match_kernels.h"
-#include "dbde_moment_kernels.h"
-#include "dbde_patch_kernels.h"
-#include "dbde_project_kernels.h"
-#include "dbde_roi_kernels.h"
-#include "dbde_rproject_kernels.h"
-#include "dbde_scaled_kernels.h"
-#include "dbde_trace_kernels.h"
-#include "dbde_wenc_kernels.h"
-#include "dbde_wproject_kernels.h"
 
 using namespace dbde;
+using namespace dbde_host;
 
-namespace {
-
-struct TimedSpan {
-    hipEvent_t a, b;
-    int kind;
-};
-
-struct Geometry {
-    uint32_t w, h, T;
-    uint64_t pixels;
-};
-
-}  // namespace
-
-struct dbde_hip_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;         // dbde_hip_create_on_own_stream: destroyed with the context
-    std::string err;
-    std::string arch;
-
-    // look-back workspace: [two sets of control words: 2 x 8 x u32][state: n_chunks x u64].  Zeroed when it is allocated
-    // and after a failed launch; otherwise every launch leaves it as it found it (persistent encoder: each record is
-    // cleared by its reader, the scanner clears the control words of the launch after it; small launches tag theirs)
-    uint8_t *lb = nullptr;
-    size_t lb_bytes = 0;
-    uint32_t enc_parity = 0;         // which set of control words the next persistent launch uses
-    // scan-ahead: a second stream so that the frame-to-frame walk of the NEXT batch runs beside the decode of this one
-    hipStream_t scan_stream = nullptr;
-    hipEvent_t scan_ev_main = nullptr, scan_ev_done = nullptr;
-    // speculative stream walk: temporary position lists of the segments
-    uint8_t *scan_ws = nullptr;
-    size_t scan_ws_bytes = 0;
-    // DBDE16 encode workspace (per-tile depth / minimum, chunk and frame totals, frame bases, arrival counter)
-    uint8_t *w16 = nullptr;
-    size_t w16_bytes = 0;
-    bool lb_fresh = true;            // the block holds arbitrary bits (fresh allocation): a small launch zeroes it before its first use
-    uint32_t enc_epoch = 0;          // tag of the last small encode launch's records (launch_encode_small)
-    // decode workspace
-    uint32_t *chunk_off = nullptr;
-    size_t chunk_off_n = 0;
-    uint32_t *frame_ok = nullptr;
-    size_t frame_ok_n = 0;
-    uint32_t *idx_ctr = nullptr;     // [2 * n]: arrival counters, then flags, of the split index kernel (kept zero)
-    size_t idx_ctr_n = 0;
-    unsigned long long *fuse_rec = nullptr;   // records of the fused index + decode launch (epoch-tagged, never cleared)
-    uint8_t *proj_ws = nullptr;      // per-segment partials of dbde_hip_project
-    size_t proj_ws_bytes = 0;
-    uint8_t *trace_ws = nullptr;     // U32 max / min per (frame, label) of dbde_hip_traces
-    size_t trace_ws_bytes = 0;
-    uint8_t *crop_ws = nullptr;      // row and frame tables, records of re-packed tiles of dbde_hip_crop_frames
-    size_t crop_ws_bytes = 0;
-    size_t fuse_rec_n = 0;
-    uint32_t fuse_epoch = 0;
-    // sticky failure word (device) + scratch
-    uint32_t *sticky = nullptr;
-    uint64_t *scratch64 = nullptr;   // small device scratch: [0..3]
-    // staging for the host-pointer entry points
-    uint8_t *st_img = nullptr;
-    size_t st_img_bytes = 0;
-    uint8_t *st_pack = nullptr;
-    size_t st_pack_bytes = 0;
-    // ... and their pinned host twins (dbde_hip_set_host_staging): the caller's pageable bytes are copied through these
-    // by the calling thread, so that the DMA never has to pin (and the runtime's pinning of pageable memory, which
-    // serialises concurrent callers, is out of the way)
-    uint64_t *h_words = nullptr;     // pinned, device-visible: [0] the encoder's byte count, [1..4] the decoder's frame result -- the kernels write them
-                                     // straight into host memory, so a call has no small copies between its two big ones
-    uint8_t *d_hdr = nullptr;        // a frame header {2, 0, 0} in device memory (dbde_hip_unpack_image puts it in front of the caller's frame data)
-    int host_staging = 0;
-    uint8_t *h_img = nullptr;
-    size_t h_img_bytes = 0;
-    uint8_t *h_pack = nullptr;
-    size_t h_pack_bytes = 0;
-    // timing
-    uint32_t exp_flags = 0;          // $DBDE_HIP_EXPERIMENT (tuning experiments only)
-    uint32_t enc_grid = 0;           // resident workgroups for the persistent encoder
-    uint32_t enc16_grid = 0;         // the same for the DBDE16 encoder (queried at its first call)
-    uint32_t wenc_grid[2] = {0, 0};  // the same for the window encoder, DBDE and DBDE16
-    int n_cu = 0;
-    int mid_dec_per_cu[2][3] = {};   // resident workgroups per CU of decode_mid_kernel (decode_mid_blocks_per_cu)
-    uint64_t *diag = nullptr;        // [16] phase cycle sums of diagnostic launches
-    bool timing = false;
-    std::vector<TimedSpan> spans;
-    double acc_ms[4] = {0, 0, 0, 0};     // encode, decode index, decode, stream scan
-    uint64_t acc_n[4] = {0, 0, 0, 0};
-};
-
-namespace {
+namespace dbde_host DBDE_HOST_HIDDEN {
 
 int fail(dbde_hip_ctx *ctx, int code, const char *fmt, ...) {
     char buf[512];
@@ -136,13 +28,6 @@ int fail(dbde_hip_ctx *ctx, int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(ctx, expr)                                                                      \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return fail(ctx, DBDE_HIP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));  \
-    } while (0)
-
 bool geometry(int W, int H, Geometry &g) {
     if (W <= 0 || H <= 0) return false;
     uint64_t w = ((uint64_t)W + 7) / 8, h = ((uint64_t)H + 7) / 8;
@@ -153,28 +38,6 @@ bool geometry(int W, int H, Geometry &g) {
     g.T = (uint32_t)T;
     g.pixels = (uint64_t)W * (uint64_t)H;
     return true;
-}
-
-template <typename Ptr>
-int grow(dbde_hip_ctx *ctx, Ptr &p, size_t &have, size_t want_elems, size_t elem_bytes, bool uncached = false) {
-    if (want_elems <= have) return DBDE_HIP_OK;
-    // everything queued may still be using the old block
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (p) HIP_TRY(ctx, hipFree(p));
-    p = nullptr;
-    have = 0;
-    size_t n = want_elems + want_elems / 4 + 64;
-    void *q = nullptr;
-    // chunk records are written by one CU and polled by others through sc1 atomics: keeping them out
-    // of the (per-XCD, mutually incoherent) L2s measured 1.5-2.5 % faster; plain memory if refused
-    if (uncached && hipExtMallocWithFlags(&q, n * elem_bytes, hipDeviceMallocUncached) != hipSuccess) {
-        (void)hipGetLastError();
-        q = nullptr;
-    }
-    if (!q) HIP_TRY(ctx, hipMalloc(&q, n * elem_bytes));
-    p = reinterpret_cast<Ptr>(q);
-    have = n;
-    return DBDE_HIP_OK;
 }
 
 void span_begin(dbde_hip_ctx *ctx, int kind) {
@@ -189,6 +52,100 @@ void span_end(dbde_hip_ctx *ctx) {
     if (!ctx->timing || ctx->spans.empty()) return;
     (void)hipEventRecord(ctx->spans.back().b, ctx->stream);
 }
+
+uint32_t index_split_for(int n_frames, uint32_t cpf) {
+    if (n_frames < 1 || n_frames >= 256 || cpf < 8u) return 1u;
+    uint32_t sp = 1024u / (uint32_t)n_frames;
+    const uint32_t most = (cpf + 3u) / 4u;
+    return sp > most ? most : (sp < 1u ? 1u : sp);
+}
+
+int run_index(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+              int n_frames, dbde_hip_frame_result *d_results, const DecGeom &dg, uint32_t min_bytes, uint32_t split) {
+    int rc = grow(ctx, ctx->chunk_off, ctx->chunk_off_n, (size_t)n_frames * (dg.cpf + 1u), sizeof(uint32_t));
+    if (rc) return rc;
+    rc = grow(ctx, ctx->frame_ok, ctx->frame_ok_n, (size_t)n_frames, sizeof(uint32_t));
+    if (rc) return rc;
+
+    IdxParams ip;
+    set_stream(ip, ctx, d_stream, stream_bytes, d_frame_offsets);
+    ip.results = d_results;
+    ip.T = dg.T;
+    ip.chunks_per_frame = dg.cpf;
+    ip.min_bytes = min_bytes;
+    ip.geom = dg;
+    ip.split = 1;
+    ip.frame_ctr = nullptr;
+    ip.frame_flag = nullptr;
+    if (split > 1u) {
+        const size_t before = ctx->idx_ctr_n;
+        rc = grow(ctx, ctx->idx_ctr, ctx->idx_ctr_n, 2 * (size_t)n_frames, sizeof(uint32_t));
+        if (rc) return rc;
+        if (ctx->idx_ctr_n != before)   // fresh block: the kernel keeps it zero from here on
+            HIP_TRY(ctx, hipMemsetAsync(ctx->idx_ctr, 0, ctx->idx_ctr_n * sizeof(uint32_t), ctx->stream));
+        ip.split = split;
+        ip.frame_ctr = ctx->idx_ctr;
+        ip.frame_flag = ctx->idx_ctr + n_frames;
+    }
+    span_begin(ctx, 1);
+    HIP_TRY(ctx, launch_decode_index(ip, n_frames, ctx->stream));
+    span_end(ctx);
+    return DBDE_HIP_OK;
+}
+
+int index_pass(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
+               int n_frames, dbde_hip_frame_result *d_results, const DecGeom &dg, uint32_t min_bytes, uint32_t split) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n_frames == 0) return DBDE_HIP_OK;
+    return run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, dg, min_bytes, split);
+}
+
+const char *plan_roi(int W, int H, int n_frames, int x0, int y0, int rw, int rh, RoiPlan &pl, uint32_t wide) {
+    if (n_frames < 0) return "n_frames < 0";
+    if (!geometry(W, H, pl.g)) return "bad frame size";
+    if (rw < 1 || rh < 1 || rw > W || rh > H) return "window size outside [1, W] x [1, H]";
+    if (x0 < 0 || y0 < 0 || x0 > W - rw || y0 > H - rh) return "window origin outside [0, W-rw] x [0, H-rh]";
+    pl.dg = roi_index_geometry(pl.g.w, pl.g.h);
+    if (pl.dg.cpf > kMaxChunksPerFrame) return "frame too large";
+    pl.tx0 = (uint32_t)x0 >> 3;
+    pl.ty0 = (uint32_t)y0 >> 3;
+    pl.ntx = (uint32_t)(x0 + rw - 1) / 8u + 1u - pl.tx0;
+    pl.nty = (uint32_t)(y0 + rh - 1) / 8u + 1u - pl.ty0;
+    // x mod 8 reaches min(7, W - rw) over the origins a window of this width can have
+    const uint32_t mx = (uint32_t)(W - rw) < 7u ? (uint32_t)(W - rw) : 7u, my = (uint32_t)(H - rh) < 7u ? (uint32_t)(H - rh) : 7u;
+    pl.max_tx = (mx + (uint32_t)rw + 7u) / 8u;
+    pl.max_ty = (my + (uint32_t)rh + 7u) / 8u;
+    pl.split = index_split_for(n_frames, pl.dg.cpf);
+    pl.threads = pl.max_tx <= kRoiNarrowThreads ? kRoiNarrowThreads : wide;
+    pl.pieces = (pl.max_tx + pl.threads - 1u) / pl.threads;
+    pl.pieces_fixed = (pl.ntx + pl.threads - 1u) / pl.threads;
+    pl.grid = (uint64_t)n_frames * pl.nty * pl.pieces_fixed;
+    pl.grid_origins = (uint64_t)n_frames * pl.max_ty * pl.pieces;
+    if (pl.grid_origins >= (1ull << 31)) return "too many workgroups in one call";
+    if ((uint64_t)n_frames * (pl.dg.cpf + 1u) >= (1ull << 31)) return "too many chunks in one call";
+    return nullptr;
+}
+
+void fill_roi_params(RoiParams &p, const RoiPlan &pl, int W, int H, int x0, int y0, int rw, int rh,
+                     const int32_t *d_origins, uint32_t pieces) {
+    p.origins = d_origins;
+    p.W = W;
+    p.H = H;
+    p.x0 = x0;
+    p.y0 = y0;
+    p.rw = rw;
+    p.rh = rh;
+    p.w = pl.g.w;
+    p.h = pl.g.h;
+    p.T = pl.g.T;
+    p.geom = pl.dg;
+    p.rows = d_origins ? pl.max_ty : pl.nty;
+    p.pieces = pieces;
+}
+
+}  // namespace dbde_host
+
+namespace {
 
 void put32(uint8_t *p, uint32_t v) { for (int i = 0; i < 4; i++) p[i] = (uint8_t)(v >> (8 * i)); }
 void put64(uint8_t *p, uint64_t v) { for (int i = 0; i < 8; i++) p[i] = (uint8_t)(v >> (8 * i)); }
@@ -703,56 +660,6 @@ static DecPlan plan_decode(const Geometry &g, int W, int n_frames, uintptr_t ib,
     return pl;
 }
 
-// Index split of the decode index kernel: few frames are cut into pieces so that the index pass fills the device too
-// (>= 4 chunks per piece, about 1024 workgroups in all); from 256 frames on, one workgroup per frame.
-static uint32_t index_split_for(int n_frames, uint32_t cpf) {
-    if (n_frames < 1 || n_frames >= 256 || cpf < 8u) return 1u;
-    uint32_t sp = 1024u / (uint32_t)n_frames;
-    const uint32_t most = (cpf + 3u) / 4u;
-    return sp > most ? most : (sp < 1u ? 1u : sp);
-}
-
-// The decode index kernel in timing slot 1: validation, results and per-chunk payload offsets (ctx->chunk_off,
-// ctx->frame_ok) of n_frames > 0 frames cut into the chunks of dg.  min_bytes: 1 = DBDE, 2 = DBDE16.  split: workgroups
-// per frame (1, or the split form's index_split_for).  Shared by every decoder that runs the index as a launch of its own.
-static int run_index(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
-                     int n_frames, dbde_hip_frame_result *d_results, const DecGeom &dg, uint32_t min_bytes,
-                     uint32_t split) {
-    int rc = grow(ctx, ctx->chunk_off, ctx->chunk_off_n, (size_t)n_frames * (dg.cpf + 1u), sizeof(uint32_t));
-    if (rc) return rc;
-    rc = grow(ctx, ctx->frame_ok, ctx->frame_ok_n, (size_t)n_frames, sizeof(uint32_t));
-    if (rc) return rc;
-
-    IdxParams ip;
-    ip.stream = d_stream;
-    ip.frame_offsets = d_frame_offsets;
-    ip.stream_bytes = stream_bytes;
-    ip.chunk_off = ctx->chunk_off;
-    ip.frame_ok = ctx->frame_ok;
-    ip.results = d_results;
-    ip.T = dg.T;
-    ip.chunks_per_frame = dg.cpf;
-    ip.min_bytes = min_bytes;
-    ip.geom = dg;
-    ip.split = 1;
-    ip.frame_ctr = nullptr;
-    ip.frame_flag = nullptr;
-    if (split > 1u) {
-        const size_t before = ctx->idx_ctr_n;
-        rc = grow(ctx, ctx->idx_ctr, ctx->idx_ctr_n, 2 * (size_t)n_frames, sizeof(uint32_t));
-        if (rc) return rc;
-        if (ctx->idx_ctr_n != before)   // fresh block: the kernel keeps it zero from here on
-            HIP_TRY(ctx, hipMemsetAsync(ctx->idx_ctr, 0, ctx->idx_ctr_n * sizeof(uint32_t), ctx->stream));
-        ip.split = split;
-        ip.frame_ctr = ctx->idx_ctr;
-        ip.frame_flag = ctx->idx_ctr + n_frames;
-    }
-    span_begin(ctx, 1);
-    HIP_TRY(ctx, launch_decode_index(ip, n_frames, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
 int dbde_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
                            const uint64_t *d_frame_offsets, int W, int H, int n_frames, uint8_t *d_images,
                            dbde_hip_frame_result *d_results) {
@@ -799,12 +706,8 @@ int dbde_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t st
     }
 
     DecParams p;
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
+    set_stream(p, ctx, d_stream, stream_bytes, d_frame_offsets);
     p.images = d_images;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
     p.results = d_results;
     p.frame_pixels = g.pixels;
     p.W = W;
@@ -826,2727 +729,6 @@ int dbde_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t st
     return DBDE_HIP_OK;
 }
 
-// ---- window decode ----------------------------------------------------------------------------------------
-struct RoiPlan {
-    Geometry g;
-    DecGeom dg;                       // the index's chunks (roi_index_geometry)
-    uint32_t tx0, ty0, ntx, nty;      // the window at (x0, y0)
-    uint32_t max_tx, max_ty;          // the most any origin needs
-    uint32_t split, threads, pieces, pieces_fixed;
-    uint64_t grid, grid_origins;
-};
-// nullptr when the arguments are good, else what is wrong with them.  wide: tiles per workgroup of windows more than 64
-// tiles across (kRoiWideThreads for DBDE, kRoi16WideThreads for DBDE16).
-static const char *plan_roi(int W, int H, int n_frames, int x0, int y0, int rw, int rh, RoiPlan &pl,
-                            uint32_t wide = kRoiWideThreads) {
-    if (n_frames < 0) return "n_frames < 0";
-    if (!geometry(W, H, pl.g)) return "bad frame size";
-    if (rw < 1 || rh < 1 || rw > W || rh > H) return "window size outside [1, W] x [1, H]";
-    if (x0 < 0 || y0 < 0 || x0 > W - rw || y0 > H - rh) return "window origin outside [0, W-rw] x [0, H-rh]";
-    pl.dg = roi_index_geometry(pl.g.w, pl.g.h);
-    if (pl.dg.cpf > kMaxChunksPerFrame) return "frame too large";
-    pl.tx0 = (uint32_t)x0 >> 3;
-    pl.ty0 = (uint32_t)y0 >> 3;
-    pl.ntx = (uint32_t)(x0 + rw - 1) / 8u + 1u - pl.tx0;
-    pl.nty = (uint32_t)(y0 + rh - 1) / 8u + 1u - pl.ty0;
-    // x mod 8 reaches min(7, W - rw) over the origins a window of this width can have
-    const uint32_t mx = (uint32_t)(W - rw) < 7u ? (uint32_t)(W - rw) : 7u, my = (uint32_t)(H - rh) < 7u ? (uint32_t)(H - rh) : 7u;
-    pl.max_tx = (mx + (uint32_t)rw + 7u) / 8u;
-    pl.max_ty = (my + (uint32_t)rh + 7u) / 8u;
-    pl.split = index_split_for(n_frames, pl.dg.cpf);
-    pl.threads = pl.max_tx <= kRoiNarrowThreads ? kRoiNarrowThreads : wide;
-    pl.pieces = (pl.max_tx + pl.threads - 1u) / pl.threads;
-    pl.pieces_fixed = (pl.ntx + pl.threads - 1u) / pl.threads;
-    pl.grid = (uint64_t)n_frames * pl.nty * pl.pieces_fixed;
-    pl.grid_origins = (uint64_t)n_frames * pl.max_ty * pl.pieces;
-    if (pl.grid_origins >= (1ull << 31)) return "too many workgroups in one call";
-    if ((uint64_t)n_frames * (pl.dg.cpf + 1u) >= (1ull << 31)) return "too many chunks in one call";
-    return nullptr;
-}
-
-static void report_roi_plan(const RoiPlan &pl, dbde_hip_roi_plan_t *plan) {
-    memset(plan, 0, sizeof *plan);
-    plan->tile_x = (int32_t)pl.tx0;
-    plan->tile_y = (int32_t)pl.ty0;
-    plan->tiles_x = (int32_t)pl.ntx;
-    plan->tiles_y = (int32_t)pl.nty;
-    plan->max_tiles_x = (int32_t)pl.max_tx;
-    plan->max_tiles_y = (int32_t)pl.max_ty;
-    plan->chunks_per_frame = pl.dg.cpf;
-    plan->chunk_tiles = pl.dg.ct;
-    plan->chunk_pieces = pl.dg.ct == pl.g.w || pl.dg.pieces > 1u ? pl.dg.pieces : 0u;
-    plan->index_split = pl.split;
-    plan->threads = pl.threads;
-    plan->pieces_x = pl.pieces;
-    plan->grid = pl.grid;
-    plan->grid_origins = pl.grid_origins;
-}
-
-int dbde_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_roi_plan_t *plan) {
-    RoiPlan pl;
-    if (!plan || plan_roi(W, H, n_frames, x0, y0, rw, rh, pl)) return DBDE_HIP_ERR_ARG;
-    report_roi_plan(pl, plan);
-    return DBDE_HIP_OK;
-}
-
-int dbde16_hip_roi_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_roi_plan_t *plan) {
-    RoiPlan pl;
-    if (!plan || plan_roi(W, H, n_frames, x0, y0, rw, rh, pl, kRoi16WideThreads)) return DBDE_HIP_ERR_ARG;
-    report_roi_plan(pl, plan);
-    return DBDE_HIP_OK;
-}
-
-// Both window decoders: the index (min_bytes: 1 = DBDE, 2 = DBDE16) in timing slot 1, the window kernel in slot 2.
-static int decode_roi_common(dbde_hip_ctx *ctx, const char *name, uint32_t min_bytes, const uint8_t *d_stream,
-                             size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
-                             int y0, int rw, int rh, const int32_t *d_origins, void *d_out,
-                             dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    RoiPlan pl;
-    const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl, min_bytes == 2u ? kRoi16WideThreads : kRoiWideThreads);
-    if (why)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", name, why, W, H, n_frames,
-                    rw, rh, x0, y0);
-    if (!d_stream || !d_frame_offsets || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (n_frames == 0) return DBDE_HIP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.dg, min_bytes, pl.split);
-    if (rc) return rc;
-
-    RoiParams p;
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.origins = d_origins;
-    p.out = static_cast<uint8_t *>(d_out);
-    p.W = W;
-    p.H = H;
-    p.x0 = x0;
-    p.y0 = y0;
-    p.rw = rw;
-    p.rh = rh;
-    p.w = pl.g.w;
-    p.h = pl.g.h;
-    p.T = pl.g.T;
-    p.geom = pl.dg;
-    p.rows = d_origins ? pl.max_ty : pl.nty;
-    p.pieces = d_origins ? pl.pieces : pl.pieces_fixed;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_decode_roi(p, (uint32_t)n_frames, pl.threads, min_bytes, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
-                        int W, int H, int n_frames, int x0, int y0, int rw, int rh, const int32_t *d_origins,
-                        uint8_t *d_out, dbde_hip_frame_result *d_results) {
-    return decode_roi_common(ctx, "decode_roi", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
-                             rh, d_origins, d_out, d_results);
-}
-
-int dbde16_hip_decode_roi(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                          const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                          const int32_t *d_origins, uint16_t *d_out, dbde_hip_frame_result *d_results) {
-    return decode_roi_common(ctx, "decode_roi16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0,
-                             rw, rh, d_origins, d_out, d_results);
-}
-
-// ---- temporal projections ---------------------------------------------------------------------------------
-struct ProjectPlan {
-    RoiPlan roi;                      // arguments, tile window and index geometry: the window decoder's (plan_roi)
-    uint32_t stats;
-    uint32_t pieces, rows, segments, fps;
-    uint64_t grid, combine_grid, workspace;
-};
-// Frames per segment: a segment is cut only to fill the device (about 4 workgroups per CU) and never below
-// kProjMinFramesPerSegment frames, whose partials would cost more traffic than they save; never above the U32 bound.
-// pix: 1 = DBDE (dbde_hip_project), 2 = DBDE16 (dbde16_hip_project: kProjTilesOf(2) tiles per workgroup, U16 / U64
-// partials); the segment rule is the same for both.
-static constexpr uint32_t kProjMinFramesPerSegment = 32;
-static const char *plan_project_segments(int n_frames, int rw, int rh, int n_cu, uint32_t pix, ProjectPlan &pl);
-static const char *plan_project(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
-                                uint32_t pix, ProjectPlan &pl) {
-    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, pix == 2u ? kRoi16WideThreads : kRoiWideThreads))
-        return why;
-    if (stats < 1u || stats > kProjAll) return "no statistic (or an unknown one) requested";
-    pl.stats = stats;
-    const uint32_t tiles = kProjTilesOf(pix);
-    pl.pieces = (pl.roi.ntx + tiles - 1u) / tiles;
-    return plan_project_segments(n_frames, rw, rh, n_cu, pix, pl);
-}
-// The rows, segments, grids and workspace of a projection whose pieces across a window tile row are set (pl.pieces).
-static const char *plan_project_segments(int n_frames, int rw, int rh, int n_cu, uint32_t pix, ProjectPlan &pl) {
-    pl.rows = pl.roi.nty;
-    const uint64_t base = (uint64_t)pl.pieces * pl.rows, n = (uint64_t)n_frames;
-    const uint64_t target = 4ull * (uint64_t)(n_cu > 0 ? n_cu : 1);
-    uint64_t seg = base >= target ? 1u : (target + base - 1u) / base;
-    const uint64_t by_len = (n + kProjMinFramesPerSegment - 1u) / kProjMinFramesPerSegment;
-    if (seg > by_len) seg = by_len;
-    const uint64_t by_bound = (n + kProjMaxFramesPerSegment - 1u) / kProjMaxFramesPerSegment;
-    if (seg < by_bound) seg = by_bound;
-    if (seg < 1u) seg = 1u;
-    uint64_t fps = (n + seg - 1u) / seg;
-    if (fps > 0u) seg = (n + fps - 1u) / fps;   // no empty segment
-    if (seg >= (1ull << 31)) return "too many workgroups in one call";
-    pl.segments = (uint32_t)seg;
-    pl.fps = (uint32_t)fps;
-    pl.grid = base * seg;
-    if (pl.grid >= (1ull << 31)) return "too many workgroups in one call";
-    const uint64_t pixels = (uint64_t)rw * (uint64_t)rh;
-    pl.combine_grid = seg > 1u ? (pixels + kProjCombineThreads - 1u) / kProjCombineThreads : 0u;
-    if (pl.combine_grid >= (1ull << 31)) return "too many workgroups in one call";
-    pl.workspace = project_workspace_bytes(pl.stats, pl.segments, pixels, pix);
-    return nullptr;
-}
-
-static int project_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
-                               uint32_t pix, dbde_hip_project_plan_t *plan) {
-    ProjectPlan pl;
-    if (!plan || plan_project(W, H, n_frames, x0, y0, rw, rh, stats, n_cu, pix, pl)) return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->tile_x = (int32_t)pl.roi.tx0;
-    plan->tile_y = (int32_t)pl.roi.ty0;
-    plan->tiles_x = (int32_t)pl.roi.ntx;
-    plan->tiles_y = (int32_t)pl.roi.nty;
-    plan->chunks_per_frame = pl.roi.dg.cpf;
-    plan->chunk_tiles = pl.roi.dg.ct;
-    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
-    plan->index_split = pl.roi.split;
-    plan->threads = kProjThreads;   // (DBDE16: 16 lanes per tile, threads / 16 tiles)
-    plan->pieces_x = pl.pieces;
-    plan->segments = pl.segments;
-    plan->frames_per_segment = pl.fps;
-    plan->max_frames_per_segment = kProjMaxFramesPerSegment;
-    plan->grid = pl.grid;
-    plan->combine_grid = pl.combine_grid;
-    plan->workspace_bytes = pl.workspace;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
-                          dbde_hip_project_plan_t *plan) {
-    return project_plan_common(W, H, n_frames, x0, y0, rw, rh, stats, n_cu, 1u, plan);
-}
-
-int dbde16_hip_project_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, unsigned stats, int n_cu,
-                            dbde_hip_project_plan_t *plan) {
-    return project_plan_common(W, H, n_frames, x0, y0, rw, rh, stats, n_cu, 2u, plan);
-}
-
-// Both projections: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the projection
-// kernels in slot 2.  d_max / d_min hold U8 (pix 1) or U16 (pix 2) pixels.
-static int project_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
-                          size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
-                          int y0, int rw, int rh, int accumulate, void *d_max, void *d_min, uint64_t *d_sum,
-                          uint64_t *d_sumsq, uint64_t *d_count, dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    const unsigned stats = (d_max ? kProjMax : 0u) | (d_min ? kProjMin : 0u) | (d_sum ? kProjSum : 0u) |
-                           (d_sumsq ? kProjSumSq : 0u);
-    ProjectPlan pl;
-    if (const char *why = plan_project(W, H, n_frames, x0, y0, rw, rh, stats, ctx->n_cu, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", name, why, W, H, n_frames,
-                    rw, rh, x0, y0);
-    if (!d_stream || !d_frame_offsets || !d_count) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if ((reinterpret_cast<uintptr_t>(d_sum) | reinterpret_cast<uintptr_t>(d_sumsq) |
-         reinterpret_cast<uintptr_t>(d_count)) & 7u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U64 outputs must be 8-byte aligned", name);
-    if ((reinterpret_cast<uintptr_t>(d_max) | reinterpret_cast<uintptr_t>(d_min)) & (pix - 1u))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U16 outputs must be 2-byte aligned", name);
-    if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n_frames > 0) {
-        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
-        if (rc) return rc;
-    }
-    ProjParams p;
-    memset(&p, 0, sizeof p);
-    if (pl.workspace) {   // the partials in project_workspace_bytes' order: max, min, sum, sumsq, each 16-byte aligned
-        int rc = grow(ctx, ctx->proj_ws, ctx->proj_ws_bytes, (size_t)pl.workspace, 1);
-        if (rc) return rc;
-        const uint64_t n = (uint64_t)pl.segments * (uint64_t)rw * (uint64_t)rh;
-        const uint64_t mm = (pix * n + 15u) & ~(uint64_t)15, u32 = (4u * n + 15u) & ~(uint64_t)15;
-        const uint64_t sq = pix == 1u ? u32 : (8u * n + 15u) & ~(uint64_t)15;
-        uint8_t *w = ctx->proj_ws;
-        if (d_max) { p.ws_max = w; w += mm; }
-        if (d_min) { p.ws_min = w; w += mm; }
-        if (d_sum) { p.ws_sum = reinterpret_cast<uint32_t *>(w); w += u32; }
-        if (d_sumsq) { p.ws_sumsq = reinterpret_cast<uint32_t *>(w); w += sq; }
-    }
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.n_frames = (uint32_t)n_frames;
-    p.x0 = x0;
-    p.y0 = y0;
-    p.rw = rw;
-    p.rh = rh;
-    p.T = pl.roi.g.T;
-    p.w = pl.roi.g.w;
-    p.geom = pl.roi.dg;
-    p.tx0 = pl.roi.tx0;
-    p.ty0 = pl.roi.ty0;
-    p.rows = pl.rows;
-    p.pieces = pl.pieces;
-    p.segments = pl.segments;
-    p.fps = pl.fps;
-    p.accumulate = accumulate ? 1 : 0;
-    p.out_max = static_cast<uint8_t *>(d_max);
-    p.out_min = static_cast<uint8_t *>(d_min);
-    p.out_sum = d_sum;
-    p.out_sumsq = d_sumsq;
-    p.out_count = d_count;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_project(p, stats, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
-                     int W, int H, int n_frames, int x0, int y0, int rw, int rh, int accumulate, uint8_t *d_max,
-                     uint8_t *d_min, uint64_t *d_sum, uint64_t *d_sumsq, uint64_t *d_count,
-                     dbde_hip_frame_result *d_results) {
-    return project_common(ctx, "project", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh,
-                          accumulate, d_max, d_min, d_sum, d_sumsq, d_count, d_results);
-}
-
-int dbde16_hip_project(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                       const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                       int accumulate, uint16_t *d_max, uint16_t *d_min, uint64_t *d_sum, uint64_t *d_sumsq,
-                       uint64_t *d_count, dbde_hip_frame_result *d_results) {
-    return project_common(ctx, "project16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
-                          rh, accumulate, d_max, d_min, d_sum, d_sumsq, d_count, d_results);
-}
-
-// ---- weighted temporal projections -------------------------------------------------------
-// The window, the index geometry and the segment rule are plan_project's (any statistics set gives the same segments);
-// ONE_SEGMENT forces one segment, whose F32 chain has no bound on its frames.
-struct WProjectPlan {
-    ProjectPlan proj;
-    uint32_t regressors;
-};
-static const char *plan_wproject(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int n_regressors,
-                                 uint64_t weight_stride, int flags, uint64_t weights_address, uint64_t out_address,
-                                 uint64_t count_address, int n_cu, uint32_t pix, WProjectPlan &pl) {
-    if (const char *why = plan_project(W, H, n_frames, x0, y0, rw, rh, kProjSum, n_cu, pix, pl.proj)) return why;
-    if (n_regressors < 1 || n_regressors > (int)kWProjMaxRegressors) return "n_regressors outside 1..8";
-    if (flags & ~DBDE_HIP_WPROJ_ONE_SEGMENT) return "unknown flag bits";
-    if (weight_stride < (uint64_t)n_frames) return "weight_stride < n_frames";
-    if (!weights_address || !out_address || !count_address) return "null pointer";
-    if ((weights_address | out_address) & 3u) return "F32 weights and output must be 4-byte aligned";
-    if (count_address & 7u) return "the U64 count must be 8-byte aligned";
-    pl.regressors = (uint32_t)n_regressors;
-    if (flags & DBDE_HIP_WPROJ_ONE_SEGMENT) {
-        pl.proj.segments = 1u;
-        pl.proj.fps = (uint32_t)n_frames;
-        pl.proj.grid = (uint64_t)pl.proj.pieces * pl.proj.rows;
-        pl.proj.combine_grid = 0u;
-    }
-    pl.proj.workspace = wproject_workspace_bytes(pl.regressors, pl.proj.segments, (uint64_t)rw * (uint64_t)rh);
-    return nullptr;
-}
-
-static int wproject_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int n_regressors,
-                                uint64_t weight_stride, int flags, uint64_t weights_address, uint64_t out_address,
-                                uint64_t count_address, int n_cu, uint32_t pix, dbde_hip_project_weighted_plan_t *plan) {
-    WProjectPlan pl;
-    if (!plan || plan_wproject(W, H, n_frames, x0, y0, rw, rh, n_regressors, weight_stride, flags, weights_address,
-                               out_address, count_address, n_cu, pix, pl))
-        return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->tile_x = (int32_t)pl.proj.roi.tx0;
-    plan->tile_y = (int32_t)pl.proj.roi.ty0;
-    plan->tiles_x = (int32_t)pl.proj.roi.ntx;
-    plan->tiles_y = (int32_t)pl.proj.roi.nty;
-    plan->chunks_per_frame = pl.proj.roi.dg.cpf;
-    plan->chunk_tiles = pl.proj.roi.dg.ct;
-    plan->chunk_pieces = pl.proj.roi.dg.ct == pl.proj.roi.g.w || pl.proj.roi.dg.pieces > 1u ? pl.proj.roi.dg.pieces : 0u;
-    plan->index_split = pl.proj.roi.split;
-    plan->threads = kProjThreads;
-    plan->pieces_x = pl.proj.pieces;
-    plan->segments = pl.proj.segments;
-    plan->frames_per_segment = pl.proj.fps;
-    plan->max_frames_per_segment = kProjMaxFramesPerSegment;
-    plan->regressors = pl.regressors;
-    plan->grid = pl.proj.grid;
-    plan->combine_grid = pl.proj.combine_grid;
-    plan->workspace_bytes = pl.proj.workspace;
-    plan->lds_bytes = kWProjLdsBytes;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_weighted_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int n_regressors,
-                                   uint64_t weight_stride, int flags, uint64_t weights_address, uint64_t out_address,
-                                   uint64_t count_address, int n_cu, dbde_hip_project_weighted_plan_t *plan) {
-    return wproject_plan_common(W, H, n_frames, x0, y0, rw, rh, n_regressors, weight_stride, flags, weights_address,
-                                out_address, count_address, n_cu, 1u, plan);
-}
-
-int dbde16_hip_project_weighted_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int n_regressors,
-                                     uint64_t weight_stride, int flags, uint64_t weights_address, uint64_t out_address,
-                                     uint64_t count_address, int n_cu, dbde_hip_project_weighted_plan_t *plan) {
-    return wproject_plan_common(W, H, n_frames, x0, y0, rw, rh, n_regressors, weight_stride, flags, weights_address,
-                                out_address, count_address, n_cu, 2u, plan);
-}
-
-// Both weighted projections: the index (pix: 1 = DBDE, 2 = DBDE16) in timing slot 1, the projection kernels in slot 2.
-static int wproject_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
-                           size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
-                           int y0, int rw, int rh, const float *d_weights, int n_regressors, size_t weight_stride,
-                           int accumulate, int flags, float *d_out, uint64_t *d_count,
-                           dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    WProjectPlan pl;
-    if (const char *why = plan_wproject(W, H, n_frames, x0, y0, rw, rh, n_regressors, (uint64_t)weight_stride, flags,
-                                        reinterpret_cast<uintptr_t>(d_weights), reinterpret_cast<uintptr_t>(d_out),
-                                        reinterpret_cast<uintptr_t>(d_count), ctx->n_cu, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d, R=%d)", name, why, W, H,
-                    n_frames, rw, rh, x0, y0, n_regressors);
-    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n_frames > 0) {
-        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.proj.roi.dg, pix,
-                           pl.proj.roi.split);
-        if (rc) return rc;
-    }
-    WProjParams p;
-    memset(&p, 0, sizeof p);
-    if (pl.proj.workspace) {   // the F32 partials [segments][R][rh * rw]
-        int rc = grow(ctx, ctx->proj_ws, ctx->proj_ws_bytes, (size_t)pl.proj.workspace, 1);
-        if (rc) return rc;
-        p.ws = reinterpret_cast<float *>(ctx->proj_ws);
-    }
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.n_frames = (uint32_t)n_frames;
-    p.x0 = x0;
-    p.y0 = y0;
-    p.rw = rw;
-    p.rh = rh;
-    p.T = pl.proj.roi.g.T;
-    p.w = pl.proj.roi.g.w;
-    p.geom = pl.proj.roi.dg;
-    p.tx0 = pl.proj.roi.tx0;
-    p.ty0 = pl.proj.roi.ty0;
-    p.rows = pl.proj.rows;
-    p.pieces = pl.proj.pieces;
-    p.segments = pl.proj.segments;
-    p.fps = pl.proj.fps;
-    p.accumulate = accumulate ? 1 : 0;
-    p.regressors = pl.regressors;
-    p.weights = d_weights;
-    p.weight_stride = (uint64_t)weight_stride;
-    p.out = d_out;
-    p.out_count = d_count;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_wproject(p, pl.regressors, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_weighted(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                              const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw,
-                              int rh, const float *d_weights, int n_regressors, size_t weight_stride, int accumulate,
-                              int flags, float *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results) {
-    return wproject_common(ctx, "project_weighted", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0,
-                           rw, rh, d_weights, n_regressors, weight_stride, accumulate, flags, d_out, d_count, d_results);
-}
-
-int dbde16_hip_project_weighted(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                                const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw,
-                                int rh, const float *d_weights, int n_regressors, size_t weight_stride, int accumulate,
-                                int flags, float *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results) {
-    return wproject_common(ctx, "project_weighted16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0,
-                           y0, rw, rh, d_weights, n_regressors, weight_stride, accumulate, flags, d_out, d_count,
-                           d_results);
-}
-
-// ---- count projections -------------------------------------------------------------------
-// The window, the index geometry and the segment rule are plan_project's (any statistics set gives the same segments).
-// The counts are integers, so the value does not depend on the segments.
-struct CountsPlan {
-    ProjectPlan proj;
-    uint32_t levels;
-};
-static const char *plan_counts(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int n_levels,
-                               uint64_t level_stride, int flags, uint64_t thresholds_address, uint64_t out_address,
-                               uint64_t count_address, int n_cu, uint32_t pix, CountsPlan &pl) {
-    if (const char *why = plan_project(W, H, n_frames, x0, y0, rw, rh, kProjSum, n_cu, pix, pl.proj)) return why;
-    if (n_levels < 1 || n_levels > (int)kCountsMaxLevels) return "n_levels outside 1..8";
-    if (flags & ~DBDE_HIP_COUNTS_MAPS) return "unknown flag bits";
-    if ((flags & DBDE_HIP_COUNTS_MAPS) && level_stride < (uint64_t)rw * (uint64_t)rh) return "level_stride < rw * rh";
-    if (!thresholds_address || !out_address || !count_address) return "null pointer";
-    if (thresholds_address & (pix - 1u)) return "U16 thresholds must be 2-byte aligned";
-    if (out_address & 3u) return "the U32 output must be 4-byte aligned";
-    if (count_address & 7u) return "the U64 count must be 8-byte aligned";
-    pl.levels = (uint32_t)n_levels;
-    pl.proj.workspace = counts_workspace_bytes(pl.levels, pl.proj.segments, (uint64_t)rw * (uint64_t)rh);
-    return nullptr;
-}
-
-static int counts_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int n_levels,
-                              uint64_t level_stride, int flags, uint64_t thresholds_address, uint64_t out_address,
-                              uint64_t count_address, int n_cu, uint32_t pix, dbde_hip_project_counts_plan_t *plan) {
-    CountsPlan pl;
-    if (!plan || plan_counts(W, H, n_frames, x0, y0, rw, rh, n_levels, level_stride, flags, thresholds_address,
-                             out_address, count_address, n_cu, pix, pl))
-        return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->tile_x = (int32_t)pl.proj.roi.tx0;
-    plan->tile_y = (int32_t)pl.proj.roi.ty0;
-    plan->tiles_x = (int32_t)pl.proj.roi.ntx;
-    plan->tiles_y = (int32_t)pl.proj.roi.nty;
-    plan->chunks_per_frame = pl.proj.roi.dg.cpf;
-    plan->chunk_tiles = pl.proj.roi.dg.ct;
-    plan->chunk_pieces = pl.proj.roi.dg.ct == pl.proj.roi.g.w || pl.proj.roi.dg.pieces > 1u ? pl.proj.roi.dg.pieces : 0u;
-    plan->index_split = pl.proj.roi.split;
-    plan->threads = kProjThreads;
-    plan->pieces_x = pl.proj.pieces;
-    plan->segments = pl.proj.segments;
-    plan->frames_per_segment = pl.proj.fps;
-    plan->max_frames_per_segment = kProjMaxFramesPerSegment;
-    plan->levels = pl.levels;
-    plan->grid = pl.proj.grid;
-    plan->combine_grid = pl.proj.combine_grid;
-    plan->workspace_bytes = pl.proj.workspace;
-    plan->lds_bytes = kCountsLdsBytes;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_counts_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int n_levels,
-                                 uint64_t level_stride, int flags, uint64_t thresholds_address, uint64_t out_address,
-                                 uint64_t count_address, int n_cu, dbde_hip_project_counts_plan_t *plan) {
-    return counts_plan_common(W, H, n_frames, x0, y0, rw, rh, n_levels, level_stride, flags, thresholds_address,
-                              out_address, count_address, n_cu, 1u, plan);
-}
-
-int dbde16_hip_project_counts_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int n_levels,
-                                   uint64_t level_stride, int flags, uint64_t thresholds_address, uint64_t out_address,
-                                   uint64_t count_address, int n_cu, dbde_hip_project_counts_plan_t *plan) {
-    return counts_plan_common(W, H, n_frames, x0, y0, rw, rh, n_levels, level_stride, flags, thresholds_address,
-                              out_address, count_address, n_cu, 2u, plan);
-}
-
-// Both count projections: the index (pix: 1 = DBDE, 2 = DBDE16) in timing slot 1, the projection kernels in slot 2.
-static int counts_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream, size_t stream_bytes,
-                         const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                         const void *d_thresholds, int n_levels, size_t level_stride, int accumulate, int flags,
-                         uint32_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    CountsPlan pl;
-    if (const char *why = plan_counts(W, H, n_frames, x0, y0, rw, rh, n_levels, (uint64_t)level_stride, flags,
-                                      reinterpret_cast<uintptr_t>(d_thresholds), reinterpret_cast<uintptr_t>(d_out),
-                                      reinterpret_cast<uintptr_t>(d_count), ctx->n_cu, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d, K=%d)", name, why, W, H,
-                    n_frames, rw, rh, x0, y0, n_levels);
-    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n_frames > 0) {
-        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.proj.roi.dg, pix,
-                           pl.proj.roi.split);
-        if (rc) return rc;
-    }
-    CountsParams p;
-    memset(&p, 0, sizeof p);
-    if (pl.proj.workspace) {   // the U32 partials [segments][K][rh * rw]
-        int rc = grow(ctx, ctx->proj_ws, ctx->proj_ws_bytes, (size_t)pl.proj.workspace, 1);
-        if (rc) return rc;
-        p.ws = reinterpret_cast<uint32_t *>(ctx->proj_ws);
-    }
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.n_frames = (uint32_t)n_frames;
-    p.x0 = x0;
-    p.y0 = y0;
-    p.rw = rw;
-    p.rh = rh;
-    p.T = pl.proj.roi.g.T;
-    p.w = pl.proj.roi.g.w;
-    p.geom = pl.proj.roi.dg;
-    p.tx0 = pl.proj.roi.tx0;
-    p.ty0 = pl.proj.roi.ty0;
-    p.rows = pl.proj.rows;
-    p.pieces = pl.proj.pieces;
-    p.segments = pl.proj.segments;
-    p.fps = pl.proj.fps;
-    p.accumulate = accumulate ? 1 : 0;
-    p.levels = pl.levels;
-    p.maps = (flags & DBDE_HIP_COUNTS_MAPS) ? 1 : 0;
-    p.thresholds = d_thresholds;
-    p.level_stride = (uint64_t)level_stride;
-    p.out = d_out;
-    p.out_count = d_count;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_counts(p, pl.levels, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_counts(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                            const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                            const uint8_t *d_thresholds, int n_levels, size_t level_stride, int accumulate, int flags,
-                            uint32_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results) {
-    return counts_common(ctx, "project_counts", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
-                         rh, d_thresholds, n_levels, level_stride, accumulate, flags, d_out, d_count, d_results);
-}
-
-int dbde16_hip_project_counts(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                              const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw,
-                              int rh, const uint16_t *d_thresholds, int n_levels, size_t level_stride, int accumulate,
-                              int flags, uint32_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results) {
-    return counts_common(ctx, "project_counts16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0,
-                         rw, rh, d_thresholds, n_levels, level_stride, accumulate, flags, d_out, d_count, d_results);
-}
-
-// ---- neighbour-product projections -------------------------------------------------------
-// The window and the index geometry are plan_project's.  The pieces across a window tile row overlap by the halo tiles
-// of the instance that serves the mask (kPairsPiecesOf), and the segment rule is plan_project's applied to that grid.
-// The sums are integers, so the value does not depend on the segments.
-struct PairsPlan {
-    ProjectPlan proj;
-    uint32_t pairs, planes, instance;
-};
-static const char *plan_pairs(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int pairs, uint64_t out_address,
-                              uint64_t count_address, int n_cu, uint32_t pix, PairsPlan &pl) {
-    if (const char *why = plan_project(W, H, n_frames, x0, y0, rw, rh, kProjSum, n_cu, pix, pl.proj)) return why;
-    if (pairs < 1 || pairs > (int)kPairAll) return "pairs outside 1..15";
-    if (!out_address || !count_address) return "null pointer";
-    if ((out_address | count_address) & 7u) return "the U64 output and count must be 8-byte aligned";
-    pl.pairs = (uint32_t)pairs;
-    pl.planes = (uint32_t)__builtin_popcount(pl.pairs);
-    pl.instance = kPairsInstanceOf(pl.pairs);
-    pl.proj.pieces = kPairsPiecesOf(pl.proj.roi.ntx, pl.instance, pix);
-    if (const char *why = plan_project_segments(n_frames, rw, rh, n_cu, pix, pl.proj)) return why;
-    pl.proj.workspace = pairs_workspace_bytes(pl.planes, pl.proj.segments, (uint64_t)rw * (uint64_t)rh, pix);
-    return nullptr;
-}
-
-static int pairs_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int pairs, uint64_t out_address,
-                             uint64_t count_address, int n_cu, uint32_t pix, dbde_hip_project_pairs_plan_t *plan) {
-    PairsPlan pl;
-    if (!plan || plan_pairs(W, H, n_frames, x0, y0, rw, rh, pairs, out_address, count_address, n_cu, pix, pl))
-        return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->tile_x = (int32_t)pl.proj.roi.tx0;
-    plan->tile_y = (int32_t)pl.proj.roi.ty0;
-    plan->tiles_x = (int32_t)pl.proj.roi.ntx;
-    plan->tiles_y = (int32_t)pl.proj.roi.nty;
-    plan->chunks_per_frame = pl.proj.roi.dg.cpf;
-    plan->chunk_tiles = pl.proj.roi.dg.ct;
-    plan->chunk_pieces = pl.proj.roi.dg.ct == pl.proj.roi.g.w || pl.proj.roi.dg.pieces > 1u ? pl.proj.roi.dg.pieces : 0u;
-    plan->index_split = pl.proj.roi.split;
-    plan->threads = kProjThreads;
-    plan->pieces_x = pl.proj.pieces;
-    plan->segments = pl.proj.segments;
-    plan->frames_per_segment = pl.proj.fps;
-    plan->max_frames_per_segment = kProjMaxFramesPerSegment;
-    plan->planes = pl.planes;
-    plan->grid = pl.proj.grid;
-    plan->combine_grid = pl.proj.combine_grid;
-    plan->workspace_bytes = pl.proj.workspace;
-    plan->lds_bytes = kPairsLdsBytesOf(pl.instance);
-    plan->instance = pl.instance;
-    plan->piece_tiles = kProjTilesOf(pix);
-    plan->piece_stride = kPairsStrideOf(pl.instance, pix);
-    plan->halo_left = kPairsHaloLeft(pl.instance);
-    plan->halo_right = kPairsHaloRight(pl.instance);
-    plan->rows_below = pl.instance != kPairRight ? pl.proj.roi.nty - 1u : 0u;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_pairs_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int pairs,
-                                uint64_t out_address, uint64_t count_address, int n_cu,
-                                dbde_hip_project_pairs_plan_t *plan) {
-    return pairs_plan_common(W, H, n_frames, x0, y0, rw, rh, pairs, out_address, count_address, n_cu, 1u, plan);
-}
-
-int dbde16_hip_project_pairs_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int pairs,
-                                  uint64_t out_address, uint64_t count_address, int n_cu,
-                                  dbde_hip_project_pairs_plan_t *plan) {
-    return pairs_plan_common(W, H, n_frames, x0, y0, rw, rh, pairs, out_address, count_address, n_cu, 2u, plan);
-}
-
-// Both pair projections: the index (pix: 1 = DBDE, 2 = DBDE16) in timing slot 1, the projection kernels in slot 2.
-static int pairs_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream, size_t stream_bytes,
-                        const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                        int pairs, int accumulate, uint64_t *d_out, uint64_t *d_count, dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    PairsPlan pl;
-    if (const char *why = plan_pairs(W, H, n_frames, x0, y0, rw, rh, pairs, reinterpret_cast<uintptr_t>(d_out),
-                                     reinterpret_cast<uintptr_t>(d_count), ctx->n_cu, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d, pairs=%d)", name, why, W, H,
-                    n_frames, rw, rh, x0, y0, pairs);
-    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n_frames > 0) {
-        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.proj.roi.dg, pix,
-                           pl.proj.roi.split);
-        if (rc) return rc;
-    }
-    PairsParams p;
-    memset(&p, 0, sizeof p);
-    if (pl.proj.workspace) {   // the partials [segments][planes][rh * rw], U32 (pix 1) or U64 (pix 2)
-        int rc = grow(ctx, ctx->proj_ws, ctx->proj_ws_bytes, (size_t)pl.proj.workspace, 1);
-        if (rc) return rc;
-        p.ws = ctx->proj_ws;
-    }
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.n_frames = (uint32_t)n_frames;
-    p.x0 = x0;
-    p.y0 = y0;
-    p.rw = rw;
-    p.rh = rh;
-    p.T = pl.proj.roi.g.T;
-    p.w = pl.proj.roi.g.w;
-    p.geom = pl.proj.roi.dg;
-    p.tx0 = pl.proj.roi.tx0;
-    p.ty0 = pl.proj.roi.ty0;
-    p.rows = pl.proj.rows;
-    p.pieces = pl.proj.pieces;
-    p.segments = pl.proj.segments;
-    p.fps = pl.proj.fps;
-    p.accumulate = accumulate ? 1 : 0;
-    p.pairs = pl.pairs;
-    p.planes = pl.planes;
-    p.out = d_out;
-    p.out_count = d_count;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_pairs(p, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_pairs(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                           int pairs, int accumulate, uint64_t *d_out, uint64_t *d_count,
-                           dbde_hip_frame_result *d_results) {
-    return pairs_common(ctx, "project_pairs", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh,
-                        pairs, accumulate, d_out, d_count, d_results);
-}
-
-int dbde16_hip_project_pairs(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                             const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                             int pairs, int accumulate, uint64_t *d_out, uint64_t *d_count,
-                             dbde_hip_frame_result *d_results) {
-    return pairs_common(ctx, "project_pairs16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
-                        rh, pairs, accumulate, d_out, d_count, d_results);
-}
-
-// ---- lag projections ---------------------------------------------------------------------
-// The window, the index geometry, the pieces and the segment rule are plan_project's (any statistics set gives the same
-// segments).  The values are integers, so they do not depend on the segments.
-struct LagPlan {
-    ProjectPlan proj;
-    uint32_t stats, instance, lag, lead, first_pair, history;
-};
-static const char *plan_lag(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int lag, int lead, unsigned stats,
-                            uint64_t sums_address, uint64_t maxdiff_address, uint64_t pairs_address,
-                            uint64_t count_address, int n_cu, uint32_t pix, LagPlan &pl) {
-    if (const char *why = plan_project(W, H, n_frames, x0, y0, rw, rh, kProjSum, n_cu, pix, pl.proj)) return why;
-    if (lag < 1 || lag > (int)kLagMax) return "lag outside 1..8";
-    if (lead < 0 || lead > n_frames) return "lead outside 0..n_frames";
-    if (stats < 1u || stats > kLagAll) return "no statistic (or an unknown one) requested";
-    if (!pairs_address || !count_address) return "null pointer";
-    if ((sums_address | pairs_address | count_address) & 7u) return "U64 outputs must be 8-byte aligned";
-    if (maxdiff_address & (pix - 1u)) return "the U16 maxdiff plane must be 2-byte aligned";
-    pl.stats = stats;
-    pl.instance = kLagInstanceOf(stats);
-    pl.lag = (uint32_t)lag;
-    pl.lead = (uint32_t)lead;
-    pl.first_pair = pl.lead > pl.lag ? pl.lead : pl.lag;
-    // segments that count a pair: those reaching past first_pair; each but the first decodes lag history frames again
-    const uint32_t active = pl.first_pair < (uint32_t)n_frames ? pl.proj.segments - pl.first_pair / pl.proj.fps : 0u;
-    pl.history = active > 1u ? (active - 1u) * pl.lag : 0u;
-    pl.proj.workspace = lag_workspace_bytes(stats, pl.proj.segments, (uint64_t)rw * (uint64_t)rh, pix);
-    return nullptr;
-}
-
-static int lag_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int lag, int lead, unsigned stats,
-                           uint64_t sums_address, uint64_t maxdiff_address, uint64_t pairs_address,
-                           uint64_t count_address, int n_cu, uint32_t pix, dbde_hip_project_lag_plan_t *plan) {
-    LagPlan pl;
-    if (!plan || plan_lag(W, H, n_frames, x0, y0, rw, rh, lag, lead, stats, sums_address, maxdiff_address, pairs_address,
-                          count_address, n_cu, pix, pl))
-        return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->tile_x = (int32_t)pl.proj.roi.tx0;
-    plan->tile_y = (int32_t)pl.proj.roi.ty0;
-    plan->tiles_x = (int32_t)pl.proj.roi.ntx;
-    plan->tiles_y = (int32_t)pl.proj.roi.nty;
-    plan->chunks_per_frame = pl.proj.roi.dg.cpf;
-    plan->chunk_tiles = pl.proj.roi.dg.ct;
-    plan->chunk_pieces = pl.proj.roi.dg.ct == pl.proj.roi.g.w || pl.proj.roi.dg.pieces > 1u ? pl.proj.roi.dg.pieces : 0u;
-    plan->index_split = pl.proj.roi.split;
-    plan->threads = kProjThreads;
-    plan->pieces_x = pl.proj.pieces;
-    plan->segments = pl.proj.segments;
-    plan->frames_per_segment = pl.proj.fps;
-    plan->max_frames_per_segment = kProjMaxFramesPerSegment;
-    plan->planes = (uint32_t)__builtin_popcount(pl.stats);
-    plan->grid = pl.proj.grid;
-    plan->combine_grid = pl.proj.combine_grid;
-    plan->workspace_bytes = pl.proj.workspace;
-    plan->lds_bytes = kLagLdsBytes;
-    plan->instance = pl.instance;
-    plan->first_frame = pl.first_pair - pl.lag;
-    plan->history_frames = pl.history;
-    plan->first_pair = pl.first_pair;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_lag_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int lag, int lead,
-                              unsigned stats, uint64_t sums_address, uint64_t maxdiff_address, uint64_t pairs_address,
-                              uint64_t count_address, int n_cu, dbde_hip_project_lag_plan_t *plan) {
-    return lag_plan_common(W, H, n_frames, x0, y0, rw, rh, lag, lead, stats, sums_address, maxdiff_address,
-                           pairs_address, count_address, n_cu, 1u, plan);
-}
-
-int dbde16_hip_project_lag_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int lag, int lead,
-                                unsigned stats, uint64_t sums_address, uint64_t maxdiff_address, uint64_t pairs_address,
-                                uint64_t count_address, int n_cu, dbde_hip_project_lag_plan_t *plan) {
-    return lag_plan_common(W, H, n_frames, x0, y0, rw, rh, lag, lead, stats, sums_address, maxdiff_address,
-                           pairs_address, count_address, n_cu, 2u, plan);
-}
-
-// Both lag projections: the index (pix: 1 = DBDE, 2 = DBDE16) in timing slot 1, the projection kernels in slot 2.
-// d_maxdiff holds U8 (pix 1) or U16 (pix 2) pixels.
-static int lag_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream, size_t stream_bytes,
-                      const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                      int lag, int lead, int accumulate, uint64_t *d_product, uint64_t *d_pairsum, uint64_t *d_absdiff,
-                      uint64_t *d_sqdiff, void *d_maxdiff, uint64_t *d_pairs, uint64_t *d_count,
-                      dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    const unsigned stats = (d_product ? kLagProduct : 0u) | (d_pairsum ? kLagPairSum : 0u) | (d_absdiff ? kLagAbsDiff : 0u) |
-                           (d_sqdiff ? kLagSqDiff : 0u) | (d_maxdiff ? kLagMaxDiff : 0u);
-    const uint64_t sums = reinterpret_cast<uintptr_t>(d_product) | reinterpret_cast<uintptr_t>(d_pairsum) |
-                          reinterpret_cast<uintptr_t>(d_absdiff) | reinterpret_cast<uintptr_t>(d_sqdiff);
-    LagPlan pl;
-    if (const char *why = plan_lag(W, H, n_frames, x0, y0, rw, rh, lag, lead, stats, sums,
-                                   reinterpret_cast<uintptr_t>(d_maxdiff), reinterpret_cast<uintptr_t>(d_pairs),
-                                   reinterpret_cast<uintptr_t>(d_count), ctx->n_cu, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d, lag=%d lead=%d)", name, why, W,
-                    H, n_frames, rw, rh, x0, y0, lag, lead);
-    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n_frames > 0) {
-        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.proj.roi.dg, pix,
-                           pl.proj.roi.split);
-        if (rc) return rc;
-    }
-    LagParams p;
-    memset(&p, 0, sizeof p);
-    if (pl.proj.workspace) {   // the partials in lag_workspace_bytes' order, each 16-byte aligned
-        int rc = grow(ctx, ctx->proj_ws, ctx->proj_ws_bytes, (size_t)pl.proj.workspace, 1);
-        if (rc) return rc;
-        const uint64_t pixels = (uint64_t)rw * (uint64_t)rh;
-        uint8_t *w = ctx->proj_ws;
-        if (d_product) { p.ws_product = w; w += lag_partial_bytes(kLagProduct, pl.proj.segments, pixels, pix); }
-        if (d_pairsum) { p.ws_pairsum = w; w += lag_partial_bytes(kLagPairSum, pl.proj.segments, pixels, pix); }
-        if (d_absdiff) { p.ws_absdiff = reinterpret_cast<uint32_t *>(w); w += lag_partial_bytes(kLagAbsDiff, pl.proj.segments, pixels, pix); }
-        if (d_sqdiff) { p.ws_sqdiff = w; w += lag_partial_bytes(kLagSqDiff, pl.proj.segments, pixels, pix); }
-        if (d_maxdiff) { p.ws_maxdiff = w; w += lag_partial_bytes(kLagMaxDiff, pl.proj.segments, pixels, pix); }
-    }
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.n_frames = (uint32_t)n_frames;
-    p.x0 = x0;
-    p.y0 = y0;
-    p.rw = rw;
-    p.rh = rh;
-    p.T = pl.proj.roi.g.T;
-    p.w = pl.proj.roi.g.w;
-    p.geom = pl.proj.roi.dg;
-    p.tx0 = pl.proj.roi.tx0;
-    p.ty0 = pl.proj.roi.ty0;
-    p.rows = pl.proj.rows;
-    p.pieces = pl.proj.pieces;
-    p.segments = pl.proj.segments;
-    p.fps = pl.proj.fps;
-    p.accumulate = accumulate ? 1 : 0;
-    p.lag = pl.lag;
-    p.lead = pl.lead;
-    p.out_product = d_product;
-    p.out_pairsum = d_pairsum;
-    p.out_absdiff = d_absdiff;
-    p.out_sqdiff = d_sqdiff;
-    p.out_maxdiff = d_maxdiff;
-    p.out_pairs = d_pairs;
-    p.out_count = d_count;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_lag(p, stats, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_lag(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                         const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                         int lag, int lead, int accumulate, uint64_t *d_product, uint64_t *d_pairsum,
-                         uint64_t *d_absdiff, uint64_t *d_sqdiff, uint8_t *d_maxdiff, uint64_t *d_pairs,
-                         uint64_t *d_count, dbde_hip_frame_result *d_results) {
-    return lag_common(ctx, "project_lag", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh, lag,
-                      lead, accumulate, d_product, d_pairsum, d_absdiff, d_sqdiff, d_maxdiff, d_pairs, d_count, d_results);
-}
-
-int dbde16_hip_project_lag(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                           int lag, int lead, int accumulate, uint64_t *d_product, uint64_t *d_pairsum,
-                           uint64_t *d_absdiff, uint64_t *d_sqdiff, uint16_t *d_maxdiff, uint64_t *d_pairs,
-                           uint64_t *d_count, dbde_hip_frame_result *d_results) {
-    return lag_common(ctx, "project_lag16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh,
-                      lag, lead, accumulate, d_product, d_pairsum, d_absdiff, d_sqdiff, d_maxdiff, d_pairs, d_count,
-                      d_results);
-}
-
-// ---- registered projections --------------------------------------------------------------
-// The sizes and the index geometry are plan_roi's for the window at (0, 0), whose tile rows are the bands of 8 output
-// rows; the pieces own kRProjColsOf(pix) output columns, and the segment rule is plan_project's applied to that grid.
-static const char *plan_rproject(int W, int H, int n_frames, int rw, int rh, unsigned stats, int n_cu, uint32_t pix,
-                                 ProjectPlan &pl) {
-    if (const char *why = plan_roi(W, H, n_frames, 0, 0, rw, rh, pl.roi, pix == 2u ? kRoi16WideThreads : kRoiWideThreads))
-        return why;
-    if (stats < 1u || stats > kProjAll) return "no statistic (or an unknown one) requested";
-    pl.stats = stats;
-    pl.pieces = ((uint32_t)rw + kRProjColsOf(pix) - 1u) / kRProjColsOf(pix);
-    return plan_project_segments(n_frames, rw, rh, n_cu, pix, pl);
-}
-
-static int rproject_plan_common(int W, int H, int n_frames, int rw, int rh, unsigned stats, int n_cu, uint32_t pix,
-                                dbde_hip_project_registered_plan_t *plan) {
-    ProjectPlan pl;
-    if (!plan || plan_rproject(W, H, n_frames, rw, rh, stats, n_cu, pix, pl)) return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->chunks_per_frame = pl.roi.dg.cpf;
-    plan->chunk_tiles = pl.roi.dg.ct;
-    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
-    plan->index_split = pl.roi.split;
-    plan->threads = kProjThreads;
-    plan->piece_cols = kRProjColsOf(pix);
-    plan->pieces_x = pl.pieces;
-    plan->band_rows = kRProjBandRows;
-    plan->bands = pl.rows;
-    plan->segments = pl.segments;
-    plan->frames_per_segment = pl.fps;
-    plan->max_frames_per_segment = kProjMaxFramesPerSegment;
-    plan->grid = pl.grid;
-    plan->combine_grid = pl.combine_grid;
-    plan->workspace_bytes = pl.workspace;
-    plan->lds_bytes = kRProjLdsBytes;
-    plan->instance = kRProjInstanceOf(stats);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_registered_plan(int W, int H, int n_frames, int rw, int rh, unsigned stats, int n_cu,
-                                     dbde_hip_project_registered_plan_t *plan) {
-    return rproject_plan_common(W, H, n_frames, rw, rh, stats, n_cu, 1u, plan);
-}
-
-int dbde16_hip_project_registered_plan(int W, int H, int n_frames, int rw, int rh, unsigned stats, int n_cu,
-                                       dbde_hip_project_registered_plan_t *plan) {
-    return rproject_plan_common(W, H, n_frames, rw, rh, stats, n_cu, 2u, plan);
-}
-
-// Both registered projections: the index (pix: 1 = DBDE, 2 = DBDE16) in timing slot 1, the projection kernels in slot
-// 2.  d_max / d_min hold U8 (pix 1) or U16 (pix 2) pixels.
-static int rproject_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
-                           size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int rw,
-                           int rh, const int32_t *d_origins, int accumulate, void *d_max, void *d_min, uint64_t *d_sum,
-                           uint64_t *d_sumsq, uint64_t *d_count, int32_t *d_origins_used,
-                           dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    const unsigned stats = (d_max ? kProjMax : 0u) | (d_min ? kProjMin : 0u) | (d_sum ? kProjSum : 0u) |
-                           (d_sumsq ? kProjSumSq : 0u);
-    ProjectPlan pl;
-    if (const char *why = plan_rproject(W, H, n_frames, rw, rh, stats, ctx->n_cu, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d)", name, why, W, H, n_frames, rw, rh);
-    if (!d_stream || !d_frame_offsets || !d_count || !d_origins)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if ((reinterpret_cast<uintptr_t>(d_sum) | reinterpret_cast<uintptr_t>(d_sumsq) |
-         reinterpret_cast<uintptr_t>(d_count)) & 7u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U64 outputs must be 8-byte aligned", name);
-    if ((reinterpret_cast<uintptr_t>(d_max) | reinterpret_cast<uintptr_t>(d_min)) & (pix - 1u))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U16 outputs must be 2-byte aligned", name);
-    if ((reinterpret_cast<uintptr_t>(d_origins) | reinterpret_cast<uintptr_t>(d_origins_used)) & 3u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: origins must be 4-byte aligned", name);
-    if (n_frames == 0 && accumulate) return DBDE_HIP_OK;   // nothing to add
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n_frames > 0) {
-        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
-        if (rc) return rc;
-    }
-    RProjParams rp;
-    memset(&rp, 0, sizeof rp);
-    ProjParams &p = rp.pj;
-    if (pl.workspace) {   // the partials in project_workspace_bytes' order: max, min, sum, sumsq, each 16-byte aligned
-        int rc = grow(ctx, ctx->proj_ws, ctx->proj_ws_bytes, (size_t)pl.workspace, 1);
-        if (rc) return rc;
-        const uint64_t n = (uint64_t)pl.segments * (uint64_t)rw * (uint64_t)rh;
-        const uint64_t mm = (pix * n + 15u) & ~(uint64_t)15, u32 = (4u * n + 15u) & ~(uint64_t)15;
-        const uint64_t sq = pix == 1u ? u32 : (8u * n + 15u) & ~(uint64_t)15;
-        uint8_t *w = ctx->proj_ws;
-        if (d_max) { p.ws_max = w; w += mm; }
-        if (d_min) { p.ws_min = w; w += mm; }
-        if (d_sum) { p.ws_sum = reinterpret_cast<uint32_t *>(w); w += u32; }
-        if (d_sumsq) { p.ws_sumsq = reinterpret_cast<uint32_t *>(w); w += sq; }
-    }
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.n_frames = (uint32_t)n_frames;
-    p.rw = rw;
-    p.rh = rh;
-    p.T = pl.roi.g.T;
-    p.w = pl.roi.g.w;
-    p.geom = pl.roi.dg;
-    p.rows = pl.rows;
-    p.pieces = pl.pieces;
-    p.segments = pl.segments;
-    p.fps = pl.fps;
-    p.accumulate = accumulate ? 1 : 0;
-    p.out_max = static_cast<uint8_t *>(d_max);
-    p.out_min = static_cast<uint8_t *>(d_min);
-    p.out_sum = d_sum;
-    p.out_sumsq = d_sumsq;
-    p.out_count = d_count;
-    rp.origins = d_origins;
-    rp.origins_used = d_origins_used;
-    rp.W = W;
-    rp.H = H;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_rproject(rp, stats, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_registered(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                                const uint64_t *d_frame_offsets, int W, int H, int n_frames, int rw, int rh,
-                                const int32_t *d_origins, int accumulate, uint8_t *d_max, uint8_t *d_min,
-                                uint64_t *d_sum, uint64_t *d_sumsq, uint64_t *d_count, int32_t *d_origins_used,
-                                dbde_hip_frame_result *d_results) {
-    return rproject_common(ctx, "project_registered", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, rw, rh,
-                           d_origins, accumulate, d_max, d_min, d_sum, d_sumsq, d_count, d_origins_used, d_results);
-}
-
-int dbde16_hip_project_registered(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                                  const uint64_t *d_frame_offsets, int W, int H, int n_frames, int rw, int rh,
-                                  const int32_t *d_origins, int accumulate, uint16_t *d_max, uint16_t *d_min,
-                                  uint64_t *d_sum, uint64_t *d_sumsq, uint64_t *d_count, int32_t *d_origins_used,
-                                  dbde_hip_frame_result *d_results) {
-    return rproject_common(ctx, "project_registered16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, rw,
-                           rh, d_origins, accumulate, d_max, d_min, d_sum, d_sumsq, d_count, d_origins_used, d_results);
-}
-
-// ---- grouped temporal projections --------------------------------------------------------
-struct GroupsPlan {
-    RoiPlan roi;                      // arguments, tile window and index geometry: the window decoder's (plan_roi)
-    uint32_t stats;
-    uint32_t pieces, rows, runs, gpr;
-    uint64_t grid;
-    uint64_t max_bytes, min_bytes, sum_bytes, sumsq_bytes, counts_bytes;
-};
-// Groups per run: a run is cut only to fill the device (about 4 workgroups per CU, project's segment rule with whole
-// groups as the unit) and never below kGProjMinFramesPerRun frames, which would start a pipeline for a handful of
-// frames.  The ragged form's groups live on the device: it counts n_frames / n_groups frames per group.
-// The *_addr arguments are the call's output pointers (0 = NULL); only their alignment is looked at.
-static constexpr uint32_t kGProjMinFramesPerRun = 32;
-static const char *plan_groups(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int group_frames,
-                               bool has_starts, int n_groups, int sum_type, int accumulate, uint64_t max_addr,
-                               uint64_t min_addr, uint64_t sum_addr, uint64_t sumsq_addr, uint64_t counts_addr,
-                               int n_cu, uint32_t pix, GroupsPlan &pl) {
-    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, pix == 2u ? kRoi16WideThreads : kRoiWideThreads))
-        return why;
-    const unsigned stats = (max_addr ? kProjMax : 0u) | (min_addr ? kProjMin : 0u) | (sum_addr ? kProjSum : 0u) |
-                           (sumsq_addr ? kProjSumSq : 0u);
-    if (!stats) return "no plane requested";
-    if (!counts_addr) return "d_counts is required";
-    if (accumulate != 0 && accumulate != 1) return "accumulate must be 0 or 1";
-    if (sum_type != DBDE_HIP_SUM_U32 && sum_type != DBDE_HIP_SUM_U16) return "unknown sum_type";
-    if (has_starts == (group_frames != 0)) return "exactly one of group_frames and d_group_starts must be given";
-    if (n_groups < 0) return "n_groups is negative";
-    const uint64_t n = (uint64_t)n_frames;
-    uint64_t max_group;   // frames the largest group can hold
-    if (has_starts) {
-        if (n_groups < 1) return "the ragged form needs n_groups >= 1";
-        if (n > kGProjMaxGroupFrames) return "the ragged form needs n_frames <= 65,536";
-        max_group = n;
-    } else {
-        if (group_frames < 1 || (uint32_t)group_frames > kGProjMaxGroupFrames) return "group_frames must be 1..65,536";
-        if ((uint64_t)n_groups != (n + (uint64_t)group_frames - 1u) / (uint64_t)group_frames)
-            return "n_groups must equal ceil(n_frames / group_frames)";
-        max_group = (uint64_t)group_frames;
-    }
-    if (sum_type == DBDE_HIP_SUM_U16) {
-        if (pix != 1u) return "DBDE16 sums are U32 only";
-        if (max_group > kGProjMaxGroupFramesU16) return "a U16 sum needs groups of at most 257 frames";
-        if (accumulate) return "a U16 sum cannot accumulate";
-    }
-    if ((max_addr | min_addr) & (pix - 1u)) return "U16 planes must be 2-byte aligned";
-    if (sum_addr & (sum_type == DBDE_HIP_SUM_U16 ? 1u : 3u)) return "d_sum is misaligned";
-    if (sumsq_addr & 7u) return "d_sumsq must be 8-byte aligned";
-    if (counts_addr & 3u) return "d_counts must be 4-byte aligned";
-    pl.stats = stats;
-    const uint32_t tiles = kProjTilesOf(pix);
-    pl.pieces = (pl.roi.ntx + tiles - 1u) / tiles;
-    pl.rows = pl.roi.nty;
-    const uint64_t base = (uint64_t)pl.pieces * pl.rows, ng = (uint64_t)n_groups;
-    const uint64_t target = 4ull * (uint64_t)(n_cu > 0 ? n_cu : 1);
-    uint64_t runs = base >= target ? 1u : (target + base - 1u) / base;
-    uint64_t per_group = has_starts ? (ng ? n / ng : 0u) : (uint64_t)group_frames;   // frames of a group (ragged: the mean)
-    if (per_group < 1u) per_group = 1u;
-    const uint64_t min_gpr = (kGProjMinFramesPerRun + per_group - 1u) / per_group;
-    uint64_t gpr = ng ? (ng + runs - 1u) / runs : 1u;
-    if (gpr < min_gpr) gpr = min_gpr;
-    if (gpr > ng && ng) gpr = ng;
-    if (gpr < 1u) gpr = 1u;
-    runs = ng ? (ng + gpr - 1u) / gpr : 0u;   // no empty run
-    pl.runs = (uint32_t)runs;
-    pl.gpr = (uint32_t)gpr;
-    pl.grid = base * runs;
-    if (pl.grid >= (1ull << 31)) return "too many workgroups in one call";
-    const uint64_t plane = (uint64_t)rw * (uint64_t)rh * ng;
-    pl.max_bytes = (stats & kProjMax) ? pix * plane : 0u;
-    pl.min_bytes = (stats & kProjMin) ? pix * plane : 0u;
-    pl.sum_bytes = (stats & kProjSum) ? (sum_type == DBDE_HIP_SUM_U16 ? 2u : 4u) * plane : 0u;
-    pl.sumsq_bytes = (stats & kProjSumSq) ? 8u * plane : 0u;
-    pl.counts_bytes = 4u * ng;
-    return nullptr;
-}
-
-static int groups_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int group_frames,
-                              int has_group_starts, int n_groups, int sum_type, int accumulate, uint64_t max_address,
-                              uint64_t min_address, uint64_t sum_address, uint64_t sumsq_address,
-                              uint64_t counts_address, int n_cu, uint32_t pix, dbde_hip_project_groups_plan_t *plan) {
-    GroupsPlan pl;
-    if (!plan || (has_group_starts != 0 && has_group_starts != 1) ||
-        plan_groups(W, H, n_frames, x0, y0, rw, rh, group_frames, has_group_starts != 0, n_groups, sum_type, accumulate,
-                    max_address, min_address, sum_address, sumsq_address, counts_address, n_cu, pix, pl))
-        return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->tile_x = (int32_t)pl.roi.tx0;
-    plan->tile_y = (int32_t)pl.roi.ty0;
-    plan->tiles_x = (int32_t)pl.roi.ntx;
-    plan->tiles_y = (int32_t)pl.roi.nty;
-    plan->chunks_per_frame = pl.roi.dg.cpf;
-    plan->chunk_tiles = pl.roi.dg.ct;
-    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
-    plan->index_split = pl.roi.split;
-    plan->threads = kProjThreads;
-    plan->pieces_x = pl.pieces;
-    plan->runs = pl.runs;
-    plan->groups_per_run = pl.gpr;
-    plan->max_group_frames = kGProjMaxGroupFrames;
-    plan->stats = pl.stats;
-    plan->grid = pl.grid;
-    plan->sum_bytes = pl.sum_bytes;
-    plan->max_bytes = pl.max_bytes;
-    plan->min_bytes = pl.min_bytes;
-    plan->sumsq_bytes = pl.sumsq_bytes;
-    plan->counts_bytes = pl.counts_bytes;
-    plan->workspace_bytes = 0;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_groups_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int group_frames,
-                                 int has_group_starts, int n_groups, int sum_type, int accumulate, uint64_t max_address,
-                                 uint64_t min_address, uint64_t sum_address, uint64_t sumsq_address,
-                                 uint64_t counts_address, int n_cu, dbde_hip_project_groups_plan_t *plan) {
-    return groups_plan_common(W, H, n_frames, x0, y0, rw, rh, group_frames, has_group_starts, n_groups, sum_type,
-                              accumulate, max_address, min_address, sum_address, sumsq_address, counts_address, n_cu, 1u,
-                              plan);
-}
-
-int dbde16_hip_project_groups_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int group_frames,
-                                   int has_group_starts, int n_groups, int sum_type, int accumulate, uint64_t max_address,
-                                   uint64_t min_address, uint64_t sum_address, uint64_t sumsq_address,
-                                   uint64_t counts_address, int n_cu, dbde_hip_project_groups_plan_t *plan) {
-    return groups_plan_common(W, H, n_frames, x0, y0, rw, rh, group_frames, has_group_starts, n_groups, sum_type,
-                              accumulate, max_address, min_address, sum_address, sumsq_address, counts_address, n_cu, 2u,
-                              plan);
-}
-
-// Both grouped projections: the index (pix: 1 = DBDE, 2 = DBDE16) in timing slot 1, the grouped kernel in slot 2.
-static int project_groups_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
-                                 size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames,
-                                 int x0, int y0, int rw, int rh, int group_frames, const uint32_t *d_group_starts,
-                                 int n_groups, int sum_type, int accumulate, void *d_max, void *d_min, void *d_sum,
-                                 uint64_t *d_sumsq, uint32_t *d_counts, dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    GroupsPlan pl;
-    if (const char *why = plan_groups(W, H, n_frames, x0, y0, rw, rh, group_frames, d_group_starts != nullptr, n_groups,
-                                      sum_type, accumulate, reinterpret_cast<uintptr_t>(d_max),
-                                      reinterpret_cast<uintptr_t>(d_min), reinterpret_cast<uintptr_t>(d_sum),
-                                      reinterpret_cast<uintptr_t>(d_sumsq), reinterpret_cast<uintptr_t>(d_counts),
-                                      ctx->n_cu, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d, g=%d groups=%d)", name, why, W,
-                    H, n_frames, rw, rh, x0, y0, group_frames, n_groups);
-    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (n_groups == 0) return DBDE_HIP_OK;   // (uniform form, n_frames == 0)
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n_frames > 0) {
-        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
-        if (rc) return rc;
-    }
-    GProjParams p;
-    memset(&p, 0, sizeof p);
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.n_frames = (uint32_t)n_frames;
-    p.x0 = x0;
-    p.y0 = y0;
-    p.rw = rw;
-    p.rh = rh;
-    p.T = pl.roi.g.T;
-    p.w = pl.roi.g.w;
-    p.geom = pl.roi.dg;
-    p.tx0 = pl.roi.tx0;
-    p.ty0 = pl.roi.ty0;
-    p.rows = pl.rows;
-    p.pieces = pl.pieces;
-    p.runs = pl.runs;
-    p.gpr = pl.gpr;
-    p.n_groups = (uint32_t)n_groups;
-    p.group_frames = (uint32_t)group_frames;
-    p.group_starts = d_group_starts;
-    p.accumulate = accumulate;
-    p.sum16 = sum_type == DBDE_HIP_SUM_U16 ? 1u : 0u;
-    p.out_max = static_cast<uint8_t *>(d_max);
-    p.out_min = static_cast<uint8_t *>(d_min);
-    p.out_sum = d_sum;
-    p.out_sumsq = d_sumsq;
-    p.out_counts = d_counts;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_gproject(p, pl.stats, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_project_groups(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                            const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                            int group_frames, const uint32_t *d_group_starts, int n_groups, int sum_type, int accumulate,
-                            uint8_t *d_max, uint8_t *d_min, void *d_sum, uint64_t *d_sumsq, uint32_t *d_counts,
-                            dbde_hip_frame_result *d_results) {
-    return project_groups_common(ctx, "project_groups", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0,
-                                 y0, rw, rh, group_frames, d_group_starts, n_groups, sum_type, accumulate, d_max, d_min,
-                                 d_sum, d_sumsq, d_counts, d_results);
-}
-
-int dbde16_hip_project_groups(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                              const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                              int group_frames, const uint32_t *d_group_starts, int n_groups, int sum_type, int accumulate,
-                              uint16_t *d_max, uint16_t *d_min, uint32_t *d_sum, uint64_t *d_sumsq, uint32_t *d_counts,
-                              dbde_hip_frame_result *d_results) {
-    return project_groups_common(ctx, "project_groups16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames,
-                                 x0, y0, rw, rh, group_frames, d_group_starts, n_groups, sum_type, accumulate, d_max,
-                                 d_min, d_sum, d_sumsq, d_counts, d_results);
-}
-
-// ---- region traces ----------------------------------------------------------------------------------------
-struct dbde_hip_trace_map {
-    dbde_hip_ctx *ctx;
-    dbde_hip_trace_map_info_t info;
-    uint8_t *dev;                     // one allocation: the layout of trace_map_layout
-    const uint32_t *span_first[2];    // [pix - 1]: first active tile of each span, [spans + 1]
-    uint32_t spans_x[2], spans[2];
-    const uint32_t *tile_pos, *tile_kind;
-    const uint16_t *blocks;
-    const uint64_t *pixels;
-};
-
-namespace {
-
-// The host side of a trace map: the active tiles in tile order, their words (the label of a whole tile, kTraceMixed |
-// block of a mixed one), the mixed tiles' label blocks, the per-label pixel counts and each pixel size's spans.
-struct HostTraceMap {
-    dbde_hip_trace_map_info_t info;
-    std::vector<uint32_t> pos, kind, span_first[2];
-    std::vector<uint16_t> blocks;
-    std::vector<uint64_t> pixels;
-    uint32_t spans_x[2];
-};
-
-// nullptr when the labels are good, else what is wrong.  full: also the tile lists, blocks and spans.
-const char *trace_classify(const int32_t *labels, int W, int H, int n_labels, HostTraceMap &m, bool full) {
-    Geometry g;
-    if (!labels) return "null labels";
-    if (!geometry(W, H, g)) return "bad frame size";
-    if (n_labels < 1 || n_labels > 65535) return "n_labels outside [1, 65535]";
-    memset(&m.info, 0, sizeof m.info);
-    m.info.W = W;
-    m.info.H = H;
-    m.info.n_labels = (uint32_t)n_labels;
-    m.info.tiles = g.T;
-    m.pixels.assign((size_t)n_labels, 0);
-    for (size_t i = 0; i < g.pixels; i++)
-        if (labels[i] < 0 || labels[i] > n_labels) return "a label outside [0, n_labels]";
-    uint16_t blk[64];
-    for (uint32_t ty = 0; ty < g.h; ty++) {
-        for (uint32_t tx = 0; tx < g.w; tx++) {
-            const uint32_t x0 = 8u * tx, y0 = 8u * ty;
-            const uint32_t vw = (uint32_t)W - x0 < 8u ? (uint32_t)W - x0 : 8u, vh = (uint32_t)H - y0 < 8u ? (uint32_t)H - y0 : 8u;
-            bool any = false, same = true;
-            const int32_t first = labels[(size_t)y0 * W + x0];
-            for (uint32_t y = 0; y < 8; y++) {
-                for (uint32_t x = 0; x < 8; x++) {
-                    int32_t l = 0;
-                    if (y < vh && x < vw) {
-                        l = labels[(size_t)(y0 + y) * W + x0 + x];
-                        if (l) m.pixels[l - 1]++;
-                        same = same && l == first;
-                    }
-                    any = any || l != 0;
-                    blk[8 * y + x] = (uint16_t)l;
-                }
-            }
-            if (!any) continue;
-            const bool whole = same && vw == 8u && vh == 8u;
-            m.info.tiles_active++;
-            if (whole) m.info.tiles_whole++;
-            else m.info.tiles_mixed++;
-            if (!full) continue;
-            m.pos.push_back(ty * g.w + tx);
-            if (whole) {
-                m.kind.push_back((uint32_t)first);
-            } else {
-                m.kind.push_back(kTraceMixed | (uint32_t)(m.blocks.size() / 64u));
-                m.blocks.insert(m.blocks.end(), blk, blk + 64);
-            }
-        }
-    }
-    if (!full) return nullptr;
-    for (uint32_t pix = 1; pix <= 2u; pix++) {
-        const uint32_t K = kTraceTilesOf(pix), sx = (g.w + K - 1u) / K;
-        std::vector<uint32_t> &sf = m.span_first[pix - 1u];
-        m.spans_x[pix - 1u] = sx;
-        sf.resize((size_t)sx * g.h + 1u);
-        size_t a = 0;
-        for (uint32_t s = 0; s < sx * g.h; s++) {   // spans in stream order: tiles [ty * w + (s % sx) * K, + K) of row ty
-            const uint32_t ty = s / sx, p0 = ty * g.w + (s - ty * sx) * K;
-            while (a < m.pos.size() && m.pos[a] < p0) a++;
-            sf[s] = (uint32_t)a;
-        }
-        sf[(size_t)sx * g.h] = (uint32_t)m.pos.size();
-    }
-    return nullptr;
-}
-
-// Byte offsets of the device map: [span_first pix 1][span_first pix 2][tile_pos][tile_kind][blocks][pixels], each
-// 16-byte aligned.
-struct TraceMapLayout {
-    size_t sf1, sf2, pos, kind, blocks, pixels, total;
-};
-TraceMapLayout trace_map_layout(const HostTraceMap &m) {
-    auto up = [](size_t v) { return (v + 15u) & ~(size_t)15; };
-    TraceMapLayout l;
-    l.sf1 = 0;
-    l.sf2 = l.sf1 + up(4u * m.span_first[0].size());
-    l.pos = l.sf2 + up(4u * m.span_first[1].size());
-    l.kind = l.pos + up(4u * m.pos.size());
-    l.blocks = l.kind + up(4u * m.kind.size());
-    l.pixels = l.blocks + up(2u * m.blocks.size());
-    l.total = l.pixels + up(8u * m.pixels.size());
-    return l;
-}
-
-}  // namespace
-
-int dbde_hip_trace_map_summary(const int32_t *labels, int W, int H, int n_labels, dbde_hip_trace_map_info_t *info,
-                               uint64_t *pixels) {
-    HostTraceMap m;
-    if (trace_classify(labels, W, H, n_labels, m, true)) return DBDE_HIP_ERR_ARG;
-    m.info.device_bytes = trace_map_layout(m).total;
-    if (info) *info = m.info;
-    if (pixels) memcpy(pixels, m.pixels.data(), 8u * m.pixels.size());
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_trace_map_create(dbde_hip_ctx *ctx, const int32_t *labels, int W, int H, int n_labels,
-                              dbde_hip_trace_map **out) {
-    if (!ctx || !out) return fail(ctx, DBDE_HIP_ERR_ARG, "trace_map_create: null pointer");
-    *out = nullptr;
-    HostTraceMap m;
-    if (const char *why = trace_classify(labels, W, H, n_labels, m, true))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "trace_map_create: %s (W=%d H=%d n_labels=%d)", why, W, H, n_labels);
-    const TraceMapLayout l = trace_map_layout(m);
-    m.info.device_bytes = l.total;
-    std::vector<uint8_t> host(l.total, 0);
-    auto put = [&](size_t at, const void *src, size_t n) { if (n) memcpy(host.data() + at, src, n); };
-    put(l.sf1, m.span_first[0].data(), 4u * m.span_first[0].size());
-    put(l.sf2, m.span_first[1].data(), 4u * m.span_first[1].size());
-    put(l.pos, m.pos.data(), 4u * m.pos.size());
-    put(l.kind, m.kind.data(), 4u * m.kind.size());
-    put(l.blocks, m.blocks.data(), 2u * m.blocks.size());
-    put(l.pixels, m.pixels.data(), 8u * m.pixels.size());
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void *dev = nullptr;
-    HIP_TRY(ctx, hipMalloc(&dev, l.total));
-    hipError_t e = hipMemcpyAsync(dev, host.data(), l.total, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(dev);
-        return fail(ctx, DBDE_HIP_ERR_HIP, "trace_map_create: copy failed: %s", hipGetErrorString(e));
-    }
-    dbde_hip_trace_map *tm = new dbde_hip_trace_map;
-    uint8_t *d = static_cast<uint8_t *>(dev);
-    tm->ctx = ctx;
-    tm->info = m.info;
-    tm->dev = d;
-    tm->span_first[0] = reinterpret_cast<const uint32_t *>(d + l.sf1);
-    tm->span_first[1] = reinterpret_cast<const uint32_t *>(d + l.sf2);
-    for (int k = 0; k < 2; k++) {
-        tm->spans_x[k] = m.spans_x[k];
-        tm->spans[k] = (uint32_t)(m.span_first[k].size() - 1u);
-    }
-    tm->tile_pos = reinterpret_cast<const uint32_t *>(d + l.pos);
-    tm->tile_kind = reinterpret_cast<const uint32_t *>(d + l.kind);
-    tm->blocks = reinterpret_cast<const uint16_t *>(d + l.blocks);
-    tm->pixels = reinterpret_cast<const uint64_t *>(d + l.pixels);
-    *out = tm;
-    return DBDE_HIP_OK;
-}
-
-void dbde_hip_trace_map_destroy(dbde_hip_trace_map *m) {
-    if (!m) return;
-    (void)hipSetDevice(m->ctx->device);
-    (void)hipStreamSynchronize(m->ctx->stream);   // queued traces may still read it
-    (void)hipFree(m->dev);
-    delete m;
-}
-
-int dbde_hip_trace_map_info(const dbde_hip_trace_map *m, dbde_hip_trace_map_info_t *info) {
-    if (!m || !info) return DBDE_HIP_ERR_ARG;
-    *info = m->info;
-    return DBDE_HIP_OK;
-}
-
-const uint64_t *dbde_hip_trace_map_pixels(const dbde_hip_trace_map *m) { return m ? m->pixels : nullptr; }
-
-namespace {
-
-struct TracePlan {
-    Geometry g;
-    DecGeom dg;                       // the index's chunks (roi_index_geometry)
-    uint32_t split, tiles, spans_x, spans, segments, fps;
-    uint64_t grid, row_grid, workspace;
-};
-// Frames per segment: segments only fill the device (about 4 busy workgroups per CU, the busy spans counted as the
-// fewest that can hold the active tiles) and never hold fewer than kTraceMinFramesPerSegment frames.  Segments cost no
-// extra traffic: each (frame, span) is traced by one workgroup.
-constexpr uint32_t kTraceMinFramesPerSegment = 16;
-const char *plan_trace(int W, int H, int n_frames, const dbde_hip_trace_map_info_t *info, unsigned stats, int n_cu,
-                       uint32_t pix, TracePlan &pl) {
-    if (!info) return "null map info";
-    if (n_frames < 0) return "n_frames < 0";
-    if (!geometry(W, H, pl.g)) return "bad frame size";
-    if (info->W != W || info->H != H) return "W / H differ from the map's";
-    if (info->n_labels < 1u || info->n_labels > 65535u || info->tiles != pl.g.T || info->tiles_active > pl.g.T)
-        return "map info does not describe a map of this frame size";
-    if (stats < 1u || stats > kProjAll) return "no statistic (or an unknown one) requested";
-    if (n_cu < 1) return "n_cu < 1";
-    pl.dg = roi_index_geometry(pl.g.w, pl.g.h);
-    if (pl.dg.cpf > kMaxChunksPerFrame) return "frame too large";
-    if ((uint64_t)n_frames * (pl.dg.cpf + 1u) >= (1ull << 31)) return "too many chunks in one call";
-    pl.split = index_split_for(n_frames, pl.dg.cpf);
-    pl.tiles = kTraceTilesOf(pix);
-    pl.spans_x = (pl.g.w + pl.tiles - 1u) / pl.tiles;
-    pl.spans = pl.spans_x * pl.g.h;
-    const uint64_t n = (uint64_t)n_frames;
-    const uint64_t busy = info->tiles_active ? (info->tiles_active + pl.tiles - 1u) / pl.tiles : 1u;
-    const uint64_t target = 4ull * (uint64_t)n_cu;
-    uint64_t seg = busy >= target ? 1u : (target + busy - 1u) / busy;
-    const uint64_t by_len = (n + kTraceMinFramesPerSegment - 1u) / kTraceMinFramesPerSegment;
-    if (seg > by_len) seg = by_len;
-    if (seg < 1u) seg = 1u;
-    uint64_t fps = (n + seg - 1u) / seg;
-    if (fps > 0u) seg = (n + fps - 1u) / fps;   // no empty segment
-    pl.segments = (uint32_t)seg;
-    pl.fps = (uint32_t)fps;
-    pl.grid = (uint64_t)pl.spans * seg;
-    if (pl.grid >= (1ull << 31)) return "too many workgroups in one call";
-    const uint64_t rows = n * info->n_labels;
-    pl.row_grid = (rows + kTraceRowThreads - 1u) / kTraceRowThreads;
-    if (pl.row_grid >= (1ull << 31)) return "too many outputs in one call";
-    const uint64_t ws = (4u * rows + 15u) & ~(uint64_t)15;
-    pl.workspace = ((stats & kProjMax) ? ws : 0u) + ((stats & kProjMin) ? ws : 0u);
-    return nullptr;
-}
-
-int trace_plan_common(int W, int H, int n_frames, const dbde_hip_trace_map_info_t *info, unsigned stats, int n_cu,
-                      uint32_t pix, dbde_hip_trace_plan_t *plan) {
-    TracePlan pl;
-    if (!plan || plan_trace(W, H, n_frames, info, stats, n_cu, pix, pl)) return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->chunks_per_frame = pl.dg.cpf;
-    plan->chunk_tiles = pl.dg.ct;
-    plan->chunk_pieces = pl.dg.ct == pl.g.w || pl.dg.pieces > 1u ? pl.dg.pieces : 0u;
-    plan->index_split = pl.split;
-    plan->threads = kTraceThreads;
-    plan->tiles_per_workgroup = pl.tiles;
-    plan->spans_x = pl.spans_x;
-    plan->spans = pl.spans;
-    plan->segments = pl.segments;
-    plan->frames_per_segment = pl.fps;
-    plan->grid = pl.grid;
-    plan->row_grid = pl.row_grid;
-    plan->workspace_bytes = pl.workspace;
-    return DBDE_HIP_OK;
-}
-
-// Both trace entry points: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the trace
-// kernels in slot 2.  d_max / d_min hold U8 (pix 1) or U16 (pix 2) values.
-int traces_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream, size_t stream_bytes,
-                  const uint64_t *d_frame_offsets, int W, int H, int n_frames, const dbde_hip_trace_map *map,
-                  void *d_max, void *d_min, uint64_t *d_sum, uint64_t *d_sumsq, dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    if (!map) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null map", name);
-    if (map->ctx != ctx) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the map belongs to another context", name);
-    const unsigned stats = (d_max ? kProjMax : 0u) | (d_min ? kProjMin : 0u) | (d_sum ? kProjSum : 0u) |
-                           (d_sumsq ? kProjSumSq : 0u);
-    TracePlan pl;
-    if (const char *why = plan_trace(W, H, n_frames, &map->info, stats, ctx->n_cu, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d, map %dx%d)", name, why, W, H, n_frames,
-                    map->info.W, map->info.H);
-    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if ((reinterpret_cast<uintptr_t>(d_sum) | reinterpret_cast<uintptr_t>(d_sumsq)) & 7u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U64 outputs must be 8-byte aligned", name);
-    if ((reinterpret_cast<uintptr_t>(d_max) | reinterpret_cast<uintptr_t>(d_min)) & (pix - 1u))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U16 outputs must be 2-byte aligned", name);
-    if (n_frames == 0) return DBDE_HIP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.dg, pix, pl.split);
-    if (rc) return rc;
-    TraceParams p;
-    memset(&p, 0, sizeof p);
-    if (pl.workspace) {   // U32 max, then U32 min, [n_frames][n_labels] each, 16-byte aligned
-        rc = grow(ctx, ctx->trace_ws, ctx->trace_ws_bytes, (size_t)pl.workspace, 1);
-        if (rc) return rc;
-        const uint64_t ws = (4u * (uint64_t)n_frames * map->info.n_labels + 15u) & ~(uint64_t)15;
-        uint8_t *w = ctx->trace_ws;
-        if (d_max) { p.ws_max = reinterpret_cast<uint32_t *>(w); w += ws; }
-        if (d_min) p.ws_min = reinterpret_cast<uint32_t *>(w);
-    }
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.n_frames = (uint32_t)n_frames;
-    p.T = pl.g.T;
-    p.w = pl.g.w;
-    p.geom = pl.dg;
-    p.spans_x = pl.spans_x;
-    p.spans = pl.spans;
-    p.segments = pl.segments;
-    p.fps = pl.fps;
-    p.n_labels = map->info.n_labels;
-    p.pix_max = pix == 1u ? 0xFFu : 0xFFFFu;
-    p.span_first = map->span_first[pix - 1u];
-    p.tile_pos = map->tile_pos;
-    p.tile_kind = map->tile_kind;
-    p.blocks = map->blocks;
-    p.out_max = static_cast<uint8_t *>(d_max);
-    p.out_min = static_cast<uint8_t *>(d_min);
-    p.out_sum = d_sum;
-    p.out_sumsq = d_sumsq;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_traces(p, stats, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-}  // namespace
-
-int dbde_hip_trace_plan(int W, int H, int n_frames, const dbde_hip_trace_map_info_t *info, unsigned stats, int n_cu,
-                        dbde_hip_trace_plan_t *plan) {
-    return trace_plan_common(W, H, n_frames, info, stats, n_cu, 1u, plan);
-}
-
-int dbde16_hip_trace_plan(int W, int H, int n_frames, const dbde_hip_trace_map_info_t *info, unsigned stats, int n_cu,
-                          dbde_hip_trace_plan_t *plan) {
-    return trace_plan_common(W, H, n_frames, info, stats, n_cu, 2u, plan);
-}
-
-int dbde_hip_traces(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
-                    int W, int H, int n_frames, const dbde_hip_trace_map *map, uint8_t *d_max, uint8_t *d_min,
-                    uint64_t *d_sum, uint64_t *d_sumsq, dbde_hip_frame_result *d_results) {
-    return traces_common(ctx, "traces", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, map, d_max, d_min,
-                         d_sum, d_sumsq, d_results);
-}
-
-int dbde16_hip_traces(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
-                      int W, int H, int n_frames, const dbde_hip_trace_map *map, uint16_t *d_max, uint16_t *d_min,
-                      uint64_t *d_sum, uint64_t *d_sumsq, dbde_hip_frame_result *d_results) {
-    return traces_common(ctx, "traces16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, map, d_max,
-                         d_min, d_sum, d_sumsq, d_results);
-}
-
-// ---- per-frame histograms ---------------------------------------------------------------------------------
-struct HistPlan {
-    RoiPlan roi;                      // arguments, tile window and index geometry: the window decoder's (plan_roi)
-    uint32_t pieces_x, pieces, segments, pps, lds_bins;
-    uint64_t grid, init_grid, atomics, workspace;
-};
-// A segment is cut only to fill the device (about 16 workgroups per CU) and never below the pieces whose pixels
-// outnumber its flush 64 times (64 * bins pixels, and at least kHistMinPieces pieces).
-static constexpr uint32_t kHistMinPieces = 16;
-static const char *plan_histogram(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins,
-                                  unsigned outputs, int n_cu, uint32_t pix, HistPlan &pl) {
-    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, pix == 2u ? kRoi16WideThreads : kRoiWideThreads))
-        return why;
-    const int max_shift = pix == 1u ? 7 : 15;
-    if (shift < 0 || shift > max_shift) return "shift outside [0, 7] (DBDE) / [0, 15] (DBDE16)";
-    const uint32_t range = (pix == 1u ? 256u : 65536u) >> shift;
-    const uint32_t most = pix == 1u ? range : (range < kHistLargeBins ? range : kHistLargeBins);
-    if (bins < 1 || (uint32_t)bins > most) return "bins outside [1, 256 >> shift] (DBDE) / [1, min(4096, 65536 >> shift)] (DBDE16)";
-    if (outputs < 1u || outputs > 3u) return "no output (or an unknown one) requested";
-    const uint32_t tiles = kHistTilesOf(pix);
-    pl.pieces_x = (pl.roi.ntx + tiles - 1u) / tiles;
-    pl.pieces = pl.pieces_x * pl.roi.nty;
-    pl.lds_bins = kHistLdsBinsOf((uint32_t)bins);
-    const uint64_t n = (uint64_t)n_frames;
-    const uint64_t px_piece = 64ull * tiles;
-    uint64_t min_pieces = (64ull * (uint64_t)bins + px_piece - 1u) / px_piece;
-    if (min_pieces < kHistMinPieces) min_pieces = kHistMinPieces;
-    const uint64_t target = 16ull * (uint64_t)(n_cu > 0 ? n_cu : 1);
-    uint64_t seg = (target + (n > 0 ? n : 1) - 1u) / (n > 0 ? n : 1);
-    const uint64_t by_len = (pl.pieces + min_pieces - 1u) / min_pieces;
-    if (seg > by_len) seg = by_len;
-    if (seg < 1u) seg = 1u;
-    const uint64_t pps = (pl.pieces + seg - 1u) / seg;
-    seg = (pl.pieces + pps - 1u) / pps;   // no empty segment
-    pl.segments = (uint32_t)seg;
-    pl.pps = (uint32_t)pps;
-    pl.grid = n * seg;
-    if (pl.grid >= (1ull << 31)) return "too many workgroups in one call";
-    const uint64_t rows = (n > 0 ? n : 1) * (uint64_t)bins;
-    pl.init_grid = (rows + kHistRowThreads - 1u) / kHistRowThreads;
-    if (pl.init_grid >= (1ull << 31)) return "too many workgroups in one call";
-    pl.atomics = seg * (uint64_t)bins * (uint64_t)(((outputs & 1u) ? 1u : 0u) + ((outputs & 2u) ? 1u : 0u));
-    pl.workspace = n * (pl.roi.dg.cpf + 1u) * 4u + n * 4u;
-    return nullptr;
-}
-
-static int histogram_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins,
-                                 unsigned outputs, int n_cu, uint32_t pix, dbde_hip_histogram_plan_t *plan) {
-    HistPlan pl;
-    if (!plan || n_cu < 1 || plan_histogram(W, H, n_frames, x0, y0, rw, rh, shift, bins, outputs, n_cu, pix, pl))
-        return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->tile_x = (int32_t)pl.roi.tx0;
-    plan->tile_y = (int32_t)pl.roi.ty0;
-    plan->tiles_x = (int32_t)pl.roi.ntx;
-    plan->tiles_y = (int32_t)pl.roi.nty;
-    plan->chunks_per_frame = pl.roi.dg.cpf;
-    plan->chunk_tiles = pl.roi.dg.ct;
-    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
-    plan->index_split = pl.roi.split;
-    plan->threads = kHistThreads;
-    plan->tiles_per_piece = kHistTilesOf(pix);
-    plan->pieces_x = pl.pieces_x;
-    plan->pieces = pl.pieces;
-    plan->segments = pl.segments;
-    plan->pieces_per_segment = pl.pps;
-    plan->lds_bins = pl.lds_bins;
-    plan->lds_copies = kHistCopiesOf(pl.lds_bins);
-    plan->lds_bytes = kHistLdsBytesOf(pl.lds_bins);
-    plan->grid = pl.grid;
-    plan->init_grid = pl.init_grid;
-    plan->global_atomics_per_frame = pl.atomics;
-    plan->workspace_bytes = pl.workspace;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_histogram_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins,
-                            unsigned outputs, int n_cu, dbde_hip_histogram_plan_t *plan) {
-    return histogram_plan_common(W, H, n_frames, x0, y0, rw, rh, shift, bins, outputs, n_cu, 1u, plan);
-}
-
-int dbde16_hip_histogram_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins,
-                              unsigned outputs, int n_cu, dbde_hip_histogram_plan_t *plan) {
-    return histogram_plan_common(W, H, n_frames, x0, y0, rw, rh, shift, bins, outputs, n_cu, 2u, plan);
-}
-
-// Both histograms: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the histogram kernels
-// in slot 2.
-static int histogram_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
-                            size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
-                            int y0, int rw, int rh, int shift, int bins, int accumulate, uint32_t *d_hist,
-                            uint64_t *d_total, uint64_t *d_count, dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    const unsigned outputs = (d_hist ? 1u : 0u) | (d_total ? 2u : 0u);
-    HistPlan pl;
-    if (const char *why = plan_histogram(W, H, n_frames, x0, y0, rw, rh, shift, bins, outputs, ctx->n_cu, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d shift %d bins %d)", name, why,
-                    W, H, n_frames, rw, rh, x0, y0, shift, bins);
-    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (d_total && !d_count) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: d_total needs d_count", name);
-    if ((reinterpret_cast<uintptr_t>(d_total) | reinterpret_cast<uintptr_t>(d_count)) & 7u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U64 outputs must be 8-byte aligned", name);
-    if (reinterpret_cast<uintptr_t>(d_hist) & 3u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U32 rows must be 4-byte aligned", name);
-    if (n_frames == 0 && (accumulate || !d_total)) return DBDE_HIP_OK;   // nothing to add or to reset
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n_frames > 0) {
-        int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
-        if (rc) return rc;
-    }
-    HistParams p;
-    memset(&p, 0, sizeof p);
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.n_frames = (uint32_t)n_frames;
-    p.x0 = x0;
-    p.y0 = y0;
-    p.rw = rw;
-    p.rh = rh;
-    p.T = pl.roi.g.T;
-    p.w = pl.roi.g.w;
-    p.geom = pl.roi.dg;
-    p.tx0 = pl.roi.tx0;
-    p.ty0 = pl.roi.ty0;
-    p.rows = pl.roi.nty;
-    p.pieces = pl.pieces_x;
-    p.segments = pl.segments;
-    p.pps = pl.pps;
-    p.shift = (uint32_t)shift;
-    p.bins = (uint32_t)bins;
-    p.accumulate = accumulate ? 1 : 0;
-    p.out_hist = d_hist;
-    p.out_total = d_total;
-    p.out_count = d_total ? d_count : nullptr;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_histogram(p, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_histogram(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
-                       int W, int H, int n_frames, int x0, int y0, int rw, int rh, int shift, int bins, int accumulate,
-                       uint32_t *d_hist, uint64_t *d_total, uint64_t *d_count, dbde_hip_frame_result *d_results) {
-    return histogram_common(ctx, "histogram", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
-                            rh, shift, bins, accumulate, d_hist, d_total, d_count, d_results);
-}
-
-int dbde16_hip_histogram(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                         const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                         int shift, int bins, int accumulate, uint32_t *d_hist, uint64_t *d_total, uint64_t *d_count,
-                         dbde_hip_frame_result *d_results) {
-    return histogram_common(ctx, "histogram16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw,
-                            rh, shift, bins, accumulate, d_hist, d_total, d_count, d_results);
-}
-
-// ---- binned decode -----------------------------------------------------------------------------------------
-struct BinnedPlan {
-    RoiPlan roi;                      // arguments, tile window and index geometry: the window decoder's (plan_roi)
-    uint32_t threads, pieces, ow, oh;
-    uint64_t grid, sum_bytes, mm_bytes;
-};
-static const char *plan_binned(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int bin, unsigned stats,
-                               uint32_t pix, BinnedPlan &pl) {
-    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, kBinWideThreadsOf(pix))) return why;
-    if (bin != 2 && bin != 4 && bin != 8) return "bin other than 2, 4, 8";
-    if (x0 % bin || y0 % bin) return "window origin not a multiple of the bin";
-    if (stats < 1u || stats > 7u) return "no statistic (or an unknown one) requested";
-    pl.threads = pl.roi.ntx <= kBinNarrowThreads ? kBinNarrowThreads : kBinWideThreadsOf(pix);
-    pl.pieces = (pl.roi.ntx + pl.threads - 1u) / pl.threads;
-    pl.ow = ((uint32_t)rw + (uint32_t)bin - 1u) / (uint32_t)bin;
-    pl.oh = ((uint32_t)rh + (uint32_t)bin - 1u) / (uint32_t)bin;
-    pl.grid = (uint64_t)n_frames * pl.roi.nty * pl.pieces;   // below 2^31: at most plan_roi's grid_origins
-    const uint64_t elems = (uint64_t)n_frames * pl.oh * pl.ow;
-    pl.sum_bytes = elems * 2u * pix;
-    pl.mm_bytes = elems * pix;
-    return nullptr;
-}
-
-static int binned_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int bin, unsigned stats,
-                              uint32_t pix, dbde_hip_binned_plan_t *plan) {
-    BinnedPlan pl;
-    if (!plan || plan_binned(W, H, n_frames, x0, y0, rw, rh, bin, stats, pix, pl)) return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->tile_x = (int32_t)pl.roi.tx0;
-    plan->tile_y = (int32_t)pl.roi.ty0;
-    plan->tiles_x = (int32_t)pl.roi.ntx;
-    plan->tiles_y = (int32_t)pl.roi.nty;
-    plan->chunks_per_frame = pl.roi.dg.cpf;
-    plan->chunk_tiles = pl.roi.dg.ct;
-    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
-    plan->index_split = pl.roi.split;
-    plan->out_w = pl.ow;
-    plan->out_h = pl.oh;
-    plan->threads = pl.threads;
-    plan->pieces_x = pl.pieces;
-    plan->lds_bytes = kBinLdsBytesOf(pl.threads, pix);
-    plan->grid = pl.grid;
-    plan->sum_bytes = (stats & DBDE_HIP_BINNED_SUM) ? pl.sum_bytes : 0u;
-    plan->max_bytes = (stats & DBDE_HIP_BINNED_MAX) ? pl.mm_bytes : 0u;
-    plan->min_bytes = (stats & DBDE_HIP_BINNED_MIN) ? pl.mm_bytes : 0u;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_binned_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int bin, unsigned stats,
-                         dbde_hip_binned_plan_t *plan) {
-    return binned_plan_common(W, H, n_frames, x0, y0, rw, rh, bin, stats, 1u, plan);
-}
-
-int dbde16_hip_binned_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int bin, unsigned stats,
-                           dbde_hip_binned_plan_t *plan) {
-    return binned_plan_common(W, H, n_frames, x0, y0, rw, rh, bin, stats, 2u, plan);
-}
-
-// Both binned decoders: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the binning kernel
-// in slot 2.
-static int decode_binned_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
-                                size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
-                                int y0, int rw, int rh, int bin, void *d_sum, void *d_max, void *d_min,
-                                dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    const unsigned stats = (d_sum ? DBDE_HIP_BINNED_SUM : 0u) | (d_max ? DBDE_HIP_BINNED_MAX : 0u) | (d_min ? DBDE_HIP_BINNED_MIN : 0u);
-    BinnedPlan pl;
-    if (const char *why = plan_binned(W, H, n_frames, x0, y0, rw, rh, bin, stats, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d bin %d)", name, why, W, H,
-                    n_frames, rw, rh, x0, y0, bin);
-    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (reinterpret_cast<uintptr_t>(d_sum) & (2u * pix - 1u))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the sum plane must be %u-byte aligned", name, 2u * pix);
-    if ((reinterpret_cast<uintptr_t>(d_max) | reinterpret_cast<uintptr_t>(d_min)) & (pix - 1u))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: U16 planes must be 2-byte aligned", name);
-    if (n_frames == 0) return DBDE_HIP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
-    if (rc) return rc;
-    BinnedParams p;
-    memset(&p, 0, sizeof p);
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.x0 = x0;
-    p.y0 = y0;
-    p.rw = rw;
-    p.rh = rh;
-    p.w = pl.roi.g.w;
-    p.T = pl.roi.g.T;
-    p.geom = pl.roi.dg;
-    p.tx0 = pl.roi.tx0;
-    p.ty0 = pl.roi.ty0;
-    p.rows = pl.roi.nty;
-    p.pieces = pl.pieces;
-    p.ow = pl.ow;
-    p.oh = pl.oh;
-    p.out_sum = d_sum;
-    p.out_max = d_max;
-    p.out_min = d_min;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_decode_binned(p, (uint32_t)n_frames, pl.threads, pix, (uint32_t)bin, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_decode_binned(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                           int bin, uint16_t *d_sum, uint8_t *d_max, uint8_t *d_min, dbde_hip_frame_result *d_results) {
-    return decode_binned_common(ctx, "decode_binned", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0,
-                                y0, rw, rh, bin, d_sum, d_max, d_min, d_results);
-}
-
-int dbde16_hip_decode_binned(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                             const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                             int bin, uint32_t *d_sum, uint16_t *d_max, uint16_t *d_min,
-                             dbde_hip_frame_result *d_results) {
-    return decode_binned_common(ctx, "decode_binned16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0,
-                                y0, rw, rh, bin, d_sum, d_max, d_min, d_results);
-}
-
-// ---- scaled float decode -------------------------------------------------------------------------------------
-struct ScaledPlan {
-    RoiPlan roi;                      // arguments, tile window, index geometry and launch: the window decoder's (plan_roi)
-    uint32_t elem;                    // bytes of an output element
-    uint64_t out_bytes;
-};
-static const char *plan_scaled(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int out_type, uint32_t pix,
-                               ScaledPlan &pl) {
-    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, kScaledWideThreadsOf(pix))) return why;
-    if (out_type != DBDE_HIP_OUT_F32 && out_type != DBDE_HIP_OUT_F16 && out_type != DBDE_HIP_OUT_BF16)
-        return "output type other than F32, F16, BF16";
-    pl.elem = kScaledElemBytesOf((uint32_t)out_type);
-    pl.out_bytes = (uint64_t)n_frames * (uint64_t)rw * (uint64_t)rh * pl.elem;
-    return nullptr;
-}
-
-static int scaled_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int out_type, uint32_t pix,
-                              dbde_hip_scaled_plan_t *plan) {
-    ScaledPlan pl;
-    if (!plan || plan_scaled(W, H, n_frames, x0, y0, rw, rh, out_type, pix, pl)) return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->tile_x = (int32_t)pl.roi.tx0;
-    plan->tile_y = (int32_t)pl.roi.ty0;
-    plan->tiles_x = (int32_t)pl.roi.ntx;
-    plan->tiles_y = (int32_t)pl.roi.nty;
-    plan->max_tiles_x = (int32_t)pl.roi.max_tx;
-    plan->max_tiles_y = (int32_t)pl.roi.max_ty;
-    plan->chunks_per_frame = pl.roi.dg.cpf;
-    plan->chunk_tiles = pl.roi.dg.ct;
-    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
-    plan->index_split = pl.roi.split;
-    plan->threads = pl.roi.threads;
-    plan->pieces_x = pl.roi.pieces;
-    plan->lds_bytes = kScaledLdsBytesOf(pl.roi.threads, pix);
-    plan->elem_bytes = pl.elem;
-    plan->grid = pl.roi.grid;
-    plan->grid_origins = pl.roi.grid_origins;
-    plan->out_bytes = pl.out_bytes;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_scaled_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int out_type,
-                         dbde_hip_scaled_plan_t *plan) {
-    return scaled_plan_common(W, H, n_frames, x0, y0, rw, rh, out_type, 1u, plan);
-}
-
-int dbde16_hip_scaled_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, int out_type,
-                           dbde_hip_scaled_plan_t *plan) {
-    return scaled_plan_common(W, H, n_frames, x0, y0, rw, rh, out_type, 2u, plan);
-}
-
-// Both scaled decoders: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the scaling kernel
-// in slot 2.
-static int decode_scaled_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
-                                size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
-                                int y0, int rw, int rh, const int32_t *d_origins, int out_type, const float *d_dark,
-                                float dark0, const float *d_gain, float gain0, void *d_out,
-                                dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    ScaledPlan pl;
-    if (const char *why = plan_scaled(W, H, n_frames, x0, y0, rw, rh, out_type, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d type %d)", name, why, W, H,
-                    n_frames, rw, rh, x0, y0, out_type);
-    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (n_frames > 0 && !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null output", name);
-    if (reinterpret_cast<uintptr_t>(d_out) & (pl.elem - 1u))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the output must be %u-byte aligned", name, pl.elem);
-    if ((reinterpret_cast<uintptr_t>(d_dark) | reinterpret_cast<uintptr_t>(d_gain)) & 3u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the maps must be 4-byte aligned", name);
-    if (n_frames == 0) return DBDE_HIP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
-    if (rc) return rc;
-
-    ScaledParams p;
-    memset(&p, 0, sizeof p);
-    p.roi.stream = d_stream;
-    p.roi.frame_offsets = d_frame_offsets;
-    p.roi.stream_bytes = stream_bytes;
-    p.roi.chunk_off = ctx->chunk_off;
-    p.roi.frame_ok = ctx->frame_ok;
-    p.roi.origins = d_origins;
-    p.roi.out = static_cast<uint8_t *>(d_out);
-    p.roi.W = W;
-    p.roi.H = H;
-    p.roi.x0 = x0;
-    p.roi.y0 = y0;
-    p.roi.rw = rw;
-    p.roi.rh = rh;
-    p.roi.w = pl.roi.g.w;
-    p.roi.h = pl.roi.g.h;
-    p.roi.T = pl.roi.g.T;
-    p.roi.geom = pl.roi.dg;
-    p.roi.rows = d_origins ? pl.roi.max_ty : pl.roi.nty;
-    p.roi.pieces = d_origins ? pl.roi.pieces : pl.roi.pieces_fixed;
-    p.dark = d_dark;
-    p.gain = d_gain;
-    p.dark0 = dark0;
-    p.gain0 = gain0;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_decode_scaled(p, (uint32_t)n_frames, pl.roi.threads, pix, (uint32_t)out_type, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_decode_scaled(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                           const int32_t *d_origins, int out_type, const float *d_dark, float dark0, const float *d_gain,
-                           float gain0, void *d_out, dbde_hip_frame_result *d_results) {
-    return decode_scaled_common(ctx, "decode_scaled", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0,
-                                y0, rw, rh, d_origins, out_type, d_dark, dark0, d_gain, gain0, d_out, d_results);
-}
-
-int dbde16_hip_decode_scaled(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                             const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                             const int32_t *d_origins, int out_type, const float *d_dark, float dark0,
-                             const float *d_gain, float gain0, void *d_out, dbde_hip_frame_result *d_results) {
-    return decode_scaled_common(ctx, "decode_scaled16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames,
-                                x0, y0, rw, rh, d_origins, out_type, d_dark, dark0, d_gain, gain0, d_out, d_results);
-}
-
-// ---- threshold mask decode ----------------------------------------------------------------------------------
-struct MaskPlan {
-    RoiPlan roi;                      // arguments, tile window and index geometry: the window decoder's (plan_roi)
-    uint32_t words, threads;
-    uint32_t piece_words, pieces;               // with per-frame origins: any x mod 8
-    uint32_t piece_words_fixed, pieces_fixed;   // at (x0, y0): one more word per piece when x0 is a multiple of 8
-    uint64_t grid, grid_origins, mask_bytes;
-};
-// Pieces are cut in window coordinates (whole mask words), so their number does not depend on the origin.
-static const char *plan_mask(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint32_t pix, MaskPlan &pl) {
-    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi, kMaskWideThreadsOf(pix))) return why;
-    pl.words = ((uint32_t)rw + 63u) / 64u;
-    pl.threads = pl.words <= kMaskNarrowWords ? kMaskNarrowThreads : kMaskWideThreadsOf(pix);
-    // as few pieces as the workgroup's tiles allow, the words spread evenly over them
-    const uint32_t cap = kMaskPieceWordsOf(pl.threads), cap_fixed = x0 % 8 == 0 ? kMaskAlignedPieceWordsOf(pl.threads) : cap;
-    pl.pieces = (pl.words + cap - 1u) / cap;
-    pl.piece_words = (pl.words + pl.pieces - 1u) / pl.pieces;
-    pl.pieces_fixed = (pl.words + cap_fixed - 1u) / cap_fixed;
-    pl.piece_words_fixed = (pl.words + pl.pieces_fixed - 1u) / pl.pieces_fixed;
-    pl.grid = (uint64_t)n_frames * pl.roi.nty * pl.pieces_fixed;
-    pl.grid_origins = (uint64_t)n_frames * pl.roi.max_ty * pl.pieces;
-    if (pl.grid_origins >= (1ull << 31)) return "too many workgroups in one call";
-    pl.mask_bytes = (uint64_t)n_frames * (uint64_t)rh * pl.words * 8u;
-    return nullptr;
-}
-
-static int mask_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint32_t pix,
-                            dbde_hip_mask_plan_t *plan) {
-    MaskPlan pl;
-    if (!plan || plan_mask(W, H, n_frames, x0, y0, rw, rh, pix, pl)) return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->tile_x = (int32_t)pl.roi.tx0;
-    plan->tile_y = (int32_t)pl.roi.ty0;
-    plan->tiles_x = (int32_t)pl.roi.ntx;
-    plan->tiles_y = (int32_t)pl.roi.nty;
-    plan->max_tiles_x = (int32_t)pl.roi.max_tx;
-    plan->max_tiles_y = (int32_t)pl.roi.max_ty;
-    plan->chunks_per_frame = pl.roi.dg.cpf;
-    plan->chunk_tiles = pl.roi.dg.ct;
-    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
-    plan->index_split = pl.roi.split;
-    plan->threads = pl.threads;
-    plan->pieces_x = pl.pieces;
-    plan->piece_words = pl.piece_words;
-    plan->lds_bytes = kMaskLdsBytesOf(pl.threads, pix);
-    plan->words = pl.words;
-    plan->pieces_x_fixed = pl.pieces_fixed;
-    plan->piece_words_fixed = pl.piece_words_fixed;
-    plan->grid = pl.grid;
-    plan->grid_origins = pl.grid_origins;
-    plan->mask_bytes = pl.mask_bytes;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_mask_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_mask_plan_t *plan) {
-    return mask_plan_common(W, H, n_frames, x0, y0, rw, rh, 1u, plan);
-}
-
-int dbde16_hip_mask_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, dbde_hip_mask_plan_t *plan) {
-    return mask_plan_common(W, H, n_frames, x0, y0, rw, rh, 2u, plan);
-}
-
-// Both mask decoders: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the counts' and boxes'
-// initialisation and the mask kernel in slot 2.
-static int decode_mask_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
-                              size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0,
-                              int y0, int rw, int rh, const int32_t *d_origins, int mode, const void *d_lo_map,
-                              uint32_t lo0, const void *d_hi_map, uint32_t hi0, uint64_t *d_mask, uint32_t *d_counts,
-                              int32_t *d_boxes, dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    MaskPlan pl;
-    if (const char *why = plan_mask(W, H, n_frames, x0, y0, rw, rh, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", name, why, W, H, n_frames,
-                    rw, rh, x0, y0);
-    if (!d_stream || !d_frame_offsets) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (mode != DBDE_HIP_MASK_INSIDE && mode != DBDE_HIP_MASK_OUTSIDE)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: mode %d is neither INSIDE nor OUTSIDE", name, mode);
-    const uint32_t pix_max = pix == 1u ? 0xFFu : 0xFFFFu;
-    if (lo0 > pix_max || hi0 > pix_max)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: thresholds %u, %u above %u", name, lo0, hi0, pix_max);
-    if (!d_mask && !d_counts && !d_boxes) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: no output requested", name);
-    if (reinterpret_cast<uintptr_t>(d_mask) & 7u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the mask must be 8-byte aligned", name);
-    if ((reinterpret_cast<uintptr_t>(d_counts) | reinterpret_cast<uintptr_t>(d_boxes)) & 3u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the counts and boxes must be 4-byte aligned", name);
-    if ((reinterpret_cast<uintptr_t>(d_lo_map) | reinterpret_cast<uintptr_t>(d_hi_map)) & (pix - 1u))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the maps must be %u-byte aligned", name, pix);
-    if (n_frames == 0) return DBDE_HIP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
-    if (rc) return rc;
-
-    MaskParams p;
-    memset(&p, 0, sizeof p);
-    p.roi.stream = d_stream;
-    p.roi.frame_offsets = d_frame_offsets;
-    p.roi.stream_bytes = stream_bytes;
-    p.roi.chunk_off = ctx->chunk_off;
-    p.roi.frame_ok = ctx->frame_ok;
-    p.roi.origins = d_origins;
-    p.roi.W = W;
-    p.roi.H = H;
-    p.roi.x0 = x0;
-    p.roi.y0 = y0;
-    p.roi.rw = rw;
-    p.roi.rh = rh;
-    p.roi.w = pl.roi.g.w;
-    p.roi.h = pl.roi.g.h;
-    p.roi.T = pl.roi.g.T;
-    p.roi.geom = pl.roi.dg;
-    p.roi.rows = d_origins ? pl.roi.max_ty : pl.roi.nty;
-    p.roi.pieces = d_origins ? pl.pieces : pl.pieces_fixed;
-    p.lo_map = d_lo_map;
-    p.hi_map = d_hi_map;
-    p.lo0 = lo0;
-    p.hi0 = hi0;
-    p.outside = mode == DBDE_HIP_MASK_OUTSIDE ? kMaskOutside : kMaskInside;
-    p.words = pl.words;
-    p.piece_words = d_origins ? pl.piece_words : pl.piece_words_fixed;
-    p.mask = d_mask;
-    p.counts = d_counts;
-    p.boxes = d_boxes;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_mask_init(d_counts, d_boxes, (uint32_t)n_frames, rw, rh, ctx->stream));
-    HIP_TRY(ctx, launch_decode_mask(p, (uint32_t)n_frames, pl.threads, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_decode_mask(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                         const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                         const int32_t *d_origins, int mode, const uint8_t *d_lo_map, uint32_t lo0,
-                         const uint8_t *d_hi_map, uint32_t hi0, uint64_t *d_mask, uint32_t *d_counts, int32_t *d_boxes,
-                         dbde_hip_frame_result *d_results) {
-    return decode_mask_common(ctx, "decode_mask", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0,
-                              rw, rh, d_origins, mode, d_lo_map, lo0, d_hi_map, hi0, d_mask, d_counts, d_boxes, d_results);
-}
-
-int dbde16_hip_decode_mask(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                           const int32_t *d_origins, int mode, const uint16_t *d_lo_map, uint32_t lo0,
-                           const uint16_t *d_hi_map, uint32_t hi0, uint64_t *d_mask, uint32_t *d_counts,
-                           int32_t *d_boxes, dbde_hip_frame_result *d_results) {
-    return decode_mask_common(ctx, "decode_mask16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0,
-                              rw, rh, d_origins, mode, d_lo_map, lo0, d_hi_map, hi0, d_mask, d_counts, d_boxes, d_results);
-}
-
-// ---- patch decode -------------------------------------------------------------------------------------------
-struct PatchPlan {
-    Geometry g;
-    DecGeom dg;                       // the index's chunks (roi_index_geometry)
-    uint32_t mtx, mty;                // the most tiles any origin makes a patch span
-    uint32_t G, groups, split;
-    uint64_t grid, out_bytes;
-};
-// nullptr when the arguments are good, else what is wrong with them.
-static const char *plan_patches(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode, uint32_t pix,
-                                PatchPlan &pl) {
-    if (n_frames < 0) return "n_frames < 0";
-    if (!geometry(W, H, pl.g)) return "bad frame size";
-    if (edge_mode != DBDE_HIP_PATCH_CLAMP && edge_mode != DBDE_HIP_PATCH_FILL) return "edge mode is neither CLAMP nor FILL";
-    if (n_patches < 1) return "n_patches < 1";
-    if (pw < 1 || ph < 1) return "patch size below 1";
-    if (((uint32_t)pw + 6u) / 8u + 1u > kPatchMaxTilesX) return "a patch could be more than 64 tiles across (pw > 505)";
-    const bool clamp = edge_mode == DBDE_HIP_PATCH_CLAMP;
-    if (clamp && (pw > W || ph > H)) return "CLAMP mode: patch size outside [1, W] x [1, H]";
-    pl.dg = roi_index_geometry(pl.g.w, pl.g.h);
-    if (pl.dg.cpf > kMaxChunksPerFrame) return "frame too large";
-    // x mod 8 reaches 7 in general, min(7, W - pw) over the origins clamping leaves (plan_roi)
-    const uint64_t mx = clamp && (uint32_t)(W - pw) < 7u ? (uint32_t)(W - pw) : 7u;
-    const uint64_t my = clamp && (uint32_t)(H - ph) < 7u ? (uint32_t)(H - ph) : 7u;
-    pl.mtx = (uint32_t)((mx + (uint64_t)pw + 7u) / 8u);
-    pl.mty = (uint32_t)((my + (uint64_t)ph + 7u) / 8u);
-    pl.G = kPatchThreads / pl.mtx < 1u ? 1u : kPatchThreads / pl.mtx;
-    pl.groups = (pl.mty + pl.G - 1u) / pl.G;
-    pl.split = index_split_for(n_frames, pl.dg.cpf);
-    // (n_frames, n_patches < 2^31 and groups < 2^29: np is bounded before it is multiplied by groups, so nothing wraps)
-    const uint64_t np = (uint64_t)n_frames * (uint64_t)n_patches;
-    if (np >= (1ull << 31)) return "too many workgroups in one call";
-    pl.grid = np * pl.groups;
-    if (pl.grid >= (1ull << 31)) return "too many workgroups in one call";
-    if ((uint64_t)n_frames * (pl.dg.cpf + 1u) >= (1ull << 31)) return "too many chunks in one call";
-    pl.out_bytes = np * (uint64_t)ph * (uint64_t)pw * pix;   // (ph <= 512 groups: np * ph < 2^40)
-    return nullptr;
-}
-
-static int patches_plan_common(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode, uint32_t pix,
-                               dbde_hip_patches_plan_t *plan) {
-    PatchPlan pl;
-    memset(&pl, 0, sizeof pl);
-    if (!plan || plan_patches(W, H, n_frames, pw, ph, n_patches, edge_mode, pix, pl)) return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->max_tiles_x = (int32_t)pl.mtx;
-    plan->max_tiles_y = (int32_t)pl.mty;
-    plan->rows_per_workgroup = pl.G;
-    plan->groups_per_patch = pl.groups;
-    plan->threads = kPatchThreads;
-    plan->chunks_per_frame = pl.dg.cpf;
-    plan->chunk_tiles = pl.dg.ct;
-    plan->chunk_pieces = pl.dg.ct == pl.g.w || pl.dg.pieces > 1u ? pl.dg.pieces : 0u;
-    plan->index_split = pl.split;
-    plan->lds_bytes = kPatchPayBytesOf(pix);
-    plan->grid = pl.grid;
-    plan->out_bytes = pl.out_bytes;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_patches_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
-                          dbde_hip_patches_plan_t *plan) {
-    return patches_plan_common(W, H, n_frames, pw, ph, n_patches, edge_mode, 1u, plan);
-}
-
-int dbde16_hip_patches_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
-                            dbde_hip_patches_plan_t *plan) {
-    return patches_plan_common(W, H, n_frames, pw, ph, n_patches, edge_mode, 2u, plan);
-}
-
-// Both patch decoders: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the patch kernel in
-// slot 2.
-static int decode_patches_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
-                                 size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int pw,
-                                 int ph, int n_patches, const int32_t *d_origins, const uint32_t *d_counts, int edge_mode,
-                                 uint32_t fill, void *d_out, int32_t *d_used, dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    PatchPlan pl;
-    memset(&pl, 0, sizeof pl);
-    if (const char *why = plan_patches(W, H, n_frames, pw, ph, n_patches, edge_mode, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d, %d patches of %dx%d, edge mode %d)", name, why, W, H,
-                    n_frames, n_patches, pw, ph, edge_mode);
-    if (!d_stream || !d_frame_offsets || !d_origins || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    const uint32_t pix_max = pix == 1u ? 0xFFu : 0xFFFFu;
-    if (fill > pix_max) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: fill %u above %u", name, fill, pix_max);
-    if (reinterpret_cast<uintptr_t>(d_out) & (pix - 1u))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the output must be %u-byte aligned", name, pix);
-    if ((reinterpret_cast<uintptr_t>(d_origins) | reinterpret_cast<uintptr_t>(d_counts) | reinterpret_cast<uintptr_t>(d_used)) & 3u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: origins, counts and used origins must be 4-byte aligned", name);
-    if (n_frames == 0) return DBDE_HIP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.dg, pix, pl.split);
-    if (rc) return rc;
-
-    PatchParams p;
-    memset(&p, 0, sizeof p);
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.origins = d_origins;
-    p.counts = d_counts;
-    p.out = static_cast<uint8_t *>(d_out);
-    p.used = d_used;
-    p.W = W;
-    p.H = H;
-    p.pw = pw;
-    p.ph = ph;
-    p.n_patches = (uint32_t)n_patches;
-    p.w = pl.g.w;
-    p.h = pl.g.h;
-    p.T = pl.g.T;
-    p.geom = pl.dg;
-    p.mtx = pl.mtx;
-    p.G = pl.G;
-    p.groups = pl.groups;
-    p.mode = edge_mode == DBDE_HIP_PATCH_FILL ? kPatchFill : kPatchClamp;
-    p.fill = fill;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_decode_patches(p, (uint32_t)n_frames, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_decode_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                            const uint64_t *d_frame_offsets, int W, int H, int n_frames, int pw, int ph, int n_patches,
-                            const int32_t *d_origins, const uint32_t *d_counts, int edge_mode, uint32_t fill,
-                            uint8_t *d_out, int32_t *d_used, dbde_hip_frame_result *d_results) {
-    return decode_patches_common(ctx, "decode_patches", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, pw,
-                                 ph, n_patches, d_origins, d_counts, edge_mode, fill, d_out, d_used, d_results);
-}
-
-int dbde16_hip_decode_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                              const uint64_t *d_frame_offsets, int W, int H, int n_frames, int pw, int ph, int n_patches,
-                              const int32_t *d_origins, const uint32_t *d_counts, int edge_mode, uint32_t fill,
-                              uint16_t *d_out, int32_t *d_used, dbde_hip_frame_result *d_results) {
-    return decode_patches_common(ctx, "decode_patches16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, pw,
-                                 ph, n_patches, d_origins, d_counts, edge_mode, fill, d_out, d_used, d_results);
-}
-
-// ---- patch moments ------------------------------------------------------------------------------------------
-// The sizes and the edge mode are the patch decoder's (plan_patches); what is added is the height limit that keeps every
-// sum inside 64 bits, and the launch: one workgroup per patch that walks the patch's groups of tile rows itself.
-static const char *plan_moments(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode, uint32_t pix,
-                                PatchPlan &pl) {
-    if (const char *why = plan_patches(W, H, n_frames, pw, ph, n_patches, edge_mode, pix, pl)) return why;
-    if (ph > kMomentMaxHeight) return "patch higher than 512 rows (the sums could pass 64 bits)";
-    static_assert(kMomentMaxTilesX == kPatchMaxTilesX && kMomentThreads == kPatchThreads, "plan_patches' geometry is the kernel's");
-    static_assert(kMomentClamp == DBDE_HIP_PATCH_CLAMP && kMomentFill == DBDE_HIP_PATCH_FILL, "edge modes");
-    static_assert(kMomentCount == DBDE_HIP_MOMENT_COUNT && kMomentValue == DBDE_HIP_MOMENT_VALUE &&
-                  kMomentAbove == DBDE_HIP_MOMENT_ABOVE && kMomentBelow == DBDE_HIP_MOMENT_BELOW, "weight modes");
-    return nullptr;
-}
-
-static int moments_plan_common(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode, uint32_t pix,
-                               dbde_hip_patch_moments_plan_t *plan) {
-    PatchPlan pl;
-    memset(&pl, 0, sizeof pl);
-    if (!plan || plan_moments(W, H, n_frames, pw, ph, n_patches, edge_mode, pix, pl)) return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->max_tiles_x = (int32_t)pl.mtx;
-    plan->max_tiles_y = (int32_t)pl.mty;
-    plan->rows_per_workgroup = pl.G;
-    plan->steps_per_patch = pl.groups;
-    plan->threads = kMomentThreads;
-    plan->chunks_per_frame = pl.dg.cpf;
-    plan->chunk_tiles = pl.dg.ct;
-    plan->chunk_pieces = pl.dg.ct == pl.g.w || pl.dg.pieces > 1u ? pl.dg.pieces : 0u;
-    plan->index_split = pl.split;
-    plan->lds_bytes = kMomentPayBytesOf(pix);
-    plan->grid = (uint64_t)n_frames * (uint64_t)n_patches;
-    plan->moments_bytes = plan->grid * 64u;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_patch_moments_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
-                                dbde_hip_patch_moments_plan_t *plan) {
-    return moments_plan_common(W, H, n_frames, pw, ph, n_patches, edge_mode, 1u, plan);
-}
-
-int dbde16_hip_patch_moments_plan(int W, int H, int n_frames, int pw, int ph, int n_patches, int edge_mode,
-                                  dbde_hip_patch_moments_plan_t *plan) {
-    return moments_plan_common(W, H, n_frames, pw, ph, n_patches, edge_mode, 2u, plan);
-}
-
-// Both calls: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the moments kernel in slot 2.
-static int patch_moments_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
-                                size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int pw,
-                                int ph, int n_patches, const int32_t *d_origins, const uint32_t *d_counts, int edge_mode,
-                                uint32_t lo, uint32_t hi, int weight_mode, uint64_t *d_moments, int32_t *d_bbox,
-                                int32_t *d_used, dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    PatchPlan pl;
-    memset(&pl, 0, sizeof pl);
-    if (const char *why = plan_moments(W, H, n_frames, pw, ph, n_patches, edge_mode, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d, %d patches of %dx%d, edge mode %d)", name, why, W, H,
-                    n_frames, n_patches, pw, ph, edge_mode);
-    if (!d_stream || !d_frame_offsets || !d_origins || !d_moments) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    const uint32_t pix_max = pix == 1u ? 0xFFu : 0xFFFFu;
-    if (lo > pix_max || hi > pix_max)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: threshold %u above %u", name, lo > pix_max ? lo : hi, pix_max);
-    if (weight_mode < DBDE_HIP_MOMENT_COUNT || weight_mode > DBDE_HIP_MOMENT_BELOW)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: unknown weight mode %d", name, weight_mode);
-    if (reinterpret_cast<uintptr_t>(d_moments) & 7u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the moments must be 8-byte aligned", name);
-    if ((reinterpret_cast<uintptr_t>(d_origins) | reinterpret_cast<uintptr_t>(d_counts) | reinterpret_cast<uintptr_t>(d_used) |
-         reinterpret_cast<uintptr_t>(d_bbox)) & 3u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: origins, counts, boxes and used origins must be 4-byte aligned", name);
-    if (n_frames == 0) return DBDE_HIP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.dg, pix, pl.split);
-    if (rc) return rc;
-
-    MomentParams p;
-    memset(&p, 0, sizeof p);
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.origins = d_origins;
-    p.counts = d_counts;
-    p.moments = d_moments;
-    p.bbox = d_bbox;
-    p.used = d_used;
-    p.W = W;
-    p.H = H;
-    p.pw = pw;
-    p.ph = ph;
-    p.n_patches = (uint32_t)n_patches;
-    p.w = pl.g.w;
-    p.h = pl.g.h;
-    p.T = pl.g.T;
-    p.geom = pl.dg;
-    p.mtx = pl.mtx;
-    p.G = pl.G;
-    p.steps = pl.groups;
-    p.mode = edge_mode == DBDE_HIP_PATCH_FILL ? kMomentFill : kMomentClamp;
-    p.lo = lo;
-    p.hi = hi;
-    p.weight = (uint32_t)weight_mode;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_patch_moments(p, (uint32_t)n_frames, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_patch_moments(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int pw, int ph, int n_patches,
-                           const int32_t *d_origins, const uint32_t *d_counts, int edge_mode, uint32_t lo, uint32_t hi,
-                           int weight_mode, uint64_t *d_moments, int32_t *d_bbox, int32_t *d_used,
-                           dbde_hip_frame_result *d_results) {
-    return patch_moments_common(ctx, "patch_moments", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, pw, ph,
-                                n_patches, d_origins, d_counts, edge_mode, lo, hi, weight_mode, d_moments, d_bbox, d_used,
-                                d_results);
-}
-
-int dbde16_hip_patch_moments(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                             const uint64_t *d_frame_offsets, int W, int H, int n_frames, int pw, int ph, int n_patches,
-                             const int32_t *d_origins, const uint32_t *d_counts, int edge_mode, uint32_t lo, uint32_t hi,
-                             int weight_mode, uint64_t *d_moments, int32_t *d_bbox, int32_t *d_used,
-                             dbde_hip_frame_result *d_results) {
-    return patch_moments_common(ctx, "patch_moments16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, pw,
-                                ph, n_patches, d_origins, d_counts, edge_mode, lo, hi, weight_mode, d_moments, d_bbox,
-                                d_used, d_results);
-}
-
-// ---- patch match --------------------------------------------------------------------------------------------
-// The search patch's size and the edge mode go through the patch decoder's plan (plan_patches); what is added are the
-// template and radius limits that keep an 8-bit entry inside 32 bits, the split of a shift's rows over lanes, and the LDS.
-struct MatchPlan {
-    PatchPlan pp;
-    int pw, ph;
-    uint32_t D, dwaves, steps, slices;
-    MatchLayout lds;
-    uint64_t surface_bytes;
-};
-static const char *plan_match(int W, int H, int n_frames, int tw, int th, int S, int n_patches, int n_templates,
-                              int edge_mode, uint32_t fill, unsigned stats, uint32_t pix, MatchPlan &pl) {
-    if (tw < 1 || th < 1 || tw > kMatchMaxTemplate || th > kMatchMaxTemplate) return "template size outside [1, 128]";
-    if (S < 0 || S > kMatchMaxRadius) return "search radius outside [0, 16]";
-    pl.pw = tw + 2 * S;
-    pl.ph = th + 2 * S;
-    if (const char *why = plan_patches(W, H, n_frames, pl.pw, pl.ph, n_patches, edge_mode, pix, pl.pp)) return why;
-    if (fill > (pix == 1u ? 0xFFu : 0xFFFFu)) return "fill above the pixel type";
-    if (n_templates != 1 && n_templates != n_patches) return "n_templates is neither 1 nor n_patches";
-    if (stats == 0u || (stats & ~7u)) return "stats empty or with unknown bits";
-    static_assert(kMatchClamp == DBDE_HIP_PATCH_CLAMP && kMatchFill == DBDE_HIP_PATCH_FILL, "edge modes");
-    static_assert(kMatchProd == DBDE_HIP_MATCH_PROD && kMatchSum == DBDE_HIP_MATCH_SUM && kMatchSq == DBDE_HIP_MATCH_SQ, "surfaces");
-    static_assert(kPatchThreads == 64u, "plan_patches' G is tile rows per wave");
-    pl.D = 2u * (uint32_t)S + 1u;
-    pl.dwaves = pl.pp.groups < kMatchWaves ? pl.pp.groups : kMatchWaves;
-    pl.steps = (pl.pp.groups + pl.dwaves - 1u) / pl.dwaves;
-    // the row slices: a lane's cost is its passes over the items times an item's cost, the batches of kMatchBatch dwords
-    // in the rows of its slice plus a fixed part: ceil(nsh r / 256) * (ceil(th / r) * batches + kMatchItemCost).  The count
-    // up to 16 (and th) with the least cost, the smallest on a tie
-    const uint32_t nsh = pl.D * pl.D, rmax = (uint32_t)th < kMatchMaxSlices ? (uint32_t)th : kMatchMaxSlices;
-    const uint32_t batches = (((uint32_t)tw * pix + 3u) / 4u + kMatchBatch - 1u) / kMatchBatch;
-    uint32_t best = 0xFFFFFFFFu;
-    pl.slices = 1u;
-    for (uint32_t r = 1; r <= rmax; r++) {
-        const uint32_t passes = (nsh * r + kMatchThreads - 1u) / kMatchThreads;
-        const uint32_t cost = passes * ((((uint32_t)th + r - 1u) / r) * batches + kMatchItemCost);
-        if (cost < best) {
-            best = cost;
-            pl.slices = r;
-        }
-    }
-    pl.lds = match_layout(pix, (uint32_t)tw, (uint32_t)th, (uint32_t)S, pl.pp.mtx, pl.pp.mty, pl.pp.G, pl.dwaves, pl.slices);
-    pl.surface_bytes = (uint64_t)n_frames * (uint64_t)n_patches * nsh * 8u;   // (below 2^31 * 1089 * 8)
-    return nullptr;
-}
-
-static int match_plan_common(int W, int H, int n_frames, int tw, int th, int S, int n_patches, int n_templates,
-                             int edge_mode, uint32_t fill, unsigned stats, uint32_t pix, dbde_hip_match_plan_t *plan) {
-    MatchPlan pl;
-    memset(&pl, 0, sizeof pl);
-    if (!plan || plan_match(W, H, n_frames, tw, th, S, n_patches, n_templates, edge_mode, fill, stats, pix, pl))
-        return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->pw = pl.pw;
-    plan->ph = pl.ph;
-    plan->D = (int32_t)pl.D;
-    plan->max_tiles_x = (int32_t)pl.pp.mtx;
-    plan->max_tiles_y = (int32_t)pl.pp.mty;
-    plan->rows_per_wave = pl.pp.G;
-    plan->decode_waves = pl.dwaves;
-    plan->steps_per_patch = pl.steps;
-    plan->row_slices = pl.slices;
-    plan->threads = kMatchThreads;
-    plan->chunks_per_frame = pl.pp.dg.cpf;
-    plan->chunk_tiles = pl.pp.dg.ct;
-    plan->chunk_pieces = pl.pp.dg.ct == pl.pp.g.w || pl.pp.dg.pieces > 1u ? pl.pp.dg.pieces : 0u;
-    plan->index_split = pl.pp.split;
-    plan->lds_bytes = pl.lds.bytes;
-    plan->grid = (uint64_t)n_frames * (uint64_t)n_patches;
-    plan->surface_bytes = pl.surface_bytes;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_match_plan(int W, int H, int n_frames, int tw, int th, int S, int n_patches, int n_templates,
-                        int edge_mode, uint32_t fill, unsigned stats, dbde_hip_match_plan_t *plan) {
-    return match_plan_common(W, H, n_frames, tw, th, S, n_patches, n_templates, edge_mode, fill, stats, 1u, plan);
-}
-
-int dbde16_hip_match_plan(int W, int H, int n_frames, int tw, int th, int S, int n_patches, int n_templates,
-                          int edge_mode, uint32_t fill, unsigned stats, dbde_hip_match_plan_t *plan) {
-    return match_plan_common(W, H, n_frames, tw, th, S, n_patches, n_templates, edge_mode, fill, stats, 2u, plan);
-}
-
-// Both calls: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the match kernel in slot 2.
-static int match_patches_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream,
-                                size_t stream_bytes, const uint64_t *d_frame_offsets, int W, int H, int n_frames, int tw,
-                                int th, int S, int n_patches, const int32_t *d_origins, const uint32_t *d_counts,
-                                int edge_mode, uint32_t fill, const void *d_templates, int n_templates, unsigned stats,
-                                uint64_t *d_prod, uint64_t *d_sum, uint64_t *d_sq, int32_t *d_used,
-                                dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    MatchPlan pl;
-    memset(&pl, 0, sizeof pl);
-    if (const char *why = plan_match(W, H, n_frames, tw, th, S, n_patches, n_templates, edge_mode, fill, stats, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d, %d patches, %d templates of %dx%d, radius %d, edge mode %d, "
-                    "fill %u, stats %u)", name, why, W, H, n_frames, n_patches, n_templates, tw, th, S, edge_mode, fill, stats);
-    if (!d_stream || !d_frame_offsets || !d_origins || !d_templates) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (reinterpret_cast<uintptr_t>(d_templates) & (pix - 1u))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: the templates must be %u-byte aligned", name, pix);
-    uint64_t *const surf[3] = {d_prod, d_sum, d_sq};
-    for (int i = 0; i < 3; i++)
-        if ((stats >> i & 1u) && (!surf[i] || (reinterpret_cast<uintptr_t>(surf[i]) & 7u)))
-            return fail(ctx, DBDE_HIP_ERR_ARG, "%s: a requested surface is null or not 8-byte aligned", name);
-    if ((reinterpret_cast<uintptr_t>(d_origins) | reinterpret_cast<uintptr_t>(d_counts) | reinterpret_cast<uintptr_t>(d_used)) & 3u)
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: origins, counts and used origins must be 4-byte aligned", name);
-    if (n_frames == 0) return DBDE_HIP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.pp.dg, pix, pl.pp.split);
-    if (rc) return rc;
-
-    MatchParams p;
-    memset(&p, 0, sizeof p);
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.origins = d_origins;
-    p.counts = d_counts;
-    p.templates = static_cast<const uint8_t *>(d_templates);
-    p.prod = (stats & DBDE_HIP_MATCH_PROD) ? d_prod : nullptr;
-    p.sum = (stats & DBDE_HIP_MATCH_SUM) ? d_sum : nullptr;
-    p.sq = (stats & DBDE_HIP_MATCH_SQ) ? d_sq : nullptr;
-    p.used = d_used;
-    p.W = W;
-    p.H = H;
-    p.pw = pl.pw;
-    p.ph = pl.ph;
-    p.tw = (uint32_t)tw;
-    p.th = (uint32_t)th;
-    p.D = pl.D;
-    p.n_patches = (uint32_t)n_patches;
-    p.per_patch = n_templates == 1 ? 0u : 1u;
-    p.w = pl.pp.g.w;
-    p.h = pl.pp.g.h;
-    p.T = pl.pp.g.T;
-    p.geom = pl.pp.dg;
-    p.mtx = pl.pp.mtx;
-    p.G = pl.pp.G;
-    p.dwaves = pl.dwaves;
-    p.steps = pl.steps;
-    p.slices = pl.slices;
-    p.mode = edge_mode == DBDE_HIP_PATCH_FILL ? kMatchFill : kMatchClamp;
-    p.fill = fill;
-    p.stats = stats;
-    p.lds = pl.lds;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_match_patches(p, (uint32_t)n_frames, pix, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_match_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int tw, int th, int S,
-                           int n_patches, const int32_t *d_origins, const uint32_t *d_counts, int edge_mode, uint32_t fill,
-                           const uint8_t *d_templates, int n_templates, unsigned stats, uint64_t *d_prod, uint64_t *d_sum,
-                           uint64_t *d_sq, int32_t *d_used, dbde_hip_frame_result *d_results) {
-    return match_patches_common(ctx, "match_patches", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, tw, th, S,
-                                n_patches, d_origins, d_counts, edge_mode, fill, d_templates, n_templates, stats, d_prod,
-                                d_sum, d_sq, d_used, d_results);
-}
-
-int dbde16_hip_match_patches(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                             const uint64_t *d_frame_offsets, int W, int H, int n_frames, int tw, int th, int S,
-                             int n_patches, const int32_t *d_origins, const uint32_t *d_counts, int edge_mode, uint32_t fill,
-                             const uint16_t *d_templates, int n_templates, unsigned stats, uint64_t *d_prod, uint64_t *d_sum,
-                             uint64_t *d_sq, int32_t *d_used, dbde_hip_frame_result *d_results) {
-    return match_patches_common(ctx, "match_patches16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, tw, th,
-                                S, n_patches, d_origins, d_counts, edge_mode, fill, d_templates, n_templates, stats, d_prod,
-                                d_sum, d_sq, d_used, d_results);
-}
-
-// ---- compressed-domain crop ---------------------------------------------------------------------------------
-struct CropPlan {
-    RoiPlan roi;                      // arguments, tile window and index geometry: the window decoder's (plan_roi)
-    uint32_t Tout, recoded;
-    uint64_t max_frame, capacity, rows;
-    uint64_t tables_bytes, rec_fixed_bytes, rec_origins_bytes;
-};
-static uint64_t crop_max_frame_bytes(uint64_t T, uint32_t pix) { return 20u + 12u + (pix == 2u ? 131u : 66u) * T; }
-static uint64_t round16(uint64_t v) { return (v + 15u) & ~(uint64_t)15; }
-static const char *plan_crop(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint64_t slot_stride,
-                             uint32_t pix, CropPlan &pl) {
-    if (const char *why = plan_roi(W, H, n_frames, x0, y0, rw, rh, pl.roi)) return why;
-    if ((x0 | y0) & 7) return "window origin not a multiple of 8";
-    const RoiPlan &r = pl.roi;
-    pl.Tout = r.ntx * r.nty;
-    pl.max_frame = crop_max_frame_bytes(pl.Tout, pix);
-    if (slot_stride && slot_stride < pl.max_frame) return "slot_stride below the cropped frame's worst case";
-    pl.capacity = n_frames == 0 ? 0u : (slot_stride ? (uint64_t)(n_frames - 1) * slot_stride + pl.max_frame : (uint64_t)n_frames * pl.max_frame);
-    pl.rows = (uint64_t)n_frames * r.nty;
-    if (pl.rows >= (1ull << 31)) return "too many workgroups in one call";
-    const uint32_t rm = (uint32_t)rw - 8u * (r.ntx - 1u), dm = (uint32_t)rh - 8u * (r.nty - 1u);
-    const uint32_t srm = (uint32_t)W - 8u * (r.tx0 + r.ntx - 1u), sdm = (uint32_t)H - 8u * (r.ty0 + r.nty - 1u);
-    const bool cut_col = rm != (srm < 8u ? srm : 8u), cut_row = dm != (sdm < 8u ? sdm : 8u);
-    pl.recoded = cut_row ? (cut_col ? r.ntx + r.nty - 1u : r.ntx) : (cut_col ? r.nty : 0u);
-    // three U32 per (frame, window tile row), two U64 per frame; the records behind them
-    pl.tables_bytes = round16(3u * 4u * pl.rows) + 2u * 8u * (uint64_t)n_frames;
-    pl.rec_origins_bytes = (uint64_t)n_frames * (r.ntx + r.nty - 1u) * kCropRecBytes;
-    pl.rec_fixed_bytes = pl.recoded ? pl.rec_origins_bytes : 0u;
-    return nullptr;
-}
-
-static int crop_plan_common(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint64_t slot_stride, uint32_t pix,
-                            dbde_hip_crop_plan_t *plan) {
-    CropPlan pl;
-    if (!plan || plan_crop(W, H, n_frames, x0, y0, rw, rh, slot_stride, pix, pl)) return DBDE_HIP_ERR_ARG;
-    memset(plan, 0, sizeof *plan);
-    plan->tile_x = (int32_t)pl.roi.tx0;
-    plan->tile_y = (int32_t)pl.roi.ty0;
-    plan->tiles_x = (int32_t)pl.roi.ntx;
-    plan->tiles_y = (int32_t)pl.roi.nty;
-    plan->out_tiles = pl.Tout;
-    plan->recoded_tiles = pl.recoded;
-    plan->chunks_per_frame = pl.roi.dg.cpf;
-    plan->chunk_tiles = pl.roi.dg.ct;
-    plan->chunk_pieces = pl.roi.dg.ct == pl.roi.g.w || pl.roi.dg.pieces > 1u ? pl.roi.dg.pieces : 0u;
-    plan->index_split = pl.roi.split;
-    plan->size_threads = kCropThreads;
-    plan->size_lds_bytes = kCropSizeLds;
-    plan->rows_threads = kCropThreads;
-    plan->rows_lds_bytes = kCropRowsLds;
-    plan->place_threads = kCropPlaceThreads;
-    plan->place_lds_bytes = kCropPlaceLds;
-    plan->copy_threads = kCropThreads;
-    plan->copy_lds_bytes = kCropCopyLds;
-    plan->repack_threads = kCropThreads;
-    plan->repack_lds_bytes = kCropRepackLds;
-    plan->repack_grid = pl.recoded ? (uint64_t)n_frames * ((pl.roi.ntx + pl.roi.nty - 1u + kCropThreads - 1u) / kCropThreads) : 0u;
-    plan->size_grid = pl.rows;
-    plan->rows_grid = (uint64_t)n_frames;
-    plan->place_grid = n_frames ? 1u : 0u;
-    plan->copy_grid = pl.rows;
-    plan->max_out_frame_bytes = pl.max_frame;
-    plan->out_capacity = pl.capacity;
-    plan->workspace_bytes = pl.tables_bytes + pl.rec_origins_bytes;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_crop_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint64_t slot_stride,
-                       dbde_hip_crop_plan_t *plan) {
-    return crop_plan_common(W, H, n_frames, x0, y0, rw, rh, slot_stride, 1u, plan);
-}
-
-int dbde16_hip_crop_plan(int W, int H, int n_frames, int x0, int y0, int rw, int rh, uint64_t slot_stride,
-                         dbde_hip_crop_plan_t *plan) {
-    return crop_plan_common(W, H, n_frames, x0, y0, rw, rh, slot_stride, 2u, plan);
-}
-
-// Both crops: the index (pix: 1 = DBDE, 2 = DBDE16, also its min_bytes) in timing slot 1, the crop kernels in slot 2.
-static int crop_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_stream, size_t stream_bytes,
-                       const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                       const int32_t *d_origins, uint8_t *d_out, size_t out_capacity, uint64_t slot_stride,
-                       uint64_t *d_out_offsets, uint64_t *d_out_bytes, int32_t *d_origins_used,
-                       dbde_hip_frame_result *d_results) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    CropPlan pl;
-    if (const char *why = plan_crop(W, H, n_frames, x0, y0, rw, rh, slot_stride, pix, pl))
-        return fail(ctx, DBDE_HIP_ERR_ARG, "%s: %s (W=%d H=%d n=%d window %dx%d at %d,%d)", name, why, W, H, n_frames, rw,
-                    rh, x0, y0);
-    if (!d_stream || !d_frame_offsets || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (n_frames == 0) return DBDE_HIP_OK;
-    if ((uint64_t)out_capacity < pl.capacity)
-        return fail(ctx, DBDE_HIP_ERR_CAPACITY, "%s: out_capacity %zu below the worst case %llu", name, out_capacity,
-                    (unsigned long long)pl.capacity);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t rec_bytes = d_origins ? pl.rec_origins_bytes : pl.rec_fixed_bytes;
-    int rc = grow(ctx, ctx->crop_ws, ctx->crop_ws_bytes, (size_t)(pl.tables_bytes + rec_bytes), 1);
-    if (rc) return rc;
-    rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, pl.roi.dg, pix, pl.roi.split);
-    if (rc) return rc;
-
-    CropParams p;
-    memset(&p, 0, sizeof p);
-    p.stream = d_stream;
-    p.frame_offsets = d_frame_offsets;
-    p.stream_bytes = stream_bytes;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
-    p.origins = d_origins;
-    p.origins_used = d_origins_used;
-    p.out = d_out;
-    p.slot_stride = slot_stride;
-    p.out_offsets = d_out_offsets;
-    p.out_bytes = d_out_bytes;
-    uint8_t *ws = ctx->crop_ws;
-    p.frame_bytes = reinterpret_cast<uint64_t *>(ws);
-    p.frame_off = p.frame_bytes + n_frames;
-    p.row_src = reinterpret_cast<uint32_t *>(ws + 16u * (size_t)n_frames);
-    p.row_copy = p.row_src + pl.rows;
-    p.row_words = p.row_copy + pl.rows;
-    p.rec = ws + pl.tables_bytes;
-    p.W = W;
-    p.H = H;
-    p.x0 = x0;
-    p.y0 = y0;
-    p.rw = rw;
-    p.rh = rh;
-    p.w = pl.roi.g.w;
-    p.T = pl.roi.g.T;
-    p.geom = pl.roi.dg;
-    p.ntx = pl.roi.ntx;
-    p.nty = pl.roi.nty;
-    p.Tout = pl.Tout;
-    p.n_frames = (uint32_t)n_frames;
-    span_begin(ctx, 2);
-    HIP_TRY(ctx, launch_crop(p, pix, d_origins != nullptr || pl.recoded != 0u, ctx->stream));
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_crop_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
-                         int W, int H, int n_frames, int x0, int y0, int rw, int rh, const int32_t *d_origins,
-                         uint8_t *d_out, size_t out_capacity, uint64_t slot_stride, uint64_t *d_out_offsets,
-                         uint64_t *d_out_bytes, int32_t *d_origins_used, dbde_hip_frame_result *d_results) {
-    return crop_common(ctx, "crop_frames", 1u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh,
-                       d_origins, d_out, out_capacity, slot_stride, d_out_offsets, d_out_bytes, d_origins_used, d_results);
-}
-
-int dbde16_hip_crop_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes,
-                           const uint64_t *d_frame_offsets, int W, int H, int n_frames, int x0, int y0, int rw, int rh,
-                           const int32_t *d_origins, uint8_t *d_out, size_t out_capacity, uint64_t slot_stride,
-                           uint64_t *d_out_offsets, uint64_t *d_out_bytes, int32_t *d_origins_used,
-                           dbde_hip_frame_result *d_results) {
-    return crop_common(ctx, "crop_frames16", 2u, d_stream, stream_bytes, d_frame_offsets, W, H, n_frames, x0, y0, rw, rh,
-                       d_origins, d_out, out_capacity, slot_stride, d_out_offsets, d_out_bytes, d_origins_used, d_results);
-}
 
 int dbde_hip_index_stream_async(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, int W, int H,
                                 int max_frames, uint64_t *d_frame_offsets, uint32_t *d_n_found) {
@@ -3778,177 +960,6 @@ int dbde16_hip_encode_frames(dbde_hip_ctx *ctx, const uint16_t *d_images, int W,
     return DBDE_HIP_OK;
 }
 
-// ---- window encode (include/dbde_hip.h) ------------------------------------------------------------
-struct WencPlan {
-    Geometry g;                       // of the window
-    uint64_t pitch, frame_stride, min_image_bytes, max_frame, capacity, workspace;
-    uint32_t lanes_per_row, units, cpf;
-    bool forwards;
-    int code;                         // of the broken rule
-};
-// nullptr when the arguments are good, else what is wrong with them (pl.code: the error code).  pix: 1 = DBDE, 2 = DBDE16.
-static const char *plan_wenc(uint64_t image_address, uint64_t image_bytes, int W, int H, uint64_t pitch, uint64_t frame_stride,
-                             int n_frames, int x0, int y0, int rw, int rh, bool has_origins, uint64_t out_capacity,
-                             bool check_capacity, uint64_t slot_stride, uint32_t pix, WencPlan &pl) {
-    pl.code = DBDE_HIP_ERR_ARG;
-    Geometry src;
-    if (n_frames < 0) return "n_frames < 0";
-    if (!geometry(W, H, src)) return "bad source size";
-    if (rw < 1 || rh < 1 || rw > W || rh > H) return "window size outside [1, W] x [1, H]";
-    if (x0 < 0 || y0 < 0 || x0 > W - rw || y0 > H - rh) return "window origin outside [0, W-rw] x [0, H-rh]";
-    if (!geometry(rw, rh, pl.g)) return "window too large";
-    const uint64_t row_bytes = (uint64_t)W * pix;
-    pl.pitch = pitch ? pitch : row_bytes;
-    if (pl.pitch < row_bytes) return "pitch below W * PIX";
-    if (pl.pitch >= (1ull << 40)) return "pitch too large";
-    const uint64_t frame_extent = (uint64_t)(H - 1) * pl.pitch + row_bytes;
-    pl.frame_stride = frame_stride ? frame_stride : (uint64_t)H * pl.pitch;
-    if (pl.frame_stride < frame_extent) return "frame_stride below (H-1) * pitch + W * PIX";
-    if (pl.frame_stride >= (1ull << 48)) return "frame_stride too large";
-    if (pix == 2u && ((pl.pitch | pl.frame_stride | image_address) & 1u)) return "DBDE16: odd pitch, frame_stride or base address";
-    pl.min_image_bytes = n_frames ? (uint64_t)(n_frames - 1) * pl.frame_stride + frame_extent : 0u;
-    if (image_bytes < pl.min_image_bytes) return "image_bytes below (n-1) * frame_stride + (H-1) * pitch + W * PIX";
-    pl.max_frame = 32ull + (pix == 2u ? 131ull : 66ull) * pl.g.T;
-    pl.capacity = n_frames == 0 ? 0u : (slot_stride ? (uint64_t)(n_frames - 1) * slot_stride + pl.max_frame : (uint64_t)n_frames * pl.max_frame);
-    if (slot_stride && slot_stride < pl.max_frame) {
-        if (pix == 2u) pl.code = DBDE_HIP_ERR_CAPACITY;   // (each as its frame encoder reports it)
-        return "slot_stride below the window's worst case";
-    }
-    if (check_capacity && out_capacity < pl.capacity) { pl.code = DBDE_HIP_ERR_CAPACITY; return "out_capacity below the worst case"; }
-    pl.forwards = !has_origins && rw == W && rh == H && pl.pitch == row_bytes && pl.frame_stride == (uint64_t)H * row_bytes;
-    pl.lanes_per_row = pix == 2u ? pl.g.w : (pl.g.w + 1u) / 2u;
-    const uint64_t units = (uint64_t)pl.g.h * pl.lanes_per_row;
-    pl.units = (uint32_t)units;
-    pl.cpf = (uint32_t)((units + kWencThreads - 1u) / kWencThreads);
-    if (!pl.forwards && (uint64_t)n_frames * pl.cpf >= (1ull << 31)) return "too many chunks in one call";
-    const uint64_t n = (uint64_t)n_frames, gpf = (pl.cpf + kWencGroup - 1u) / kWencGroup;
-    pl.workspace = 16u + 8u * (n * pl.cpf + n * gpf + n + (n + kWencGroup - 1u) / kWencGroup);
-    return nullptr;
-}
-
-static int wenc_plan_common(uint64_t image_address, size_t image_bytes, int W, int H, uint64_t pitch, uint64_t frame_stride,
-                            int n_frames, int x0, int y0, int rw, int rh, int has_origins, size_t out_capacity,
-                            uint64_t slot_stride, int n_cu, uint32_t pix, dbde_hip_window_encode_plan_t *plan) {
-    WencPlan pl;
-    if (!plan || n_cu < 1) return DBDE_HIP_ERR_ARG;
-    if (plan_wenc(image_address, image_bytes, W, H, pitch, frame_stride, n_frames, x0, y0, rw, rh, has_origins != 0,
-                  out_capacity, out_capacity != 0, slot_stride, pix, pl))
-        return pl.code;
-    memset(plan, 0, sizeof *plan);
-    plan->forwards = pl.forwards ? 1u : 0u;
-    plan->tiles_x = pl.g.w;
-    plan->tiles_y = pl.g.h;
-    plan->tiles = pl.g.T;
-    plan->pitch = pl.pitch;
-    plan->frame_stride = pl.frame_stride;
-    plan->min_image_bytes = pl.min_image_bytes;
-    plan->max_out_frame_bytes = pl.max_frame;
-    plan->out_capacity = pl.capacity;
-    if (pl.forwards) return DBDE_HIP_OK;
-    plan->lanes_per_row = pl.lanes_per_row;
-    plan->chunks_per_frame = pl.cpf;
-    plan->chunk_tiles = wenc_chunk_tiles(pix);
-    plan->record_group = kWencGroup;
-    plan->threads = kWencThreads;
-    plan->lds_bytes = kWencLdsBytes;
-    const uint64_t chunks = (uint64_t)n_frames * pl.cpf, resident = (uint64_t)n_cu * kWencBlocksPerCu;
-    plan->grid = chunks < resident ? chunks : resident;
-    plan->workspace_bytes = pl.workspace;
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_window_encode_plan(uint64_t image_address, size_t image_bytes, int W, int H, uint64_t pitch, uint64_t frame_stride,
-                                int n_frames, int x0, int y0, int rw, int rh, int has_origins, size_t out_capacity,
-                                uint64_t slot_stride, int n_cu, dbde_hip_window_encode_plan_t *plan) {
-    return wenc_plan_common(image_address, image_bytes, W, H, pitch, frame_stride, n_frames, x0, y0, rw, rh, has_origins,
-                            out_capacity, slot_stride, n_cu, 1u, plan);
-}
-
-int dbde16_hip_window_encode_plan(uint64_t image_address, size_t image_bytes, int W, int H, uint64_t pitch, uint64_t frame_stride,
-                                  int n_frames, int x0, int y0, int rw, int rh, int has_origins, size_t out_capacity,
-                                  uint64_t slot_stride, int n_cu, dbde_hip_window_encode_plan_t *plan) {
-    return wenc_plan_common(image_address, image_bytes, W, H, pitch, frame_stride, n_frames, x0, y0, rw, rh, has_origins,
-                            out_capacity, slot_stride, n_cu, 2u, plan);
-}
-
-// Both window encoders (pix: 1 = DBDE, 2 = DBDE16), timing slot 0.
-static int encode_window_common(dbde_hip_ctx *ctx, const char *name, uint32_t pix, const uint8_t *d_images, size_t image_bytes,
-                                int W, int H, uint64_t pitch, uint64_t frame_stride, int n_frames, int x0, int y0, int rw, int rh,
-                                const int32_t *d_origins, uint64_t first_index, const uint64_t *d_indices,
-                                const uint64_t *d_elapsed_ns, uint8_t *d_out, size_t out_capacity, uint64_t slot_stride,
-                                uint64_t *d_frame_offsets, uint64_t *d_frame_bytes) {
-    if (!ctx) return DBDE_HIP_ERR_ARG;
-    WencPlan pl;
-    if (const char *why = plan_wenc(reinterpret_cast<uintptr_t>(d_images), image_bytes, W, H, pitch, frame_stride, n_frames, x0,
-                                    y0, rw, rh, d_origins != nullptr, out_capacity, true, slot_stride, pix, pl))
-        return fail(ctx, pl.code, "%s: %s (W=%d H=%d pitch=%llu stride=%llu n=%d window %dx%d at %d,%d)", name, why, W, H,
-                    (unsigned long long)pitch, (unsigned long long)frame_stride, n_frames, rw, rh, x0, y0);
-    if (!d_images || !d_out) return fail(ctx, DBDE_HIP_ERR_ARG, "%s: null pointer", name);
-    if (n_frames == 0) return DBDE_HIP_OK;
-    if (pl.forwards)   // exactly the frame encoders' layout: the plain case stays on the persistent encoder
-        return pix == 2u ? dbde16_hip_encode_frames(ctx, reinterpret_cast<const uint16_t *>(d_images), W, H, n_frames, first_index,
-                                                    d_out, out_capacity, slot_stride, d_frame_offsets, d_frame_bytes)
-                         : dbde_hip_encode_frames(ctx, d_images, W, H, n_frames, first_index, d_indices, d_elapsed_ns, d_out,
-                                                  out_capacity, slot_stride, d_frame_offsets, d_frame_bytes);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = grow(ctx, ctx->w16, ctx->w16_bytes, (size_t)pl.workspace, 1, true);
-    if (rc) return rc;
-    WencParams p;
-    memset(&p, 0, sizeof p);
-    p.images = d_images;
-    p.image_bytes = image_bytes;
-    p.pitch = pl.pitch;
-    p.frame_stride = pl.frame_stride;
-    p.origins = d_origins;
-    p.W = W; p.H = H; p.x0 = x0; p.y0 = y0; p.rw = rw; p.rh = rh;
-    p.narrow = (uint32_t)rw * pix < 16u ? 1u : 0u;
-    p.out = d_out;
-    p.frame_offsets = d_frame_offsets;
-    p.frame_bytes = d_frame_bytes;
-    p.indices = d_indices;
-    p.elapsed_ns = d_elapsed_ns;
-    p.first_index = first_index;
-    p.slot_stride = slot_stride;
-    p.w = pl.g.w; p.h = pl.g.h; p.T = pl.g.T;
-    p.lanes_per_row = pl.lanes_per_row;
-    p.units = pl.units;
-    p.chunks_per_frame = pl.cpf;
-    p.n_frames = (uint32_t)n_frames;
-    const size_t n = (size_t)n_frames, gpf = (pl.cpf + kWencGroup - 1u) / kWencGroup;
-    p.ticket = reinterpret_cast<uint32_t *>(ctx->w16);
-    p.state = reinterpret_cast<unsigned long long *>(ctx->w16 + 16);
-    p.gsum = p.state + n * pl.cpf;
-    p.fsize = p.gsum + n * gpf;
-    p.fgsum = p.fsize + n;
-    p.sticky = ctx->sticky;
-    p.force_tickets = (ctx->exp_flags & 1u) ? 1u : 0u;
-    uint32_t &resident = ctx->wenc_grid[pix - 1u];
-    if (!resident) resident = (uint32_t)(wenc_blocks_per_cu(pix) * ctx->n_cu);
-    span_begin(ctx, 0);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->w16, 0, (size_t)pl.workspace, ctx->stream));
-    HIP_TRY(ctx, launch_encode_window(p, pix, (ctx->exp_flags & 1024u) ? 3u : resident, ctx->stream));   // (experiment bit 10: three workgroups)
-    span_end(ctx);
-    return DBDE_HIP_OK;
-}
-
-int dbde_hip_encode_window(dbde_hip_ctx *ctx, const uint8_t *d_images, size_t image_bytes, int W, int H, uint64_t pitch,
-                           uint64_t frame_stride, int n_frames, int x0, int y0, int rw, int rh, const int32_t *d_origins,
-                           uint64_t first_index, const uint64_t *d_indices, const uint64_t *d_elapsed_ns, uint8_t *d_out,
-                           size_t out_capacity, uint64_t slot_stride, uint64_t *d_frame_offsets, uint64_t *d_frame_bytes) {
-    return encode_window_common(ctx, "encode_window", 1u, d_images, image_bytes, W, H, pitch, frame_stride, n_frames, x0, y0, rw,
-                                rh, d_origins, first_index, d_indices, d_elapsed_ns, d_out, out_capacity, slot_stride,
-                                d_frame_offsets, d_frame_bytes);
-}
-
-int dbde16_hip_encode_window(dbde_hip_ctx *ctx, const uint16_t *d_images, size_t image_bytes, int W, int H, uint64_t pitch,
-                             uint64_t frame_stride, int n_frames, int x0, int y0, int rw, int rh, const int32_t *d_origins,
-                             uint64_t first_index, uint8_t *d_out, size_t out_capacity, uint64_t slot_stride,
-                             uint64_t *d_frame_offsets, uint64_t *d_frame_bytes) {
-    return encode_window_common(ctx, "encode_window16", 2u, reinterpret_cast<const uint8_t *>(d_images), image_bytes, W, H, pitch,
-                                frame_stride, n_frames, x0, y0, rw, rh, d_origins, first_index, nullptr, nullptr, d_out,
-                                out_capacity, slot_stride, d_frame_offsets, d_frame_bytes);
-}
-
 int dbde16_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t stream_bytes, const uint64_t *d_frame_offsets,
                              int W, int H, int n_frames, uint16_t *d_images, dbde_hip_frame_result *d_results) {
     if (!ctx) return DBDE_HIP_ERR_ARG;
@@ -3965,12 +976,8 @@ int dbde16_hip_decode_frames(dbde_hip_ctx *ctx, const uint8_t *d_stream, size_t 
     int rc = run_index(ctx, d_stream, stream_bytes, d_frame_offsets, n_frames, d_results, dg, 2u, 1u);
     if (rc) return rc;
     dbde16::DecParams16 p;
-    p.stream = d_stream;
-    p.stream_bytes = stream_bytes;
-    p.frame_offsets = d_frame_offsets;
+    set_stream(p, ctx, d_stream, stream_bytes, d_frame_offsets);
     p.images = d_images;
-    p.chunk_off = ctx->chunk_off;
-    p.frame_ok = ctx->frame_ok;
     p.frame_pixels = g.pixels;
     p.W = W; p.H = H; p.w = g.w; p.h = g.h; p.T = g.T;
     p.chunks_per_frame = dg.cpf;

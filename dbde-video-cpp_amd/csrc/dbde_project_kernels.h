@@ -61,5 +61,7 @@ hipError_t launch_project_combine(const ProjParams &p, uint32_t pix, hipStream_t
 // sum, sumsq, each 16-byte aligned.  pix: 1 = DBDE (U8 max / min, U32 sums), 2 = DBDE16 (U16 max / min, U32 sums, U64
 // sums of squares).
 uint64_t project_workspace_bytes(uint32_t stats, uint32_t segments, uint64_t pixels, uint32_t pix);
+// Bytes of one statistic's partials (bit: one of kProj*), rounded up to 16.
+uint64_t project_partial_bytes(uint32_t bit, uint32_t segments, uint64_t pixels, uint32_t pix);
 
 }  // namespace dbde

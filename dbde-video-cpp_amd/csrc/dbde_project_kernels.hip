@@ -380,13 +380,18 @@ __global__ __launch_bounds__(kProjCombineThreads) void project_combine_kernel(Pr
     if (blockIdx.x == 0u) write_count(p);
 }
 
-uint64_t project_workspace_bytes(uint32_t stats, uint32_t segments, uint64_t pixels, uint32_t pix) {
+uint64_t project_partial_bytes(uint32_t bit, uint32_t segments, uint64_t pixels, uint32_t pix) {
     if (segments <= 1u) return 0;
     const uint64_t n = (uint64_t)segments * pixels;
-    const uint64_t mm = (pix * n + 15u) & ~(uint64_t)15, u32 = (4u * n + 15u) & ~(uint64_t)15;
-    const uint64_t sq = pix == 1u ? u32 : (8u * n + 15u) & ~(uint64_t)15;   // DBDE16: U64 sums of squares
-    return ((stats & kProjMax) ? mm : 0) + ((stats & kProjMin) ? mm : 0) + ((stats & kProjSum) ? u32 : 0) +
-           ((stats & kProjSumSq) ? sq : 0);
+    const uint64_t width = bit == kProjSum ? 4u : bit == kProjSumSq ? 4u * pix : pix;   // DBDE16: U64 sums of squares
+    return (width * n + 15u) & ~(uint64_t)15;
+}
+
+uint64_t project_workspace_bytes(uint32_t stats, uint32_t segments, uint64_t pixels, uint32_t pix) {
+    uint64_t total = 0;
+    for (uint32_t bit = 1u; bit <= kProjSumSq; bit <<= 1)
+        if (stats & bit) total += project_partial_bytes(bit, segments, pixels, pix);
+    return total;
 }
 
 typedef void (*ProjKernel)(ProjParams);

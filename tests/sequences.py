@@ -67,7 +67,7 @@ def split_for(n, cpf):
 
 
 def grown(cap, want):
-    """grow() of dbde_capi.cpp: the capacity after a request for `want` elements."""
+    """grow() of dbde_host.h: the capacity after a request for `want` elements."""
     return cap if want <= cap else want + want // 4 + 64
 
 
