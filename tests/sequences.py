@@ -315,6 +315,10 @@ def frames_of(pool, prm):
 
 
 def window_of(pool, prm):
+    """The step's window: prm["win"] = (x, y, rw, rh) where the step brings its own (tests/geometry_cases.py), else
+    entry prm["w"] of the pool geometry's WINDOWS."""
+    if prm.get("win") is not None:
+        return tuple(prm["win"])
     return WINDOWS[(pool.W, pool.H)][prm.get("w", 0)]
 
 
@@ -325,10 +329,13 @@ def stream_args(pool, prm):
 
 
 def origins_of(pool, prm):
-    """Per-frame origins (host, (n, 2) int32) of a step that asks for them, else None."""
+    """Per-frame origins (host, (n, 2) int32) of a step that asks for them, else None: prm["origins"] (one (x, y) per
+    pool frame) where the step brings its own, else (prm["org"]) random ones."""
+    f0, n = frames_of(pool, prm)
+    if prm.get("origins") is not None:
+        return np.array(prm["origins"], np.int32).reshape(-1, 2)[f0:f0 + n]
     if not prm.get("org"):
         return None
-    f0, n = frames_of(pool, prm)
     rng = np.random.default_rng(pool.W * 131 + pool.H * 7 + n + f0)
     return np.stack([rng.integers(-3, pool.W + 3, n), rng.integers(-3, pool.H + 3, n)], 1).astype(np.int32)
 
@@ -338,7 +345,7 @@ def origins_dev(pool, prm):
     org = origins_of(pool, prm)
     if org is None:
         return None
-    return const(("org", pool.name) + frames_of(pool, prm), lambda: torch.from_numpy(org).cuda())
+    return const(("org", pool.name, prm.get("origins")) + frames_of(pool, prm), lambda: torch.from_numpy(org).cuda())
 
 
 def pix_dtype(bits):
@@ -501,6 +508,11 @@ LABEL_COUNTS = {"few": 7, "many": 40}
 
 
 def labels_of(pool, prm):
+    if prm.get("label_windows") is not None:     # label k + 1 = the k-th window (x, y, rw, rh); later ones over earlier ones
+        lab = np.zeros((pool.H, pool.W), np.int32)
+        for k, (x, y, rw, rh) in enumerate(prm["label_windows"]):
+            lab[y:y + rh, x:x + rw] = k + 1
+        return lab, len(prm["label_windows"])
     lab, L = map_discs(pool.W, pool.H, seed=5, count=LABEL_COUNTS[prm.get("labels", "few")])
     lab[:, : pool.W // 4] = 0          # untouched tiles too
     return lab, L
@@ -508,7 +520,7 @@ def labels_of(pool, prm):
 
 def _trace_map(codec, pool, prm):
     maps = codec.__dict__.setdefault("_sequence_maps", {})
-    key = (pool.W, pool.H, prm.get("labels", "few"))
+    key = (pool.W, pool.H, prm.get("labels", "few"), prm.get("label_windows"))
     if key not in maps:
         maps[key] = codec.trace_map(*labels_of(pool, prm))
     return maps[key]
@@ -516,7 +528,7 @@ def _trace_map(codec, pool, prm):
 
 def _trace_outputs(pool, prm):
     f0, n = frames_of(pool, prm)
-    L = LABEL_COUNTS[prm.get("labels", "few")]
+    L = len(prm["label_windows"]) if prm.get("label_windows") is not None else LABEL_COUNTS[prm.get("labels", "few")]
     spec = {s: ((n, L), pix_dtype(pool.bits) if s in ("max", "min") else "int64") for s in prm.get("stats", ALL4)}
     return dict(spec, **results_spec(n))
 
@@ -824,8 +836,11 @@ def band_of(pool, prm):
 
 
 def patch_origins_of(pool, prm):
-    """(n, K, 2) int64 origins: inside the frame, across its edges and wholly outside it."""
+    """(n, K, 2) int64 origins: prm["porg"] (K per pool frame) where the step brings its own, else random ones inside
+    the frame, across its edges and wholly outside it."""
     f0, n = frames_of(pool, prm)
+    if prm.get("porg") is not None:
+        return np.array(prm["porg"], np.int64).reshape(-1, PATCHES_PER_FRAME, 2)[f0:f0 + n]
     pw, ph = PATCH
     rng = np.random.default_rng(pool.W * 137 + pool.H * 11 + n + f0)
     org = np.stack([rng.integers(-pw - 2, pool.W + 3, (n, PATCHES_PER_FRAME)),
@@ -849,7 +864,7 @@ def _patch_inputs(pool, prm):
     """The device origins (for a call without frames: those of one frame, which is never read) and counts."""
     import torch
     f0, n = frames_of(pool, prm)
-    key = (pool.name, f0, n, bool(prm.get("counts")))
+    key = (pool.name, f0, n, bool(prm.get("counts")), prm.get("porg"))
     src = prm if n else dict(prm, n=1)
     org = const(("patch_org",) + key, lambda: torch.from_numpy(patch_origins_of(pool, src).astype(np.int32)).cuda())
     cnt = patch_counts_of(pool, src)
