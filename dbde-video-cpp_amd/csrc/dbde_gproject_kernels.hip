@@ -22,20 +22,17 @@
 #include <type_traits>
 #include <utility>
 
-#include "dbde_bits.h"
-#include "dbde_device.h"
+#include "dbde_proj_pipeline.h"
 
 namespace dbde {
 
 namespace {
 
 constexpr uint32_t kGProjStep = 4;                 // slots per pipeline step
-constexpr uint32_t kGProjWaves = kProjThreads / 64u;
 
 template <uint32_t PIX> using GProjPix = typename std::conditional<PIX == 1u, uint8_t, uint16_t>::type;
 template <uint32_t PIX> using GProjSq = typename std::conditional<PIX == 1u, uint32_t, uint64_t>::type;
 
-__device__ __forceinline__ uint32_t readlane(uint32_t v, uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j); }
 __device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 }  // namespace
@@ -48,7 +45,7 @@ __global__ __launch_bounds__(kProjThreads) void gproject_kernel(GProjParams p) {
     constexpr bool kSum = (STATS & kProjSum) != 0u, kSq = (STATS & kProjSumSq) != 0u;
     constexpr uint32_t G = kGProjStep, kTiles = kProjTilesOf(PIX), kDmax = 8u * PIX, kNpx = 8u / PIX;   // kNpx: pixels per lane
     constexpr uint32_t kPixMask = PIX == 1u ? 0xFFu : 0xFFFFu;
-    __shared__ uint32_t s_wsum[2][G][2][kGProjWaves];   // per step (double-buffered): wave depth totals, sums in front
+    __shared__ uint32_t s_wsum[2][G][2][kProjWaves];   // per step (double-buffered): wave depth totals, sums in front
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     // tile of the piece, row of the tile, half of the row (PIX 2)
@@ -166,16 +163,6 @@ __global__ __launch_bounds__(kProjThreads) void gproject_kernel(GProjParams p) {
             }
         }
     };
-    // the mask of the depth bytes [cb, pos0) in this lane's pre dword of frame fb
-    auto pre_keep = [&](const uint8_t *fb) __attribute__((always_inline)) -> uint32_t {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(fb + 24 + cb);
-        const uint32_t head = (uint32_t)(a & 3u), ndw = (head + npre + 3u) >> 2;
-        if (tid >= ndw) return 0u;
-        const uint32_t lo = 4u * tid < head ? head - 4u * tid : 0u;   // bytes in front of cb
-        const uint32_t hi = head + npre - 4u * tid;                   // bytes before pos0
-        return (hi >= 4u ? ~0u : (1u << (8u * hi)) - 1u) & ~((1u << (8u * lo)) - 1u);
-    };
-
     // the step's tile offsets (one barrier) and its payload loads
     uint32_t buf = 0;
     auto issue_payload = [&](const Meta &m, Pay &q) __attribute__((always_inline)) {
@@ -192,7 +179,7 @@ __global__ __launch_bounds__(kProjThreads) void gproject_kernel(GProjParams p) {
         for (uint32_t k = 0; k < G; k++) {
             const uint32_t d = has_tile ? (m.d8[k] > kDmax ? kDmax : m.d8[k]) : 0u;   // (a validated frame has none above)
             incl[k] = wave_scan_incl((PIX == 1u ? r == 0u : (tid & 15u) == 0u) ? d : 0u);   // the tile's first lane
-            const uint32_t pw = wave_sum(__builtin_amdgcn_sad_u8(m.pre[k] & pre_keep(m.fb[k]), 0u, 0u));
+            const uint32_t pw = wave_sum(__builtin_amdgcn_sad_u8(m.pre[k] & pre_keep(m.fb[k], cb, npre, tid), 0u, 0u));
             if (lane == 63u) s_wsum[buf][k][0][wave] = incl[k];
             if (lane == 0u) s_wsum[buf][k][1][wave] = pw;
         }
@@ -201,7 +188,7 @@ __global__ __launch_bounds__(kProjThreads) void gproject_kernel(GProjParams p) {
         for (uint32_t k = 0; k < G; k++) {
             uint32_t wbase = 0, PRE = 0;
 #pragma unroll
-            for (uint32_t w = 0; w < kGProjWaves; w++) {
+            for (uint32_t w = 0; w < kProjWaves; w++) {
                 wbase += w < wave ? s_wsum[buf][k][0][w] : 0u;
                 PRE += s_wsum[buf][k][1][w];
             }
@@ -321,15 +308,9 @@ __global__ __launch_bounds__(kProjThreads) void gproject_kernel(GProjParams p) {
         for (uint32_t k = 0; k < G; k++) {
             if (m.ok[k]) {   // (a rejected frame, an empty group's slot or padding contributes nothing)
                 cnt++;
+                uint32_t px[2];
+                cut_row<PIX>(q.a0[k], q.a1[k], q.a2[k], q.dms[k], hh, px[0], px[1]);
                 if constexpr (PIX == 1u) {
-                    const uint32_t d = q.dms[k] & 0xFFu, sh = q.dms[k] >> 16;
-                    const uint32_t mm = ((q.dms[k] >> 8) & 0xFFu) * 0x01010101u;
-                    const uint64_t bits = (uint64_t)__builtin_amdgcn_alignbyte(q.a1[k], q.a0[k], sh) |
-                                          ((uint64_t)__builtin_amdgcn_alignbyte(q.a2[k], q.a1[k], sh) << 32);
-                    uint32_t px[2];
-                    expand_row(bits, d, px[0], px[1]);
-                    px[0] = add_bytes(px[0], mm);
-                    px[1] = add_bytes(px[1], mm);
 #pragma unroll
                     for (int h = 0; h < 2; h++) {
                         const uint32_t e = px[h] & 0x00FF00FFu;
@@ -343,20 +324,13 @@ __global__ __launch_bounds__(kProjThreads) void gproject_kernel(GProjParams p) {
                         }
                     }
                 } else {
-                    const uint32_t d = q.dms[k] & 0xFFu, sh = (q.dms[k] >> 8) & 0xFFu, so = 4u * hh * (d & 1u);
-                    const uint32_t m32 = d >= 16u ? 0xFFFFu : (1u << d) - 1u, mn2 = (q.dms[k] >> 16) * 0x00010001u;
-                    const bool c2 = 2u * d >= 32u, c3 = 3u * d >= 32u;
-                    const uint32_t x0 = __builtin_amdgcn_alignbyte(q.a1[k], q.a0[k], sh);
-                    const uint32_t x1 = __builtin_amdgcn_alignbyte(q.a2[k], q.a1[k], sh);
-                    uint32_t e[2];
-                    cut_four16(__builtin_amdgcn_alignbit(x1, x0, so), x1 >> so, d, m32, mn2, c2, c3, e[0], e[1]);
 #pragma unroll
                     for (int j = 0; j < 2; j++) {
-                        if (kMax) mx[j] = pk_max_u16(mx[j], e[j]);
-                        if (kMin) mn[j] = pk_min_u16(mn[j], e[j]);
+                        if (kMax) mx[j] = pk_max_u16(mx[j], px[j]);
+                        if (kMin) mn[j] = pk_min_u16(mn[j], px[j]);
 #pragma unroll
                         for (int i = 0; i < 2; i++) {
-                            const uint32_t v = (e[j] >> (16 * i)) & 0xFFFFu;
+                            const uint32_t v = (px[j] >> (16 * i)) & 0xFFFFu;
                             if (kSum) sum[2 * j + i] += v;
                             if (kSq) sq[2 * j + i] += (uint64_t)(v * v);   // v * v < 2^32; the add carries into the high dword
                         }

@@ -4,7 +4,7 @@
 // written).  DESIGN.md 4.20.
 //
 // pairs_kernel<MASK, PIX>: MASK = 1, 3 or 15, the instance's offsets (kPairsInstanceOf), PIX = 1 for DBDE frames,
-// PIX = 2 for DBDE16 frames.  The launch shape and the load pipeline are project_kernel's (dbde_project_kernels.hip),
+// PIX = 2 for DBDE16 frames.  The launch shape and the load pipeline are project_kernel's (dbde_proj_pipeline.h),
 // as counts_kernel took them: one 256-lane workgroup per (frame segment, window tile row, piece), one lane per tile
 // row (PIX 2: per half row), the segment's frames walked in groups of kPairsGroup with the payload loads of group
 // k + 1, the depth / minimum loads of group k + 2 and the per-frame words of group k + 3 in flight while group k is
@@ -33,20 +33,15 @@
 
 #include <type_traits>
 
-#include "dbde_bits.h"
-#include "dbde_device.h"
+#include "dbde_proj_pipeline.h"
 
 namespace dbde {
 
 namespace {
 
-constexpr uint32_t kPairsWaves = kProjThreads / 64u;
-
-__device__ __forceinline__ uint32_t readlane(uint32_t v, uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j); }
-
 // Frames of [0, p.n_frames) that the index accepted -> *p.out_count (added to it when accumulating).  Whole workgroup.
 __device__ void write_count(const PairsParams &p) {
-    __shared__ uint32_t s_c[kPairsWaves];
+    __shared__ uint32_t s_c[kProjWaves];
     const uint32_t tid = threadIdx.x;
     uint32_t c = 0;
     for (uint32_t g = tid; g < p.n_frames; g += kProjThreads) c += p.frame_ok[g] != 0u ? 1u : 0u;
@@ -55,7 +50,7 @@ __device__ void write_count(const PairsParams &p) {
     __syncthreads();
     if (tid == 0) {
         uint64_t total = 0;
-        for (uint32_t k = 0; k < kPairsWaves; k++) total += s_c[k];
+        for (uint32_t k = 0; k < kProjWaves; k++) total += s_c[k];
         *p.out_count = (p.accumulate ? *p.out_count : 0ull) + total;
     }
 }
@@ -77,7 +72,7 @@ __global__ __launch_bounds__(kProjThreads) void pairs_kernel(PairsParams p) {
     constexpr uint32_t NR = kBelow ? 2u : 1u;                    // prefixes: the piece's tile row, the tile row below
     constexpr uint32_t NB = popc(MASK), kRows = kPairsBandRowsOf(MASK), kRowDw = kPairsRowDwords;
     typedef typename std::conditional<PIX == 1u, uint32_t, uint64_t>::type Acc;
-    __shared__ uint32_t s_wsum[2][G][NR][2][kPairsWaves];   // per group of frames (double-buffered): wave depth totals, sums in front
+    __shared__ uint32_t s_wsum[2][G][NR][2][kProjWaves];   // per group of frames (double-buffered): wave depth totals, sums in front
     __shared__ __attribute__((aligned(8))) uint32_t s_band[2][G][kRows][kRowDw];
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -187,16 +182,6 @@ __global__ __launch_bounds__(kProjThreads) void pairs_kernel(PairsParams p) {
             }
         }
     };
-    // the mask of the depth bytes [cb, pos0) in this lane's pre dword of frame fb
-    auto pre_keep = [&](const uint8_t *fb, uint32_t rr) __attribute__((always_inline)) -> uint32_t {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(fb + 24 + cb[rr]);
-        const uint32_t head = (uint32_t)(a & 3u), ndw = (head + npre[rr] + 3u) >> 2;
-        if (tid >= ndw) return 0u;
-        const uint32_t lo = 4u * tid < head ? head - 4u * tid : 0u;   // bytes in front of cb
-        const uint32_t hi = head + npre[rr] - 4u * tid;               // bytes before pos0
-        return (hi >= 4u ? ~0u : (1u << (8u * hi)) - 1u) & ~((1u << (8u * lo)) - 1u);
-    };
-
     // the group's tile offsets (the group's one barrier, which also publishes the band written in front of it) and its
     // payload loads.  In the row below only the lanes of tile row 0 load: its row 0 is all that is needed.
     uint32_t buf = 0;
@@ -220,7 +205,7 @@ __global__ __launch_bounds__(kProjThreads) void pairs_kernel(PairsParams p) {
             for (uint32_t k = 0; k < G; k++) {
                 const uint32_t d = has_tile ? (m.d8[rr][k] > kDmax ? kDmax : m.d8[rr][k]) : 0u;   // (a validated frame has none above)
                 incl[rr][k] = wave_scan_incl((PIX == 1u ? r == 0u : (tid & 15u) == 0u) ? d : 0u);   // the tile's first lane
-                const uint32_t pw = wave_sum(__builtin_amdgcn_sad_u8(m.pre[rr][k] & pre_keep(m.fb[k], rr), 0u, 0u));
+                const uint32_t pw = wave_sum(__builtin_amdgcn_sad_u8(m.pre[rr][k] & pre_keep(m.fb[k], cb[rr], npre[rr], tid), 0u, 0u));
                 if (lane == 63u) s_wsum[buf][k][rr][0][wave] = incl[rr][k];
                 if (lane == 0u) s_wsum[buf][k][rr][1][wave] = pw;
             }
@@ -233,7 +218,7 @@ __global__ __launch_bounds__(kProjThreads) void pairs_kernel(PairsParams p) {
             for (uint32_t k = 0; k < G; k++) {
                 uint32_t wbase = 0, PRE = 0;
 #pragma unroll
-                for (uint32_t w = 0; w < kPairsWaves; w++) {
+                for (uint32_t w = 0; w < kProjWaves; w++) {
                     wbase += w < wave ? s_wsum[buf][k][rr][0][w] : 0u;
                     PRE += s_wsum[buf][k][rr][1][w];
                 }
@@ -259,8 +244,7 @@ __global__ __launch_bounds__(kProjThreads) void pairs_kernel(PairsParams p) {
                     }
                 }
                 q.a0[rr][k] = w0; q.a1[rr][k] = w1; q.a2[rr][k] = w2;
-                if constexpr (PIX == 1u) q.dms[rr][k] = d | (m.ml[rr][k] << 8) | (sh << 16);
-                else q.dms[rr][k] = d | (sh << 8) | (m.ml[rr][k] << 16) | (m.mh[rr][k] << 24);
+                q.dms[rr][k] = pack_dms<PIX>(d, sh, m.ml[rr][k], m.mh[rr][k]);
             }
         }
         buf ^= 1u;
@@ -268,23 +252,7 @@ __global__ __launch_bounds__(kProjThreads) void pairs_kernel(PairsParams p) {
 
     // the lane's (half) row of frame k of prefix rr: two dwords of four U8 or two U16 pixels each
     auto decode = [&](const Pay &q, uint32_t rr, uint32_t k, uint32_t &v0, uint32_t &v1) __attribute__((always_inline)) {
-        if constexpr (PIX == 1u) {
-            const uint32_t d = q.dms[rr][k] & 0xFFu, sh = q.dms[rr][k] >> 16;
-            const uint32_t mm = ((q.dms[rr][k] >> 8) & 0xFFu) * 0x01010101u;
-            const uint64_t bits = (uint64_t)__builtin_amdgcn_alignbyte(q.a1[rr][k], q.a0[rr][k], sh) |
-                                  ((uint64_t)__builtin_amdgcn_alignbyte(q.a2[rr][k], q.a1[rr][k], sh) << 32);
-            uint32_t lo, hi;
-            expand_row(bits, d, lo, hi);
-            v0 = add_bytes(lo, mm);
-            v1 = add_bytes(hi, mm);
-        } else {
-            const uint32_t d = q.dms[rr][k] & 0xFFu, sh = (q.dms[rr][k] >> 8) & 0xFFu, so = 4u * hh * (d & 1u);
-            const uint32_t m32 = d >= 16u ? 0xFFFFu : (1u << d) - 1u, mn2 = (q.dms[rr][k] >> 16) * 0x00010001u;
-            const bool c2 = 2u * d >= 32u, c3 = 3u * d >= 32u;
-            const uint32_t x0 = __builtin_amdgcn_alignbyte(q.a1[rr][k], q.a0[rr][k], sh);
-            const uint32_t x1 = __builtin_amdgcn_alignbyte(q.a2[rr][k], q.a1[rr][k], sh);
-            cut_four16(__builtin_amdgcn_alignbit(x1, x0, so), x1 >> so, d, m32, mn2, c2, c3, v0, v1);
-        }
+        cut_row<PIX>(q.a0[rr][k], q.a1[rr][k], q.a2[rr][k], q.dms[rr][k], hh, v0, v1);
     };
 
     // the group's rows -> the band (in front of the group's barrier)

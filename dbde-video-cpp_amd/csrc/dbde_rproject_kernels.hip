@@ -30,23 +30,18 @@
 
 #include <type_traits>
 
-#include "dbde_bits.h"
-#include "dbde_device.h"
+#include "dbde_proj_pipeline.h"
 
 namespace dbde {
 
 namespace {
 
-constexpr uint32_t kRProjWaves = kProjThreads / 64u;
-
 template <uint32_t PIX> using RProjPix = typename std::conditional<PIX == 1u, uint8_t, uint16_t>::type;
 template <uint32_t PIX> using RProjSq = typename std::conditional<PIX == 1u, uint32_t, uint64_t>::type;
 
-__device__ __forceinline__ uint32_t readlane(uint32_t v, uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j); }
-
 // Frames of [0, p.n_frames) that the index accepted -> *p.out_count (added to it when accumulating).  Whole workgroup.
 __device__ void write_count(const ProjParams &p) {
-    __shared__ uint32_t s_c[kRProjWaves];
+    __shared__ uint32_t s_c[kProjWaves];
     const uint32_t tid = threadIdx.x;
     uint32_t c = 0;
     for (uint32_t g = tid; g < p.n_frames; g += kProjThreads) c += p.frame_ok[g] != 0u ? 1u : 0u;
@@ -55,7 +50,7 @@ __device__ void write_count(const ProjParams &p) {
     __syncthreads();
     if (tid == 0) {
         uint64_t total = 0;
-        for (uint32_t k = 0; k < kRProjWaves; k++) total += s_c[k];
+        for (uint32_t k = 0; k < kProjWaves; k++) total += s_c[k];
         *p.out_count = (p.accumulate ? *p.out_count : 0ull) + total;
     }
 }
@@ -121,7 +116,7 @@ __global__ __launch_bounds__(kProjThreads) void rproject_kernel(RProjParams rp) 
     constexpr uint32_t G = kRProjGroup, kDmax = 8u * PIX, kNpx = 8u / PIX;   // kNpx: pixels per lane
     constexpr uint32_t kCols = kRProjColsOf(PIX), kOwnedSlots = kCols / kNpx, kRowDw = kRProjRowDwords;
     constexpr uint32_t kPixMask = PIX == 1u ? 0xFFu : 0xFFFFu;
-    __shared__ uint32_t s_wsum[2][G][2][2][kRProjWaves];   // per group of frames (double-buffered), per tile row: wave depth totals, sums in front
+    __shared__ uint32_t s_wsum[2][G][2][2][kProjWaves];   // per group of frames (double-buffered), per tile row: wave depth totals, sums in front
     __shared__ __attribute__((aligned(8))) uint32_t s_band[2][G][kRProjBandRows][kRowDw];
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -204,16 +199,6 @@ __global__ __launch_bounds__(kProjThreads) void rproject_kernel(RProjParams rp) 
             }
         }
     };
-    // the mask of the depth bytes [cb, cb + npre) in this lane's pre dword, cb being byte cb of the frame's depths
-    auto pre_keep = [&](const uint8_t *fb, uint32_t cb, uint32_t npre) __attribute__((always_inline)) -> uint32_t {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(fb + 24 + cb);
-        const uint32_t head = (uint32_t)(a & 3u), ndw = (head + npre + 3u) >> 2;
-        if (tid >= ndw) return 0u;
-        const uint32_t lo = 4u * tid < head ? head - 4u * tid : 0u;   // bytes in front of cb
-        const uint32_t hi = head + npre - 4u * tid;                   // bytes before the piece
-        return (hi >= 4u ? ~0u : (1u << (8u * hi)) - 1u) & ~((1u << (8u * lo)) - 1u);
-    };
-
     // the group's tile offsets (the group's one barrier, which also publishes the band written in front of it) and its
     // payload loads
     uint32_t buf = 0;
@@ -243,7 +228,7 @@ __global__ __launch_bounds__(kProjThreads) void rproject_kernel(RProjParams rp) 
                 const uint32_t d = t < nt ? (m.d8[rr][k] > kDmax ? kDmax : m.d8[rr][k]) : 0u;   // (a validated frame has none above)
                 const uint32_t sc = wave_scan_incl((PIX == 1u ? r == 0u : (tid & 15u) == 0u) ? d : 0u);   // the tile's first lane
                 if (rr) incl1[k] = sc; else incl0[k] = sc;
-                const uint32_t pw = wave_sum(__builtin_amdgcn_sad_u8(m.pre[rr][k] & pre_keep(fb, cb, npre), 0u, 0u));
+                const uint32_t pw = wave_sum(__builtin_amdgcn_sad_u8(m.pre[rr][k] & pre_keep(fb, cb, npre, tid), 0u, 0u));
                 if (lane == 63u) s_wsum[buf][k][rr][0][wave] = sc;
                 if (lane == 0u) s_wsum[buf][k][rr][1][wave] = pw;
             }
@@ -258,7 +243,7 @@ __global__ __launch_bounds__(kProjThreads) void rproject_kernel(RProjParams rp) 
             const uint32_t rr = (sy + rc) >> 3, trow = (sy + rc) & 7u;   // this lane's tile row of the band, its row of the tile
             uint32_t wbase = 0, PRE = 0;
 #pragma unroll
-            for (uint32_t w = 0; w < kRProjWaves; w++) {
+            for (uint32_t w = 0; w < kProjWaves; w++) {
                 wbase += w < wave ? s_wsum[buf][k][rr][0][w] : 0u;
                 PRE += s_wsum[buf][k][rr][1][w];
             }
@@ -299,23 +284,7 @@ __global__ __launch_bounds__(kProjThreads) void rproject_kernel(RProjParams rp) 
         for (uint32_t k = 0; k < G; k++) {
             if (!readlane(m.w.ok, k)) continue;   // rejected (or past the segment): contributes nothing
             uint32_t v0, v1;
-            if constexpr (PIX == 1u) {
-                const uint32_t d = q.dms[k] & 0xFFu, sh = q.dms[k] >> 16;
-                const uint32_t mm = ((q.dms[k] >> 8) & 0xFFu) * 0x01010101u;
-                const uint64_t bits = (uint64_t)__builtin_amdgcn_alignbyte(q.a1[k], q.a0[k], sh) |
-                                      ((uint64_t)__builtin_amdgcn_alignbyte(q.a2[k], q.a1[k], sh) << 32);
-                uint32_t lo, hi;
-                expand_row(bits, d, lo, hi);
-                v0 = add_bytes(lo, mm);
-                v1 = add_bytes(hi, mm);
-            } else {
-                const uint32_t d = q.dms[k] & 0xFFu, sh = (q.dms[k] >> 8) & 0xFFu, so = 4u * hh * (d & 1u);
-                const uint32_t m32 = d >= 16u ? 0xFFFFu : (1u << d) - 1u, mn2 = (q.dms[k] >> 16) * 0x00010001u;
-                const bool c2 = 2u * d >= 32u, c3 = 3u * d >= 32u;
-                const uint32_t x0 = __builtin_amdgcn_alignbyte(q.a1[k], q.a0[k], sh);
-                const uint32_t x1 = __builtin_amdgcn_alignbyte(q.a2[k], q.a1[k], sh);
-                cut_four16(__builtin_amdgcn_alignbit(x1, x0, so), x1 >> so, d, m32, mn2, c2, c3, v0, v1);
-            }
+            cut_row<PIX>(q.a0[k], q.a1[k], q.a2[k], q.dms[k], hh, v0, v1);
             *reinterpret_cast<uint2 *>(&s_band[bb][k][r][2u * slot]) = make_uint2(v0, v1);
         }
     };

@@ -3,7 +3,7 @@
 // image is written).  DESIGN.md 4.17.
 //
 // wproject_kernel<R, PIX>: R = 1..8 regressors, PIX = 1 for DBDE frames, PIX = 2 for DBDE16 frames.  The launch shape
-// and the load pipeline are project_kernel's (dbde_project_kernels.hip): one 256-lane workgroup per (frame segment,
+// and the load pipeline are project_kernel's (dbde_proj_pipeline.h): one 256-lane workgroup per (frame segment,
 // window tile row, piece of kProjTilesOf(PIX) tiles), one lane per tile row (PIX 2: per half row), the segment's frames
 // walked in groups of kWProjGroup with the payload loads of group k + 1, the depth / minimum loads of group k + 2 and
 // the per-frame words of group k + 3 in flight while group k is folded in, one barrier per group.  The body is this
@@ -22,20 +22,15 @@
 // partial 0.  That order is part of the contract (include/dbde_hip.h).
 #include "dbde_wproject_kernels.h"
 
-#include "dbde_bits.h"
-#include "dbde_device.h"
+#include "dbde_proj_pipeline.h"
 
 namespace dbde {
 
 namespace {
 
-constexpr uint32_t kWProjWaves = kProjThreads / 64u;
-
-__device__ __forceinline__ uint32_t readlane(uint32_t v, uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j); }
-
 // Frames of [0, p.n_frames) that the index accepted -> *p.out_count (added to it when accumulating).  Whole workgroup.
 __device__ void write_count(const WProjParams &p) {
-    __shared__ uint32_t s_c[kWProjWaves];
+    __shared__ uint32_t s_c[kProjWaves];
     const uint32_t tid = threadIdx.x;
     uint32_t c = 0;
     for (uint32_t g = tid; g < p.n_frames; g += kProjThreads) c += p.frame_ok[g] != 0u ? 1u : 0u;
@@ -44,7 +39,7 @@ __device__ void write_count(const WProjParams &p) {
     __syncthreads();
     if (tid == 0) {
         uint64_t total = 0;
-        for (uint32_t k = 0; k < kWProjWaves; k++) total += s_c[k];
+        for (uint32_t k = 0; k < kProjWaves; k++) total += s_c[k];
         *p.out_count = (p.accumulate ? *p.out_count : 0ull) + total;
     }
 }
@@ -56,7 +51,7 @@ __global__ __launch_bounds__(kProjThreads) void wproject_kernel(WProjParams p) {
     static_assert(PIX == 1u || PIX == 2u, "U8 or U16 pixels");
     static_assert(R >= 1u && R <= kWProjMaxRegressors && R * kWProjGroup <= 32u, "a group's weights fit lanes 0-31");
     constexpr uint32_t G = kWProjGroup, kTiles = kProjTilesOf(PIX), kDmax = 8u * PIX, kNpx = 8u / PIX;   // kNpx: pixels per lane
-    __shared__ uint32_t s_wsum[2][G][2][kWProjWaves];   // per group of frames (double-buffered): wave depth totals, sums in front
+    __shared__ uint32_t s_wsum[2][G][2][kProjWaves];   // per group of frames (double-buffered): wave depth totals, sums in front
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     // tile of the piece, row of the tile, half of the row (PIX 2)
@@ -147,16 +142,6 @@ __global__ __launch_bounds__(kProjThreads) void wproject_kernel(WProjParams p) {
             }
         }
     };
-    // the mask of the depth bytes [cb, pos0) in this lane's pre dword of frame fb
-    auto pre_keep = [&](const uint8_t *fb) __attribute__((always_inline)) -> uint32_t {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(fb + 24 + cb);
-        const uint32_t head = (uint32_t)(a & 3u), ndw = (head + npre + 3u) >> 2;
-        if (tid >= ndw) return 0u;
-        const uint32_t lo = 4u * tid < head ? head - 4u * tid : 0u;   // bytes in front of cb
-        const uint32_t hi = head + npre - 4u * tid;                   // bytes before pos0
-        return (hi >= 4u ? ~0u : (1u << (8u * hi)) - 1u) & ~((1u << (8u * lo)) - 1u);
-    };
-
     // the group's tile offsets (one barrier) and its payload loads
     uint32_t buf = 0;
     auto issue_payload = [&](const Meta &m, Pay &q) __attribute__((always_inline)) {
@@ -173,7 +158,7 @@ __global__ __launch_bounds__(kProjThreads) void wproject_kernel(WProjParams p) {
         for (uint32_t k = 0; k < G; k++) {
             const uint32_t d = has_tile ? (m.d8[k] > kDmax ? kDmax : m.d8[k]) : 0u;   // (a validated frame has none above)
             incl[k] = wave_scan_incl((PIX == 1u ? r == 0u : (tid & 15u) == 0u) ? d : 0u);   // the tile's first lane
-            const uint32_t pw = wave_sum(__builtin_amdgcn_sad_u8(m.pre[k] & pre_keep(m.fb[k]), 0u, 0u));
+            const uint32_t pw = wave_sum(__builtin_amdgcn_sad_u8(m.pre[k] & pre_keep(m.fb[k], cb, npre, tid), 0u, 0u));
             if (lane == 63u) s_wsum[buf][k][0][wave] = incl[k];
             if (lane == 0u) s_wsum[buf][k][1][wave] = pw;
         }
@@ -182,7 +167,7 @@ __global__ __launch_bounds__(kProjThreads) void wproject_kernel(WProjParams p) {
         for (uint32_t k = 0; k < G; k++) {
             uint32_t wbase = 0, PRE = 0;
 #pragma unroll
-            for (uint32_t w = 0; w < kWProjWaves; w++) {
+            for (uint32_t w = 0; w < kProjWaves; w++) {
                 wbase += w < wave ? s_wsum[buf][k][0][w] : 0u;
                 PRE += s_wsum[buf][k][1][w];
             }
@@ -224,31 +209,18 @@ __global__ __launch_bounds__(kProjThreads) void wproject_kernel(WProjParams p) {
 #pragma unroll
         for (uint32_t k = 0; k < G; k++) {
             if (!m.ok[k]) continue;   // rejected (or past the segment): no FMA, its weights stay unused
+            uint32_t px[2];
+            cut_row<PIX>(q.a0[k], q.a1[k], q.a2[k], q.dms[k], hh, px[0], px[1]);
             if constexpr (PIX == 1u) {
-                const uint32_t d = q.dms[k] & 0xFFu, sh = q.dms[k] >> 16;
-                const uint32_t mm = ((q.dms[k] >> 8) & 0xFFu) * 0x01010101u;
-                const uint64_t bits = (uint64_t)__builtin_amdgcn_alignbyte(q.a1[k], q.a0[k], sh) |
-                                      ((uint64_t)__builtin_amdgcn_alignbyte(q.a2[k], q.a1[k], sh) << 32);
-                uint32_t px[2];
-                expand_row(bits, d, px[0], px[1]);
-                px[0] = add_bytes(px[0], mm);
-                px[1] = add_bytes(px[1], mm);
 #pragma unroll
                 for (uint32_t h = 0; h < 2; h++)
 #pragma unroll
                     for (uint32_t i = 0; i < 4; i++) fold(m, k, 4u * h + i, (px[h] >> (8u * i)) & 0xFFu);
             } else {
-                const uint32_t d = q.dms[k] & 0xFFu, sh = (q.dms[k] >> 8) & 0xFFu, so = 4u * hh * (d & 1u);
-                const uint32_t m32 = d >= 16u ? 0xFFFFu : (1u << d) - 1u, mn2 = (q.dms[k] >> 16) * 0x00010001u;
-                const bool c2 = 2u * d >= 32u, c3 = 3u * d >= 32u;
-                const uint32_t x0 = __builtin_amdgcn_alignbyte(q.a1[k], q.a0[k], sh);
-                const uint32_t x1 = __builtin_amdgcn_alignbyte(q.a2[k], q.a1[k], sh);
-                uint32_t e[2];
-                cut_four16(__builtin_amdgcn_alignbit(x1, x0, so), x1 >> so, d, m32, mn2, c2, c3, e[0], e[1]);
 #pragma unroll
                 for (uint32_t j = 0; j < 2; j++)
 #pragma unroll
-                    for (uint32_t i = 0; i < 2; i++) fold(m, k, 2u * j + i, (e[j] >> (16u * i)) & 0xFFFFu);
+                    for (uint32_t i = 0; i < 2; i++) fold(m, k, 2u * j + i, (px[j] >> (16u * i)) & 0xFFFFu);
             }
         }
     };
