@@ -176,9 +176,9 @@ class Lag:
     def test_extreme_products_and_differences(self, codec):
         """Constant 0 and constant 255 / 65,535 alternating.  At 16 bits and n = 70 the largest per-lane sums are
         35 * 65,535^2 (product, sqdiff) and 69 * 65,535 (pairsum): a U32 pairsum or absdiff accumulator would have to
-        wrap to show, which takes more than 32,768 pairs of a segment, so the accumulator widths (DBDE16: U64 for
-        product, sqdiff and pairsum, 65,536 * 131,070 = 2^33) are a review item, not a test; no 65,536-frame test is
-        built."""
+        wrap to show, which takes more than 32,768 pairs of a segment: the accumulator widths (DBDE16: U64 for
+        product, sqdiff and pairsum, 65,536 * 131,070 = 2^33) are tested by tests/test_gpu_bounds.py, whose segments
+        count 65,536 pairs."""
         lc.run(codec, lc.extremes(self.BITS), self.BITS, "extremes")
 
     def test_python_forms_and_argument_errors(self, dv, codec):

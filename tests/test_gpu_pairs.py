@@ -204,8 +204,8 @@ def test_sums_beyond_u32(dv, codec, cus):
     """66,052 frames of 8 x 16, all 255: more than a segment may hold (65,536), and the smallest count whose sum
     n * 65,025 = 4,294,981,300 exceeds 2^32 = 4,294,967,296 (65,537 frames give 4,261,543,425, still below it), through
     U32 partials of several segments and the combine.  On a device of many compute units the plan cuts far more than
-    the two segments the bound asks for, so no partial comes near 2^32 here; the per-lane bound is the header's
-    arithmetic (65,536 * 255^2 < 2^32)."""
+    the two segments the bound asks for, so no partial comes near 2^32 here: tests/test_gpu_bounds.py fills the
+    per-lane accumulators to the header's bound (65,536 frames in one segment, 65,536 * 255^2 < 2^32)."""
     import torch
     n, W, H = 66052, 8, 16
     assert (n - 1) * 65025 < 2 ** 32 < n * 65025
